@@ -17,7 +17,11 @@ images of a step are sharded camera-major over the ranks, ONE all-gather of desc
 place, the (frame, keyframe) pairs are sharded.  Per-GPU work is fixed (F multi-frames and F x keyframes pairs per GPU): weak scaling.  N = 1 runs the
 same code without the collective.  Barrier + max-over-ranks timing.
 
-Legs of the default run besides the headline (each checked against the oracle): `e2e` — the same step with host buffers at the boundary (images up through the SDMA
+A plain run (`python bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps, writes the last timed step's outputs if --dump-outputs
+DIR is given, and prints the result line.  Everything else needs --full: the oracle check of the timed output, the roofline block (per-kernel passes of its
+own), and for the default workload the further legs below and the CPU baseline.
+
+Legs of a --full run besides the headline (each checked against the oracle): `e2e` — the same step with host buffers at the boundary (images up through the SDMA
 engine on a stream picked by the library's hardware-queue probe, results down through mcs_copy_narrow on the context's result stream; --e2e-sweep "h2d:d2h,..."
 and the MCS_E2E_* variables are its A/B switches, tools/ab_e2e.sh) —, configs[2] at 16 multi-frames per step with its own e2e leg, the reference's
 shipped ORB settings, the N > 1 exchange path at world size 1 over RCCL, and last the CPU baseline.  Every leg runs `settle_steps` untimed steps in front of its
@@ -77,11 +81,16 @@ def parse(argv=None):
     ap.add_argument("--height", type=int, default=0)
     ap.add_argument("--keyframes", type=int, default=-1, help="stored keyframes every multi-frame is matched against (0 = the multi-frame before it)")
     ap.add_argument("--topk", type=int, default=32)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the e2e / configs[2] / shipped-settings legs of the default run")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the oracle check of the timed output, the roofline block (per-kernel passes of "
+                                                        "their own) and, for the default workload, the e2e / configs[2] / shipped-settings / latency / batch-sweep / "
+                                                        "RCCL world-1 legs and the CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps write what the last timed step handed its caller as DIR/<name>.npy "
+                                                                      "(float32 / float64, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="(--full) skip the e2e / configs[2] / shipped-settings legs of the default run")
     ap.add_argument("--cpu-frames", type=int, default=0, help="multi-frames in the bounded CPU-baseline sample (default: 3 x cpu quota, >= 48)")
-    ap.add_argument("--check", action="store_true", help="(default; kept for old command lines) verify the timed output against the oracle")
-    ap.add_argument("--no-check", action="store_true", help="skip the oracle check of the timed output (profiling runs)")
+    ap.add_argument("--check", action="store_true", help="verify the timed output against the oracle (implied by --full)")
+    ap.add_argument("--no-check", action="store_true", help="skip the oracle check of the timed output, also under --full (profiling runs)")
     ap.add_argument("--e2e-sweep", default="", help="A/B of the e2e leg's copy mechanism: comma list of H2D:D2H settings, each 'runtime' or a workgroup count "
                                                     "(e.g. runtime:runtime,16:16,16:runtime); runs only the headline job and those e2e legs")
     ap.add_argument("--dry-run", action="store_true", help="no GPU: build the multi-GPU plan (slabs, exchange runs, pair ownership, buffer sizes) of every workload for "
@@ -699,9 +708,52 @@ def roofline_block(sp, job, kern, feats_local, pairs_local):
     return out
 
 
-def run_job(e, sp, args, steps, warmup, want_roofline=True, check=True):
+DUMP_BYTES = 60 * 10 ** 6   # --dump-outputs: the most a dump may write (under 64 MB with the .npy headers)
+
+
+def dump_outputs(e, job, d):
+    """--dump-outputs DIR: what the last timed step handed its caller — the buffer set whose search that step issued (Job.step: results one step late) — as
+    DIR/<name>.npy: per image the keypoint count, and over the valid rows the keypoint records (x, y, size, angle, response, octave, class_id), rays,
+    descriptors and (mdBRIEF) masks as the search read them, then the search's match indices and per-pair match counts.  Descriptor and mask bytes are
+    stored as little-endian 16-bit words, every integer exactly in float32; rays float64; matches one row per (frame, keyframe) pair.  Over DUMP_BYTES in all,
+    every array of 1 MiB or more keeps the same fraction of its rows, drawn with a fixed seed (the drawn row numbers in <name>_rows.npy)."""
+    lay, view = job.lay, job.view
+    b = job.last()
+    e.torch.cuda.synchronize(e.dev)
+    nkp = b.nkp.cpu().numpy().astype(np.int64)
+    own = np.concatenate([i * job.cap + np.arange(n) for i, n in enumerate(nkp)])   # rows of this rank's images that hold a keypoint
+    kp = b.kps.cpu().numpy().view(np.uint8).reshape(-1, 28)[own].copy().view(e.mcs.KP_DTYPE).reshape(-1)
+    valid = b.valid.cpu().numpy().reshape(-1) != 0
+    rows = b.G.cpu().numpy().reshape(view.images_total * lay.rows_img, lay.row_stride)[valid]
+    ds = lay.desc_size
+    out = {"keypoint_counts": nkp.astype(np.float32),
+           "keypoints": np.stack([kp[f].astype(np.float32) for f in kp.dtype.names], axis=1),
+           "rays": b.rays.cpu().numpy()[own],
+           "descriptors": np.ascontiguousarray(rows[:, :ds]).view("<u2").astype(np.float32)}
+    if job.masks_on:
+        out["masks"] = np.ascontiguousarray(rows[:, ds:2 * ds]).view("<u2").astype(np.float32)
+    match = b.match.cpu().numpy()
+    out["matches"] = match.astype(np.float32 if np.abs(match).max(initial=0) < (1 << 24) else np.float64).reshape(-1, lay.rows_frame)
+    out["match_counts"] = b.nmatch.cpu().numpy().astype(np.float32)
+    if sum(a.nbytes for a in out.values()) > DUMP_BYTES:
+        big = [name for name in out if out[name].nbytes >= 1 << 20]
+        room = DUMP_BYTES - sum(a.nbytes for name, a in out.items() if name not in big) - 8 * sum(len(out[name]) for name in big)   # less the row numbers (float64)
+        keep = room / sum(out[name].nbytes for name in big)
+        rng = np.random.default_rng(0)
+        for name in big:
+            n = len(out[name])
+            r = np.sort(rng.choice(n, max(1, int(n * keep)), replace=False))
+            out[name], out[name + "_rows"] = out[name][r], r.astype(np.float64)
+    os.makedirs(d, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
+def run_job(e, sp, args, steps, warmup, want_roofline=True, check=True, dump=None):
     job = Job(e, sp)
     elapsed = timed(e, job.step, warmup, steps, job.status)
+    if dump and e.rank == 0:
+        dump_outputs(e, job, dump)
     x0 = job.ex.describe_stats()[0]
     job.step()
     exact_kp = job.ex.describe_stats()[0] - x0   # keypoints the guarded fast descriptor pass handed to the exact pass in one (untimed) step
@@ -1367,8 +1419,9 @@ def main():
     if args.exchange == "nccl1":
         force_exchange_world1(e)
     sp = Spec(args, e.world)
-    check = not args.no_check
-    job, out = run_job(e, sp, args, args.steps, args.warmup, check=check)
+    # a plain run times the headline and nothing else; the oracle check (--check) and everything below that is not the headline need --full
+    check = (args.full or args.check) and not args.no_check
+    job, out = run_job(e, sp, args, args.steps, args.warmup, want_roofline=args.full, check=check, dump=args.dump_outputs)
     headline = args.workload == "stream" and args.mode == "mdbrief" and not (args.ncam or args.width or args.height or args.nfeatures or args.keyframes >= 0
                                                                                or args.frames or args.exchange != "auto")
     out["cpu_baseline"] = None   # filled in LAST (below): the oracle's OpenMP threads keep spinning for a while after their last parallel region, on the same 16 CPUs
@@ -1382,7 +1435,7 @@ def main():
             r = run_e2e(e, sp, args.steps, args.warmup, check)
             checks.append(r["oracle_check"])
             out["e2e_sweep"][item] = {k: r[k] for k in ("value", "ms_per_step", "oracle_check", "h2d_GBps_alone", "d2h_GBps_alone")}
-    elif e.world == 1 and headline and not args.no_secondary:
+    elif e.world == 1 and headline and args.full and not args.no_secondary:
         # further legs of the default run, each bounded: host buffers at the boundary (configs[1] and [2]); the matcher-dominated BASELINE configs[2]; the
         # reference's shipped settings; the N > 1 code path at world size 1 over RCCL
         s2 = min(args.steps, 10)
@@ -1417,7 +1470,7 @@ def main():
         except Exception as ex:   # an environment without a usable RCCL is reported, not hidden; a wrong RESULT is a failed check above
             out["exchange_world1"] = {"error": "%s: %s" % (type(ex).__name__, str(ex)[:300])}
         e.exchange = False
-    if e.rank == 0 and e.world == 1 and headline and not args.no_cpu_baseline:
+    if e.rank == 0 and e.world == 1 and headline and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, e, sp, job)
         orc = cpu.pop("_oracle_outputs", None)
         if check and orc is not None and getattr(job, "snapshot", None) is not None:

@@ -1,16 +1,17 @@
-"""CPU: vocabulary loader + oracle DBoW2 descent on a hand-built tree, a synthetic vocabulary and, where the reference
-checkout exists, the shipped small_orb_omni_voc_9_6.yml."""
+"""CPU: vocabulary loader + oracle DBoW2 descent on a hand-built tree, a synthetic vocabulary and the shipped
+small_orb_omni_voc_9_6.yml (stored gzip-compressed under tests/golden/)."""
+import gzip
 import importlib
 import os
+import shutil
 
 import numpy as np
-import pytest
 
 import oracle_lib as O
 import vocab_synth
 
 io = importlib.import_module("multicol-slam_amd.io")
-REAL = "/root/reference/Examples/small_orb_omni_voc_9_6.yml"
+REAL = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "small_orb_omni_voc_9_6.yml.gz")
 
 
 def bits(n):
@@ -60,9 +61,11 @@ def test_synthetic_vocabulary_round_trip(tmp_path):
     assert np.array_equal(nid, anc)
 
 
-@pytest.mark.skipif(not os.path.exists(REAL), reason="reference checkout not present (GPU box)")
-def test_shipped_vocabulary_parses():
-    v = io.load_vocabulary(REAL)
+def test_shipped_vocabulary_parses(tmp_path):
+    path = str(tmp_path / "small_orb_omni_voc_9_6.yml")
+    with gzip.open(REAL, "rb") as src, open(path, "wb") as dst:
+        shutil.copyfileobj(src, dst)
+    v = io.load_vocabulary(path)
     assert (v["k"], v["L"]) == (9, 6) and len(v["node_desc"]) == 8823 and v["n_words"] == 6999
     assert np.diff(v["child_off"]).max() == 9 and v["child_off"][1] == 9
     assert (v["weight"] > 0).sum() == 5676 and abs(v["weight"].max() - 2.6390573296152584) == 0

@@ -1,7 +1,7 @@
 """-m gpu: the bench's own jobs at BASELINE.json's full sizes, one step each, checked against the oracle — and the N > 1 code path on real RCCL.
 
 bench.py runs in a subprocess (it brings torch, which must not share a process with the ctypes-loaded library of the other tests, tests/gpu_common.py).
-Every run prints one JSON line; `oracle_check` is bench.check_against_oracle: two multi-frames (every camera: keypoint records, descriptors, masks,
+Every run prints one JSON line; the runs here that read the oracle check or the roofline block ask for them with --full.  `oracle_check` is bench.check_against_oracle: two multi-frames (every camera: keypoint records, descriptors, masks,
 counts) and the match indices of >= 2 (frame, keyframe) pairs — reference semantics src/cORBmatcher.cpp:179-323 (SearchByBoW(KF,F), vocabulary
 restriction removed) and :885-966 (SearchByBoW(KF,KF)) — bit for bit.  A failed check also makes bench.py exit non-zero.
 
@@ -11,6 +11,7 @@ restriction removed) and :885-966 (SearchByBoW(KF,KF)) — bit for bit.  A faile
   nccl1       the step of the N > 1 runs — separate send buffer, asynchronous all_gather_into_tensor on RCCL's stream, work.wait(), row flags, three
               buffer sets in rotation, matching one step late — at world size 1 over the nccl backend, stream and database workloads
 """
+import importlib
 import json
 import os
 import subprocess
@@ -26,7 +27,7 @@ def run_bench(*args, timeout=600):
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     env.setdefault("MASTER_ADDR", "127.0.0.1")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-secondary", *args], cwd=ROOT, env=env,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-secondary", *args], cwd=ROOT, env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=timeout)
     assert p.returncode == 0, "bench.py %s failed (rc %d):\n%s\n%s" % (" ".join(args), p.returncode, p.stdout[-2000:], p.stderr[-4000:])
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -62,10 +63,10 @@ def test_exchange_path_on_rccl_at_world_size_1(args):
 
 
 def test_default_run_checks_every_leg():
-    """the driver's command line (plus a short CPU sample): every leg carries oracle_check true, the world-1 RCCL leg ran"""
+    """the driver's command line with --full (plus a short CPU sample): every leg carries oracle_check true, the world-1 RCCL leg ran"""
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--cpu-frames", "8"], cwd=ROOT, env=env,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--cpu-frames", "8", "--full"], cwd=ROOT, env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-4000:]
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
@@ -81,6 +82,38 @@ def test_default_run_checks_every_leg():
         assert out[k]
 
 
+def test_plain_run_times_the_headline_and_dumps_its_outputs(tmp_path):
+    """a plain run: the headline alone (no oracle check, no roofline passes, no further legs), --steps timed steps, and --dump-outputs writes what the last
+    timed step handed its caller — float arrays within 64 MB, the first image's keypoints and descriptors equal to the oracle's"""
+    import numpy as np
+    import oracle_lib as O
+    synth = importlib.import_module("multicol-slam_amd.synth")
+    env = dict(os.environ)
+    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    d = str(tmp_path / "out")
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", d], cwd=ROOT, env=env,
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-4000:]
+    out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0 and out["unit"] == "Mfeatures/s" and out["higher_is_better"] is True
+    assert out["roofline"] is None and out["cpu_baseline"] is None and "oracle_check" not in out and "e2e" not in out and "secondary" not in out
+    files = sorted(os.listdir(d))
+    assert {"keypoint_counts.npy", "keypoints.npy", "rays.npy", "descriptors.npy", "masks.npy", "matches.npy", "match_counts.npy"} <= set(files), files
+    arrs = {f[:-4]: np.load(os.path.join(d, f)) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+    assert sum(os.path.getsize(os.path.join(d, f)) for f in files) <= 64 * 10 ** 6
+    n = arrs["keypoint_counts"].astype(np.int64)
+    assert len(n) == 64 * 3 and len(arrs["keypoints"]) == len(arrs["rays"]) == len(arrs["descriptors"]) == n.sum()
+    assert arrs["match_counts"].sum() > 0
+    # image 0 of the slab is camera 0 of multi-frame 0
+    cam = synth.lafida_cameras()[0]
+    ok, od, om = O.Extractor(nfeatures=1000, do_dBrief=1, learnMasks=1)(synth.stream_image(0, 0, cam, 64), synth.mirror_mask(cam), O.make_ocam(cam))
+    assert n[0] == len(ok)
+    assert np.array_equal(arrs["keypoints"][:n[0]], np.stack([ok[f].astype(np.float32) for f in ok.dtype.names], axis=1))
+    assert np.array_equal(arrs["descriptors"][:n[0]], od.view("<u2").astype(np.float32))
+    assert np.array_equal(arrs["masks"][:n[0]], om.view("<u2").astype(np.float32))
+
+
 @pytest.mark.parametrize("n,args", [(2, []), (3, ["--workload", "db", "--frames", "4"])])
 def test_gpus_n_starts_n_ranks_by_itself(n, args):
     """`python bench.py --gpus N` with no launcher around it starts N ranks (here on one shared GPU over gloo: a functional run of the N > 1 step) and rank 0
@@ -89,7 +122,7 @@ def test_gpus_n_starts_n_ranks_by_itself(n, args):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
     env["MCS_BENCH_SHARE_GPU"] = "1"
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--no-secondary", *args],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "3", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-secondary", *args],
                        cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

@@ -104,7 +104,7 @@ def test_pipelined_loop_with_a_wide_band_reproduces_the_oracle(args):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     env.setdefault("MASTER_ADDR", "127.0.0.1")
     env["MCS_BENCH_TIE_BAND"] = "2e-4"
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-secondary", "--steps", "4", "--warmup", "2", *args], cwd=ROOT, env=env,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-secondary", "--steps", "4", "--warmup", "2", *args], cwd=ROOT, env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-4000:]
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])

@@ -5,8 +5,10 @@ oracle/_ref/libmcs_ref.so is /root/reference/src/mdBRIEFextractorOct.cpp + cam_m
 forward to the oracle's restatements).  Where that library exists the oracle must reproduce it bit for bit; everywhere it must reproduce the
 golden vectors tools/gen_golden_ref.py stored from it."""
 import ctypes as C
+import gzip
 import importlib
 import os
+import shutil
 import sys
 
 import numpy as np
@@ -139,10 +141,10 @@ def test_bow_transform_equals_dbow2_code(which, tmp_path):
     multicol-slam_amd.io + the oracle's descent + the host-side map arithmetic."""
     import vocab_synth
     io = importlib.import_module("multicol-slam_amd.io")
-    if which == "shipped":
-        path = "/root/reference/Examples/small_orb_omni_voc_9_6.yml"
-        if not os.path.exists(path):
-            pytest.skip("reference checkout not present")
+    if which == "shipped":   # stored gzip-compressed under tests/golden/
+        path = str(tmp_path / "small_orb_omni_voc_9_6.yml")
+        with gzip.open(os.path.join(ROOT, "tests", "golden", "small_orb_omni_voc_9_6.yml.gz"), "rb") as src, open(path, "wb") as dst:
+            shutil.copyfileobj(src, dst)
     else:
         path = str(tmp_path / "voc.yml")
         vocab_synth.write_vocabulary(path, k=9, L=5, seed=3)

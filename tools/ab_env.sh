@@ -1,7 +1,7 @@
 #!/bin/bash
 args=$1; shift
 for envs in "$@"; do
-  env $envs timeout 600 python bench.py --no-cpu-baseline --no-secondary $args > /tmp/ab.json 2>/tmp/ab.err
+  env $envs timeout 600 python bench.py --full --no-cpu-baseline --no-secondary $args > /tmp/ab.json 2>/tmp/ab.err
   python - "$envs" <<'PY'
 import json, sys
 try:

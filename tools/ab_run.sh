@@ -3,7 +3,7 @@
 args=$1; shift
 for g in "$@"; do
   lib=$PWD/gpurun_ab/libmcs_hip_$g.so
-  MCS_HIP_LIB=$lib timeout 600 python bench.py --no-cpu-baseline --no-secondary $args > /tmp/ab.json 2>/tmp/ab.err
+  MCS_HIP_LIB=$lib timeout 600 python bench.py --full --no-cpu-baseline --no-secondary $args > /tmp/ab.json 2>/tmp/ab.err
   python - "$g" <<'PY'
 import json, sys
 try:

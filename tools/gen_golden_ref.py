@@ -6,11 +6,11 @@ cam_model_omni.cpp compiled unmodified against oracle/cvshim, see oracle/Makefil
 
 Writes tests/golden/ref_extract.npz: for a few small synthetic images and all three descriptor modes the keypoints, descriptors and masks the
 reference code produced.  tests/test_oracle_vs_ref.py checks the oracle against them everywhere (the GPU box has no reference checkout)."""
-import os, sys
+import importlib, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import ref_compare as R
+sys.path.insert(0, os.path.join(ROOT, "tools")); sys.path.insert(0, ROOT)
+synth = importlib.import_module("multicol-slam_amd.synth")   # (the cases and their inputs need no oracle/_ref: the test reads them where it is not built)
 
 CASES = [  # (name, frame, cam, width, height, nfeatures, scale, nlevels, fastTh, do_dBrief, learnMasks, descSize, use mask)
     ("orb_376x240", 0, 0, 376, 240, 300, 1.2, 8, 20, 0, 0, 32, 1),
@@ -33,13 +33,14 @@ CASES_DET = [
 
 
 def case_inputs(frame, cam_idx, w, h, use_mask):
-    cam = R.synth.scaled_camera(R.synth.lafida_cameras()[cam_idx], w, h)
-    img = R.synth.synth_image(frame, cam_idx, cam)
-    mask = np.ascontiguousarray(R.synth.mirror_mask(cam)) if use_mask else None
+    cam = synth.scaled_camera(synth.lafida_cameras()[cam_idx], w, h)
+    img = synth.synth_image(frame, cam_idx, cam)
+    mask = np.ascontiguousarray(synth.mirror_mask(cam)) if use_mask else None
     return cam, img, mask
 
 
 if __name__ == "__main__":
+    import ref_compare as R
     out = {}
     for name, frame, ci, w, h, nf, sf, nl, th, db, lm, ds, um in CASES:
         cam, img, mask = case_inputs(frame, ci, w, h, um)

@@ -3,7 +3,7 @@
 # then frame_latency runs 40 calls under rocprofv3 --kernel-trace --memory-copy-trace.  -> gpurun_out/latency_trace.txt (the last call's kernels and copies, us)
 set -u
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-rm -rf /tmp/latdir; MCS_KEEP_LATENCY_DIR=/tmp/latdir timeout 300 python bench.py --steps 2 --warmup 1 --no-cpu-baseline > /dev/null 2>&1
+rm -rf /tmp/latdir; MCS_KEEP_LATENCY_DIR=/tmp/latdir timeout 300 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > /dev/null 2>&1
 sed -i 's/^calls .*/calls 40/' /tmp/latdir/cfg.txt
 rm -rf /tmp/lattr; timeout 200 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d /tmp/lattr -- multicol-slam_amd/host/frame_latency /tmp/latdir/cfg.txt > /tmp/lat.json 2>/tmp/lat.err
 python - <<'P' > gpurun_out/latency_trace.txt

@@ -2,7 +2,7 @@
 # functional run of the N > 1 code path on a ONE-GPU box: N ranks share cuda:0, collectives over gloo (bench.py MCS_BENCH_SHARE_GPU=1); prints value / oracle_check per run
 for spec in "2 " "4 " "3 --workload db --frames 4" "8 --frames 8" "2 --workload rig --frames 2"; do
   set -- $spec; n=$1; shift
-  MCS_BENCH_SHARE_GPU=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29500 + n)) bench.py --gpus $n --steps 3 --warmup 2 --no-cpu-baseline --no-secondary "$@" > /tmp/sh_$n.json 2> /tmp/sh_$n.err
+  MCS_BENCH_SHARE_GPU=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29500 + n)) bench.py --full --gpus $n --steps 3 --warmup 2 --no-cpu-baseline --no-secondary "$@" > /tmp/sh_$n.json 2> /tmp/sh_$n.err
   python - "$n" "$*" <<'PY'
 import json, sys
 try:
