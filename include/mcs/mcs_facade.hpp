@@ -6,11 +6,13 @@
 //   MultiColSLAM::cORBmatcher           include/cORBmatcher.h:43-133 (brute-force and grid-window searches on flat views)
 //   MultiColSLAM::cMultiCamSys_ / LoadMCS / cORBVocabulary / ComputeDistinctiveDescriptors   the callers either side of the path
 //   MultiColSLAM::DescriptorDistance64[_Masked]   src/cORBmatcher.cpp:2438-2474
+//   MultiColSLAM::cMultiKeyFrameDatabase<KF>     include/cMultiKeyFrameDatabase.h, src/cMultiKeyFrameDatabase.cpp (the inverted file on the device)
 //
 // OpenCV is not a dependency: minimal layout-compatible PODs stand in for cv::KeyPoint / cv::Mat / cv::Vec3d.  With
 // -DMCS_WITH_OPENCV the adapters at the bottom accept the real types (cv::KeyPoint is 28 bytes, same layout).
 // Link with -lmcs_hip.  No CPU fallback: every call needs a HIP device and throws std::runtime_error otherwise.
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <cstdint>
@@ -19,6 +21,7 @@
 #include <cstring>
 #include <fstream>
 #include <map>
+#include <set>
 #include <sstream>
 #include <stdexcept>
 #include <string>
@@ -343,7 +346,35 @@ public:
 		}
 		if (h_) { mcs_vocabulary_destroy(h_); h_ = nullptr; }
 		mcs_throw(mcs_vocabulary_create(ctx_.h, nn, nodeDesc.data(), childOff.data(), childIdx.data(), m_L, &h_));
+		mcs_throw(mcs_vocabulary_set_words(h_, wordId.data(), weight.data()));
+		m_words = 0;
+		for (int32_t w : wordId) m_words = w + 1 > m_words ? w + 1 : m_words;
 	}
+	unsigned size() const { return (unsigned)m_words; }   // TemplatedVocabulary::size(): number of words
+	// score(a, b) = L1Scoring::score (ThirdParty/DBoW2/DBoW2/ScoringObject.cpp:23-66): one pair, shared words in ascending id order, vi from a.
+	// The loop closer's many pairs against stored keyframes go through cMultiKeyFrameDatabase::score on the device.
+	double score(const BowVector& a, const BowVector& b) const {
+		double s = 0;
+		auto i = a.begin(), j = b.begin();
+		while (i != a.end() && j != b.end()) {
+			if (i->first == j->first) { const double vi = i->second, wi = j->second; s += std::fabs(vi - wi) - std::fabs(vi) - std::fabs(wi); ++i; ++j; }
+			else if (i->first < j->first) i = a.lower_bound(j->first);
+			else j = b.lower_bound(i->first);
+		}
+		return -s / 2.0;
+	}
+	// the BowVector of transform() built on the device from the leaf nodes (mcs_bow_vector); v is identical to transform()'s
+	void transformBow(const uint8_t* descriptors, int n, int stride, BowVector& v, int levelsup = 4) {
+		v.clear();
+		if (!h_ || n <= 0) return;
+		std::vector<int32_t> leaf(n), nid(n), w(n);
+		std::vector<double> val(n);
+		int32_t nw = 0;
+		mcs_throw(mcs_bow_transform(h_, descriptors, n, stride, levelsup, MCS_MEM_HOST, leaf.data(), nid.data()));
+		mcs_throw(mcs_bow_vector(h_, leaf.data(), n, MCS_MEM_HOST, w.data(), val.data(), &nw));
+		for (int i = 0; i < nw; ++i) v.emplace_hint(v.end(), (unsigned)w[i], val[i]);
+	}
+	mcs_vocabulary* handle() const { return h_; }
 	// transform(features, v, fv, levelsup) (:1127-1205, TF_IDF weighting, L1 scoring): descriptors = n rows of `stride` >= 32 bytes
 	void transform(const uint8_t* descriptors, int n, int stride, BowVector& v, FeatureVector& fv, int levelsup) {
 		v.clear(); fv.clear();
@@ -358,7 +389,7 @@ public:
 		for (auto& e : v) norm += std::fabs(e.second);
 		if (norm > 0.0) for (auto& e : v) e.second /= norm;
 	}
-	int m_k = 0, m_L = 0;
+	int m_k = 0, m_L = 0, m_words = 0;
 	std::vector<uint8_t> nodeDesc; std::vector<int32_t> childOff, childIdx, wordId; std::vector<double> weight;
 private:
 	Context& ctx_;
@@ -569,5 +600,88 @@ inline int DescriptorDistance64Masked(Context& c, const uint64_t* descr_i, const
 	mcs_throw(mcs_descriptor_distance_masked(c.h, (const uint8_t*)descr_i, (const uint8_t*)descr_j, (const uint8_t*)mask_i, (const uint8_t*)mask_j, dim, &out));
 	return out;
 }
+
+// cMultiKeyFrameDatabase (src/cMultiKeyFrameDatabase.cpp) over mcs_kfdb_*.  KF: the caller's keyframe / frame type with `mnId` and
+// `mBowVec` (a std::map<word, value> as DBoW2::BowVector).  The covisibility the queries read (GetBestCovisibilityKeyFrames(10),
+// src/cMultiKeyFrame.cpp:231-240) is handed over with SetCovisibility whenever it changes; the connected set of a loop query is an argument.
+// Candidates come back as the KF pointers that were added or named as neighbours.
+template <class KF>
+class cMultiKeyFrameDatabase {
+public:
+	cMultiKeyFrameDatabase(Context& ctx, const cORBVocabulary& voc, int capacityHint = 0) { mcs_throw(mcs_kfdb_create(ctx.h, (int)voc.size(), capacityHint, &h_)); }
+	cMultiKeyFrameDatabase(Context& ctx, int nWords, int capacityHint = 0) { mcs_throw(mcs_kfdb_create(ctx.h, nWords, capacityHint, &h_)); }
+	~cMultiKeyFrameDatabase() { if (h_) mcs_kfdb_destroy(h_); }
+	cMultiKeyFrameDatabase(const cMultiKeyFrameDatabase&) = delete;
+	cMultiKeyFrameDatabase& operator=(const cMultiKeyFrameDatabase&) = delete;
+
+	void add(KF* pKF) {   // :43-51
+		std::vector<int32_t> off, w; std::vector<double> v; std::vector<int64_t> ids;
+		csr(std::vector<KF*>{pKF}, ids, off, w, v);
+		mcs_throw(mcs_kfdb_add(h_, 1, ids.data(), off.data(), w.data(), v.data(), MCS_MEM_HOST));
+		obj_[(int64_t)pKF->mnId] = pKF;
+	}
+	void erase(KF* pKF) { const int64_t id = (int64_t)pKF->mnId; mcs_throw(mcs_kfdb_erase(h_, 1, &id)); }   // :53-73
+	void clear() { mcs_throw(mcs_kfdb_clear(h_)); }                                                          // :75-79
+	void SetCovisibility(KF* pKF, const std::vector<KF*>& orderedNeighbours) {
+		const int64_t id = (int64_t)pKF->mnId;
+		int64_t nb[10] = {0};
+		const int32_t n = (int32_t)std::min<size_t>(orderedNeighbours.size(), 10);
+		for (int k = 0; k < n; ++k) { nb[k] = (int64_t)orderedNeighbours[k]->mnId; obj_[nb[k]] = orderedNeighbours[k]; }
+		obj_[id] = pKF;
+		mcs_throw(mcs_kfdb_set_covisibility(h_, 1, &id, nb, &n));
+	}
+	template <class F>
+	std::vector<KF*> DetectRelocalisationCandidates(F* pF) { return DetectRelocalisationCandidates(std::vector<F*>{pF})[0]; }   // :213-329
+	template <class F>
+	std::vector<std::vector<KF*>> DetectRelocalisationCandidates(const std::vector<F*>& frames) {   // the same queries one after another, in one call
+		std::vector<int32_t> off, w; std::vector<double> v; std::vector<int64_t> ids;
+		csr(frames, ids, off, w, v);
+		return run(frames.size(), [&](int cap, int32_t* cnt, int64_t* out) {
+			return mcs_kfdb_detect_relocalisation(h_, (int)frames.size(), ids.data(), off.data(), w.data(), v.data(), MCS_MEM_HOST, cap, cnt, out, nullptr); });
+	}
+	std::vector<KF*> DetectLoopCandidates(KF* pKF, double minScore, const std::set<KF*>& connected) {   // :82-210
+		std::vector<int32_t> off, w; std::vector<double> v; std::vector<int64_t> ids, conn;
+		csr(std::vector<KF*>{pKF}, ids, off, w, v);
+		for (KF* k : connected) conn.push_back((int64_t)k->mnId);
+		const int32_t coff[2] = {0, (int32_t)conn.size()};
+		return run(1, [&](int cap, int32_t* cnt, int64_t* out) {
+			return mcs_kfdb_detect_loop(h_, 1, ids.data(), off.data(), w.data(), v.data(), coff, conn.data(), &minScore, MCS_MEM_HOST, cap, cnt, out, nullptr); })[0];
+	}
+	// ORBVocabulary::score(bow, pKFi->mBowVec) for stored keyframes (src/cLoopClosing.cpp:132-151)
+	template <class Bow>
+	std::vector<double> score(const Bow& bow, const std::vector<KF*>& kfs) {
+		std::vector<int32_t> w; std::vector<double> v, out(kfs.size()); std::vector<int64_t> ids;
+		for (auto& e : bow) { w.push_back((int32_t)e.first); v.push_back(e.second); }
+		for (KF* k : kfs) ids.push_back((int64_t)k->mnId);
+		if (!kfs.empty()) mcs_throw(mcs_kfdb_score(h_, (int)w.size(), w.data(), v.data(), (int)ids.size(), ids.data(), MCS_MEM_HOST, out.data()));
+		return out;
+	}
+	int size() const { int n = 0; mcs_throw(mcs_kfdb_size(h_, &n)); return n; }
+	mcs_kfdb* handle() const { return h_; }
+
+private:
+	template <class T>
+	static void csr(const std::vector<T*>& xs, std::vector<int64_t>& ids, std::vector<int32_t>& off, std::vector<int32_t>& w, std::vector<double>& v) {
+		off.assign(1, 0);
+		for (T* x : xs) {
+			ids.push_back((int64_t)x->mnId);
+			for (auto& e : x->mBowVec) { w.push_back((int32_t)e.first); v.push_back(e.second); }
+			off.push_back((int32_t)w.size());
+		}
+	}
+	template <class Call>
+	std::vector<std::vector<KF*>> run(size_t nq, Call call) {
+		const int cap = (int)obj_.size() + 1;   // a query returns each keyframe at most once
+		std::vector<int32_t> cnt(nq);
+		std::vector<int64_t> out(nq * (size_t)cap);
+		mcs_throw(call(cap, cnt.data(), out.data()));
+		std::vector<std::vector<KF*>> r(nq);
+		for (size_t q = 0; q < nq; ++q)
+			for (int i = 0; i < cnt[q]; ++i) r[q].push_back(obj_.at(out[q * cap + i]));
+		return r;
+	}
+	mcs_kfdb* h_ = nullptr;
+	std::map<int64_t, KF*> obj_;
+};
 
 }  // namespace MultiColSLAM

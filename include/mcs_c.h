@@ -33,9 +33,10 @@ extern "C" {
 
 /* ABI revision of this header: bumped whenever a struct layout or an entry point's signature changes (3: mcs_desc_set carries block_rows / block_pitch_rows
  * since round 2 — callers built against an older header must be recompiled; mcs_describe_fast_table, FAST types 0 / 1 in round 3; 4: mcs_extractor_tie_stats; 5: mcs_copy_narrow,
- * mcs_ctx_result_stream, mcs_ctx_stream_conflicts, mcs_ctx_transfer_stream in round 4; 8: mcs_extractor_set_tie_capture / _patch_ties in round 6).  mcs_abi_version() returns
+ * mcs_ctx_result_stream, mcs_ctx_stream_conflicts, mcs_ctx_transfer_stream in round 4; 8: mcs_extractor_set_tie_capture / _patch_ties in round 6;
+ * 9: the keyframe database mcs_kfdb_*, mcs_vocabulary_set_words, mcs_bow_vector).  mcs_abi_version() returns
  * the value the LIBRARY was built with: compare it with MCS_ABI_VERSION after dlopen. */
-#define MCS_ABI_VERSION 8
+#define MCS_ABI_VERSION 9
 
 #define MCS_MAX_POLY 16
 #define MCS_MAX_LEVELS 16
@@ -373,6 +374,59 @@ typedef struct mcs_vocabulary mcs_vocabulary;
 int mcs_vocabulary_create(mcs_ctx*, int n_nodes, const uint8_t* node_desc, const int32_t* child_off, const int32_t* child_idx, int L, mcs_vocabulary** out);
 void mcs_vocabulary_destroy(mcs_vocabulary*);
 int mcs_bow_transform(mcs_vocabulary*, const uint8_t* desc, int n, int stride, int levelsup, mcs_mem_kind kind, int32_t* leaf_node, int32_t* node_at_level);
+
+/* The BowVector of one frame on the device: the second half of TemplatedVocabulary::transform (TF_IDF branch, ThirdParty/DBoW2/DBoW2/
+ * TemplatedVocabulary.h:1147-1163: bow[word] += weight in feature order, words of weight 0 dropped) and BowVector::normalize(L1)
+ * (BowVector.cpp: |v| summed in ascending word order, one division per word), bit for bit.
+ *   mcs_vocabulary_set_words  word id (-1 for inner nodes) and weight of every node of the flat tree given to mcs_vocabulary_create
+ *   mcs_bow_vector            leaf_nodes[n] = the leaf_node output of mcs_bow_transform -> word_ids_out[*nwords_out] ascending,
+ *                             values_out[*nwords_out]; both outputs must hold n entries.  kind: where leaf_nodes and the outputs live
+ *                             (DEVICE: nwords_out too).  Synchronous. */
+int mcs_vocabulary_set_words(mcs_vocabulary*, const int32_t* word_id_per_node, const double* weight_per_node);
+int mcs_bow_vector(mcs_vocabulary*, const int32_t* leaf_nodes, int n, mcs_mem_kind kind, int32_t* word_ids_out, double* values_out, int32_t* nwords_out);
+
+/* ------------------------------------------------------------------ cMultiKeyFrameDatabase (src/cMultiKeyFrameDatabase.cpp)
+ *   mcs_kfdb_create / _destroy         cMultiKeyFrameDatabase::cMultiKeyFrameDatabase (:32-40): n_words = the vocabulary's word count
+ *   mcs_kfdb_add                       add (:43-51): keyframe i has mnId kf_ids[i] and the BowVector word_ids / values[offsets[i] .. offsets[i+1])
+ *                                      (ascending word ids, L1-normalised values: mBowVec).  An id already in the database is refused.
+ *   mcs_kfdb_erase                     erase (:53-73); a keyframe erased and added again goes to the END of every inverted list
+ *   mcs_kfdb_clear                     clear (:75-79)
+ *   mcs_kfdb_set_covisibility          GetBestCovisibilityKeyFrames(10) (src/cMultiKeyFrame.cpp:231-240) of each kf_ids[i]: neighbours[i*10 ..
+ *                                      i*10 + counts[i]) in covisibility order; set again whenever the covisibility graph changes
+ *   mcs_kfdb_detect_relocalisation     DetectRelocalisationCandidates(F) (:213-329) for nq frames: query_ids = F->mnId, BowVector CSR as in _add
+ *   mcs_kfdb_detect_loop               DetectLoopCandidates(pKF, minScore) (:82-210): query_ids = pKF->mnId, connected CSR =
+ *                                      pKF->GetConnectedKeyFrames() (may be NULL: no connected keyframes), min_scores[nq]
+ *   mcs_kfdb_score                     ORBVocabulary::score(pKF->mBowVec, pKFi->mBowVec) of src/cLoopClosing.cpp:132-151 against stored keyframes
+ *   mcs_kfdb_size                      number of keyframes in the database
+ * Candidates of query q: cand_ids[q*cap .. q*cap + cand_count[q]) in the reference's output order.  Every keyframe id the database has seen keeps the
+ * reference's per-keyframe state (mnRelocQuery / mnRelocWords / mRelocScore, mnLoopQuery / mnLoopWords / mLoopScore) across calls, across erase and clear;
+ * a batch equals its queries issued one after another.  mRelocScore / mLoopScore of a keyframe never scored read 0.0 (the reference reads an
+ * unwritten double there).  cand_count receives the full counts; a count above cap fails with MCS_ERR_CAPACITY and then the
+ * state is left as it was.  kind: where every array argument lives (DEVICE: BowVector values are read in place).  The detect and score calls are synchronous.
+ * Optional diagnostics, per query in list order (lScoreAndMatch): keyframe id, its word counter, its score, its accumulated score and best keyframe. */
+typedef struct mcs_kfdb mcs_kfdb;
+typedef struct {
+	int32_t cap;        /* entries per query in each array below */
+	int32_t* count;     /* [nq] entries of lScoreAndMatch (full count; MCS_ERR_CAPACITY above cap) */
+	int64_t* kf_id;     /* [nq * cap] */
+	int32_t* words;     /* [nq * cap] mnRelocWords / mnLoopWords */
+	double* score;      /* [nq * cap] L1 score */
+	double* acc;        /* [nq * cap] accScore after the covisibility accumulation */
+	int64_t* best;      /* [nq * cap] pBestKF */
+} mcs_kfdb_diag;
+int mcs_kfdb_create(mcs_ctx*, int n_words, int capacity_hint, mcs_kfdb** out);
+int mcs_kfdb_destroy(mcs_kfdb*);
+int mcs_kfdb_clear(mcs_kfdb*);
+int mcs_kfdb_size(const mcs_kfdb*, int* n);
+int mcs_kfdb_add(mcs_kfdb*, int nkf, const int64_t* kf_ids, const int32_t* offsets, const int32_t* word_ids, const double* values, mcs_mem_kind kind);
+int mcs_kfdb_erase(mcs_kfdb*, int nkf, const int64_t* kf_ids);
+int mcs_kfdb_set_covisibility(mcs_kfdb*, int nkf, const int64_t* kf_ids, const int64_t* neighbours, const int32_t* counts);
+int mcs_kfdb_detect_relocalisation(mcs_kfdb*, int nq, const int64_t* query_ids, const int32_t* offsets, const int32_t* word_ids, const double* values,
+                                   mcs_mem_kind kind, int cap, int32_t* cand_count, int64_t* cand_ids, const mcs_kfdb_diag* diag);
+int mcs_kfdb_detect_loop(mcs_kfdb*, int nq, const int64_t* query_ids, const int32_t* offsets, const int32_t* word_ids, const double* values,
+                         const int32_t* connected_offsets, const int64_t* connected_ids, const double* min_scores, mcs_mem_kind kind, int cap,
+                         int32_t* cand_count, int64_t* cand_ids, const mcs_kfdb_diag* diag);
+int mcs_kfdb_score(mcs_kfdb*, int nw, const int32_t* word_ids, const double* values, int nkf, const int64_t* kf_ids, mcs_mem_kind kind, double* scores);
 
 /* self-test of an arithmetic shortcut of the descriptor kernel: the omni model's three divisions by the same norm (src/cam_model_omni.cpp:
  * 146-161) share one refined reciprocal; this runs n pseudo-random (numerator, denominator) pairs of the magnitudes the kernel sees through

@@ -72,6 +72,8 @@ EXPORTS = [
     "mcs_search_triangulation_sweep", "mcs_search_kf_kf_ring", "mcs_rows_valid", "mcs_extractor_set_describe", "mcs_extractor_describe_stats", "mcs_extractor_tie_stats", "mcs_extractor_set_tie_band", "mcs_extractor_fix_ties", "mcs_extractor_tie_counts", "mcs_extractor_set_tie_capture", "mcs_extractor_patch_ties", "mcs_describe_fast_bound",
     "mcs_selftest_describe_fast", "mcs_describe_fast_table", "mcs_describe_fast_table_packed", "mcs_extract_batch_strided", "mcs_rig_pack_headers", "mcs_rig_rows_valid",
     "mcs_search_by_projection", "mcs_window_match", "mcs_window_best", "mcs_rotation_consistency", "mcs_world_to_cam", "mcs_distinctive_descriptors", "mcs_selftest_shared_reciprocal", "mcs_vocabulary_create", "mcs_vocabulary_destroy", "mcs_bow_transform", "mcs_copy_narrow", "mcs_ctx_result_stream", "mcs_ctx_stream_conflicts", "mcs_ctx_transfer_stream", "mcs_host_alloc", "mcs_host_free",
+    "mcs_vocabulary_set_words", "mcs_bow_vector", "mcs_kfdb_create", "mcs_kfdb_destroy", "mcs_kfdb_clear", "mcs_kfdb_size", "mcs_kfdb_add", "mcs_kfdb_erase",
+    "mcs_kfdb_set_covisibility", "mcs_kfdb_detect_relocalisation", "mcs_kfdb_detect_loop", "mcs_kfdb_score",
 ]
 
 WINDOW_RATIO, WINDOW_BEST, WINDOW_INITIALIZE = 1, 2, 3
@@ -91,6 +93,13 @@ class FrameView(C.Structure):
     _fields_ = [("keys", C.c_void_p), ("desc", C.c_void_p), ("mask", C.c_void_p), ("cam", C.c_void_p), ("assigned", C.c_void_p),
                 ("n", C.c_int32), ("stride", C.c_int32), ("nr_cams", C.c_int32), ("width", C.c_void_p), ("height", C.c_void_p),
                 ("scale_factors", C.c_void_p), ("nlevels", C.c_int32)]
+
+
+
+class KfdbDiag(C.Structure):
+    _fields_ = [("cap", C.c_int32), ("count", C.c_void_p), ("kf_id", C.c_void_p), ("words", C.c_void_p), ("score", C.c_void_p), ("acc", C.c_void_p),
+                ("best", C.c_void_p)]
+
 
 _lib = None
 
@@ -167,6 +176,18 @@ def lib():
     L.mcs_vocabulary_destroy.argtypes = [vp]
     L.mcs_vocabulary_destroy.restype = None
     L.mcs_bow_transform.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
+    L.mcs_vocabulary_set_words.argtypes = [vp, vp, vp]
+    L.mcs_bow_vector.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp]
+    L.mcs_kfdb_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp)]
+    L.mcs_kfdb_destroy.argtypes = [vp]
+    L.mcs_kfdb_clear.argtypes = [vp]
+    L.mcs_kfdb_size.argtypes = [vp, i32p]
+    L.mcs_kfdb_add.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int]
+    L.mcs_kfdb_erase.argtypes = [vp, C.c_int, vp]
+    L.mcs_kfdb_set_covisibility.argtypes = [vp, C.c_int, vp, vp, vp]
+    L.mcs_kfdb_detect_relocalisation.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, C.POINTER(KfdbDiag)]
+    L.mcs_kfdb_detect_loop.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, C.POINTER(KfdbDiag)]
+    L.mcs_kfdb_score.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp]
     L.mcs_copy_narrow.argtypes = [vp, vp, vp, C.c_size_t, C.c_int, vp]
     L.mcs_ctx_result_stream.argtypes = [vp, C.POINTER(vp)]
     L.mcs_ctx_stream_conflicts.argtypes = [vp, vp, C.POINTER(C.c_uint)]

@@ -51,7 +51,35 @@ struct mcs_vocabulary {
 	mcs_ctx* ctx = nullptr;
 	int nNodes = 0, L = 0;
 	uint8_t* nodeDesc = nullptr; int* childOff = nullptr; int* childIdx = nullptr;
+	// word id and weight of every node (mcs_vocabulary_set_words) and a zeroed per-word histogram for mcs_bow_vector (mcs_kfdb.hip)
+	int nWords = 0; int* wordOf = nullptr; double* weightOf = nullptr; int* hist = nullptr;
 };
+
+int mcs_vocabulary_set_words_internal(mcs_vocabulary* v, const int32_t* word_id_per_node, const double* weight_per_node) {
+	int mx = -1;
+	for (int i = 0; i < v->nNodes; ++i) {
+		if (word_id_per_node[i] < -1) return fail(MCS_ERR_INVALID, "word ids must be >= 0 (-1: an inner node)");
+		if (!(weight_per_node[i] >= 0.0) || std::isinf(weight_per_node[i])) return fail(MCS_ERR_INVALID, "weights must be finite and >= 0 (TF-IDF)");
+		mx = std::max(mx, (int)word_id_per_node[i]);
+	}
+	HIPCHK(hipSetDevice(v->ctx->device));
+	(void)hipFree(v->wordOf); (void)hipFree(v->weightOf); (void)hipFree(v->hist);
+	v->wordOf = nullptr; v->weightOf = nullptr; v->hist = nullptr; v->nWords = 0;
+	const size_t nn = (size_t)v->nNodes, nw = (size_t)std::max(mx + 1, 1);
+	bool ok = hipMalloc((void**)&v->wordOf, nn * 4) == hipSuccess && hipMalloc((void**)&v->weightOf, nn * 8) == hipSuccess &&
+	          hipMalloc((void**)&v->hist, nw * 4) == hipSuccess;
+	ok = ok && hipMemcpy(v->wordOf, word_id_per_node, nn * 4, hipMemcpyHostToDevice) == hipSuccess &&
+	     hipMemcpy(v->weightOf, weight_per_node, nn * 8, hipMemcpyHostToDevice) == hipSuccess && hipMemset(v->hist, 0, nw * 4) == hipSuccess;
+	if (!ok) return fail(MCS_ERR_HIP, "vocabulary word upload failed");
+	v->nWords = (int)nw;
+	return MCS_OK;
+}
+
+int mcs_vocabulary_words_internal(mcs_vocabulary* v, mcs_ctx** c, int* nNodes, int** wordOf, double** weightOf, int** hist, int* nWords) {
+	if (!v->wordOf) return fail(MCS_ERR_INVALID, "mcs_bow_vector: call mcs_vocabulary_set_words first");
+	*c = v->ctx; *nNodes = v->nNodes; *wordOf = v->wordOf; *weightOf = v->weightOf; *hist = v->hist; *nWords = v->nWords;
+	return MCS_OK;
+}
 
 int mcs_vocabulary_create(mcs_ctx* c, int n_nodes, const uint8_t* node_desc, const int32_t* child_off, const int32_t* child_idx, int L,
                           mcs_vocabulary** out) {
@@ -81,6 +109,7 @@ int mcs_vocabulary_create(mcs_ctx* c, int n_nodes, const uint8_t* node_desc, con
 void mcs_vocabulary_destroy(mcs_vocabulary* v) {
 	if (!v) return;
 	(void)hipFree(v->nodeDesc); (void)hipFree(v->childOff); (void)hipFree(v->childIdx);
+	(void)hipFree(v->wordOf); (void)hipFree(v->weightOf); (void)hipFree(v->hist);
 	delete v;
 }
 

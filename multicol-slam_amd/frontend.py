@@ -6,6 +6,7 @@
   cORBmatcher (grid-window searches)   src/cORBmatcher.cpp:67-166,326-726,1990-2118
   cMultiCamSys_ (pose, projection)     src/cam_system_omni.cpp:92-133,168-198
   DescriptorDistance64[_Masked]        src/cORBmatcher.cpp:2438-2474
+  cMultiKeyFrameDatabase               src/cMultiKeyFrameDatabase.cpp:43-329 (inverted file, relocalisation / loop candidates)
 
 Everything numeric runs in libmcs_hip.so on the GPU; this file only shapes inputs/outputs (numpy stands in for cv::Mat).
 """
@@ -14,7 +15,7 @@ import ctypes as C
 import numpy as np
 
 from . import Context, Extractor
-from ._capi import KP_DTYPE, MEM_HOST, DescSet, check, lib, make_ocam, np_ptr
+from ._capi import KP_DTYPE, MEM_DEVICE, MEM_HOST, MCS_ERR_CAPACITY, DescSet, KfdbDiag, check, lib, make_ocam, np_ptr
 
 FRAME_GRID_ROWS, FRAME_GRID_COLS = 48, 64   # include/cMultiFrame.h
 
@@ -255,7 +256,12 @@ class cMultiFrame:
 class cMultiKeyFrame:
     """Thin keyframe view: the accessors the brute-force searches use (src/cMultiKeyFrame.cpp:54,77,356-364)."""
 
+    nNextId = 0
+
     def __init__(self, F):
+        self.mnId = cMultiKeyFrame.nNextId          # src/cMultiKeyFrame.cpp:38-45
+        cMultiKeyFrame.nNextId += 1
+        self.mnFrameId = getattr(F, "mnId", None)
         self.camSystem = F.camSystem
         self.mDescriptors, self.mDescriptorMasks = F.mDescriptors, F.mDescriptorMasks   # shallow copies like cv::Mat
         self.mvKeys, self.mvKeysRays = F.mvKeys, F.mvKeysRays
@@ -263,6 +269,10 @@ class cMultiKeyFrame:
         self.mvpMapPoints = list(F.mvpMapPoints)
         self._d, self._m = F.all_descriptors(), F.all_masks()
         self.mBowVec, self.mFeatVec = getattr(F, "mBowVec", None), getattr(F, "mFeatVec", None)
+        self.mvpOrderedConnectedKeyFrames = []
+
+    def GetBestCovisibilityKeyFrames(self, N):      # src/cMultiKeyFrame.cpp:231-240
+        return list(self.mvpOrderedConnectedKeyFrames[:N])
 
     def GetMapPointMatches(self):
         return self.mvpMapPoints
@@ -685,6 +695,12 @@ class cORBVocabulary:
         nd = np.ascontiguousarray(voc["node_desc"], np.uint8)
         co, ci = np.ascontiguousarray(voc["child_off"], np.int32), np.ascontiguousarray(voc["child_idx"], np.int32)
         check(lib().mcs_vocabulary_create(self.ctx.h, len(nd), np_ptr(nd), np_ptr(co), np_ptr(ci), self.m_L, C.byref(self.h)))
+        wid, wt = np.ascontiguousarray(voc["word_id"], np.int32), np.ascontiguousarray(voc["weight"], np.float64)
+        check(lib().mcs_vocabulary_set_words(self.h, np_ptr(wid), np_ptr(wt)))
+        self.n_words = int(voc.get("n_words", int(wid.max()) + 1))
+
+    def size(self):
+        return self.n_words
 
     def __del__(self):
         try:
@@ -720,3 +736,153 @@ class cORBVocabulary:
         if norm > 0.0:
             bow = {k: v / norm for k, v in bow.items()}
         return bow, dict(sorted(fv.items()))
+
+    def bow_vector(self, descriptors, levelsup=4):
+        """The BowVector of transform() built on the device (mcs_bow_vector): -> (word ids int32 ascending, values float64), bit-identical to
+        transform()'s dict."""
+        leaf, _ = self.descend(descriptors, levelsup)
+        n = len(leaf)
+        w, v, nw = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.float64), np.zeros(1, np.int32)
+        check(lib().mcs_bow_vector(self.h, np_ptr(np.ascontiguousarray(leaf, np.int32)), n, MEM_HOST, np_ptr(w), np_ptr(v), np_ptr(nw)))
+        return w[:nw[0]].copy(), v[:nw[0]].copy()
+
+    def bow_vector_device(self, leaf_nodes_dev, n, word_ids_dev, values_dev, nwords_dev):
+        """Device pointers (ints, e.g. torch tensor data_ptr()): leaf nodes of mcs_bow_transform -> BowVector, never leaving the GPU."""
+        check(lib().mcs_bow_vector(self.h, C.c_void_p(leaf_nodes_dev), int(n), MEM_DEVICE, C.c_void_p(word_ids_dev), C.c_void_p(values_dev),
+                                   C.c_void_p(nwords_dev)))
+
+
+def _bow_arrays(bow):
+    """mBowVec as a dict {word: value} (cORBVocabulary.transform) or a (word ids, values) pair (bow_vector) -> contiguous arrays"""
+    if isinstance(bow, dict):
+        items = sorted(bow.items())
+        return np.array([k for k, _ in items], np.int32), np.array([v for _, v in items], np.float64)
+    w, v = bow
+    return np.ascontiguousarray(w, np.int32), np.ascontiguousarray(v, np.float64)
+
+
+def _csr(bows):
+    arrs = [_bow_arrays(b) for b in bows]
+    off = np.zeros(len(arrs) + 1, np.int32)
+    off[1:] = np.cumsum([len(w) for w, _ in arrs])
+    w = np.concatenate([a[0] for a in arrs]) if arrs else np.zeros(0, np.int32)
+    v = np.concatenate([a[1] for a in arrs]) if arrs else np.zeros(0, np.float64)
+    return off, np.ascontiguousarray(w, np.int32), np.ascontiguousarray(v, np.float64)
+
+
+class cMultiKeyFrameDatabase:
+    """cMultiKeyFrameDatabase (include/cMultiKeyFrameDatabase.h, src/cMultiKeyFrameDatabase.cpp) on the device (mcs_kfdb_*).
+    Keyframes need mnId and mBowVec; their covisibility (GetBestCovisibilityKeyFrames(10)) is read when they are added and whenever
+    SetCovisibility / UpdateCovisibility is called.  Candidates come back as the keyframe objects that were added (or named as neighbours)."""
+
+    def __init__(self, voc, ctx=None, capacity_hint=0):
+        """voc: a cORBVocabulary (its word count sizes the inverted file, as mpVoc->size() does) or a word count."""
+        n_words = voc.size() if hasattr(voc, "size") else int(voc)
+        self.ctx = ctx or getattr(voc, "ctx", None) or default_context()
+        self.mpVoc = voc
+        self.h = C.c_void_p()
+        check(lib().mcs_kfdb_create(self.ctx.h, int(n_words), int(capacity_hint), C.byref(self.h)))
+        self.objects = {}   # mnId -> keyframe object
+        self.diag_cap = 0   # > 0: the last query's diagnostics in self.last_trace (lists of (kf id, words, score, acc, best id))
+        self.last_trace = None
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().mcs_kfdb_destroy(self.h)
+        except Exception:
+            pass
+
+    def add(self, pKF):
+        off, w, v = _csr([pKF.mBowVec])
+        ids = np.array([pKF.mnId], np.int64)
+        check(lib().mcs_kfdb_add(self.h, 1, np_ptr(ids), np_ptr(off), np_ptr(w), np_ptr(v), MEM_HOST))
+        self.objects[int(pKF.mnId)] = pKF
+        if hasattr(pKF, "GetBestCovisibilityKeyFrames"):
+            self.SetCovisibility(pKF, pKF.GetBestCovisibilityKeyFrames(10))
+
+    def erase(self, pKF):
+        ids = np.array([pKF.mnId], np.int64)
+        check(lib().mcs_kfdb_erase(self.h, 1, np_ptr(ids)))
+
+    def clear(self):
+        check(lib().mcs_kfdb_clear(self.h))
+
+    def size(self):
+        n = C.c_int32()
+        check(lib().mcs_kfdb_size(self.h, C.byref(n)))
+        return n.value
+
+    def SetCovisibility(self, pKF, ordered_neighbours):
+        nb = list(ordered_neighbours)[:10]
+        for k in nb:
+            self.objects.setdefault(int(k.mnId), k)
+        ids = np.array([pKF.mnId], np.int64)
+        arr = np.zeros(10, np.int64)
+        arr[:len(nb)] = [k.mnId for k in nb]
+        self.objects.setdefault(int(pKF.mnId), pKF)
+        cnt = np.array([len(nb)], np.int32)
+        check(lib().mcs_kfdb_set_covisibility(self.h, 1, np_ptr(ids), np_ptr(arr), np_ptr(cnt)))
+
+    def UpdateCovisibility(self, kfs=None):
+        for kf in (kfs if kfs is not None else list(self.objects.values())):
+            if hasattr(kf, "GetBestCovisibilityKeyFrames"):
+                self.SetCovisibility(kf, kf.GetBestCovisibilityKeyFrames(10))
+
+    def _run(self, loop, ids, bows, connected=None, min_scores=None):
+        nq = len(ids)
+        off, w, v = _csr(bows)
+        qid = np.ascontiguousarray(ids, np.int64)
+        cap = max(16, 2 * len(self.objects))
+        while True:
+            cnt = np.zeros(max(nq, 1), np.int32)
+            out = np.zeros(max(nq * cap, 1), np.int64)
+            diag, dd = None, None
+            if self.diag_cap > 0:
+                dc = self.diag_cap
+                dd = dict(count=np.zeros(max(nq, 1), np.int32), kf_id=np.zeros(nq * dc, np.int64), words=np.zeros(nq * dc, np.int32),
+                          score=np.zeros(nq * dc), acc=np.zeros(nq * dc), best=np.zeros(nq * dc, np.int64))
+                diag = KfdbDiag(dc, *[np_ptr(dd[k]) for k in ("count", "kf_id", "words", "score", "acc", "best")])
+            if loop:
+                coff = np.zeros(nq + 1, np.int32)
+                coff[1:] = np.cumsum([len(c) for c in connected])
+                cids = np.array([int(k.mnId) for c in connected for k in c], np.int64)
+                ms = np.ascontiguousarray(min_scores, np.float64)
+                rc = lib().mcs_kfdb_detect_loop(self.h, nq, np_ptr(qid), np_ptr(off), np_ptr(w), np_ptr(v), np_ptr(coff), np_ptr(cids) if len(cids) else None,
+                                                np_ptr(ms), MEM_HOST, cap, np_ptr(cnt), np_ptr(out), C.byref(diag) if diag else None)
+            else:
+                rc = lib().mcs_kfdb_detect_relocalisation(self.h, nq, np_ptr(qid), np_ptr(off), np_ptr(w), np_ptr(v), MEM_HOST, cap, np_ptr(cnt), np_ptr(out),
+                                                          C.byref(diag) if diag else None)
+            if rc == MCS_ERR_CAPACITY and int(cnt[:nq].max(initial=0)) > cap:   # the state is unchanged: run again with room
+                cap = int(cnt[:nq].max())
+                continue
+            check(rc)
+            break
+        if dd is not None:
+            self.last_trace = [[(int(dd["kf_id"][q * dc + i]), int(dd["words"][q * dc + i]), float(dd["score"][q * dc + i]), float(dd["acc"][q * dc + i]),
+                                 int(dd["best"][q * dc + i])) for i in range(int(dd["count"][q]))] for q in range(nq)]
+        return [[self.objects[int(i)] for i in out[q * cap:q * cap + cnt[q]]] for q in range(nq)]
+
+    def DetectRelocalisationCandidates(self, F):
+        return self._run(False, [F.mnId], [F.mBowVec])[0]
+
+    def detect_relocalisation(self, frames):
+        """DetectRelocalisationCandidates of every frame, in one device call (= the calls one after another)."""
+        return self._run(False, [F.mnId for F in frames], [F.mBowVec for F in frames]) if frames else []
+
+    def DetectLoopCandidates(self, pKF, minScore, connected=None):
+        """connected: pKF->GetConnectedKeyFrames() (default: pKF.GetConnectedKeyFrames() if it exists, else none)"""
+        if connected is None:
+            connected = pKF.GetConnectedKeyFrames() if hasattr(pKF, "GetConnectedKeyFrames") else []
+        return self._run(True, [pKF.mnId], [pKF.mBowVec], [list(connected)], [float(minScore)])[0]
+
+    def detect_loop(self, kfs, min_scores, connected):
+        return self._run(True, [k.mnId for k in kfs], [k.mBowVec for k in kfs], [list(c) for c in connected], min_scores) if kfs else []
+
+    def score(self, bow, kfs):
+        """ORBVocabulary::score(bow, pKFi->mBowVec) for stored keyframes (src/cLoopClosing.cpp:132-151)"""
+        w, v = _bow_arrays(bow)
+        ids = np.array([k.mnId for k in kfs], np.int64)
+        out = np.zeros(max(len(ids), 1))
+        check(lib().mcs_kfdb_score(self.h, len(w), np_ptr(w), np_ptr(v), len(ids), np_ptr(ids), MEM_HOST, np_ptr(out)))
+        return out[:len(ids)]
