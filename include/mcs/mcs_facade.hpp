@@ -684,4 +684,106 @@ private:
 	std::map<int64_t, KF*> obj_;
 };
 
+
+// cSim3Solver (src/cSim3Solver.cpp, include/cSim3Solver.h) over mcs_sim3_*.  KF: the caller's keyframe type with GetMapPointMatches() (a vector of MP*),
+// GetKeyPoint(i).octave, GetSigma2(level), keypoint_to_cam (find(i)->second) and camSystem (a cMultiCamSys_ of this header); MP: the map point type
+// with isBad(), GetIndexInKeyFrame(KF*) (a vector of indices, the first is used) and GetWorldPos() (a Vec3d or anything indexable by 0..2).  The
+// constructor's pointer filtering runs here, everything numeric on the device; the solver's RANSAC state lives in the library from its first iterate().
+// The draws are the library's counter-based draws of `seed` (include/mcs_c.h: mcs_sim3_draw), not std::random_device's.
+inline double Sim3At(const Vec3d& v, int i) { return v.v[i]; }
+template <class T>
+inline double Sim3At(const T& v, int i) { return (double)v[i]; }
+
+template <class KF, class MP>
+class cSim3Solver {
+public:
+	cSim3Solver(Context& ctx, KF* pKF1, KF* pKF2, const std::vector<MP*>& vpMatched12, cMultiCamSys_* camSys, uint64_t seed = 0)
+	    : ctx_(ctx), cs_(camSys), seed_(seed), mN1_((int)vpMatched12.size()) {
+		std::vector<MP*> vpKeyFrameMP1 = pKF1->GetMapPointMatches();
+		for (int i1 = 0; i1 < mN1_; ++i1) {   // :71-134
+			MP* pMP2 = vpMatched12[i1];
+			if (!pMP2) continue;
+			MP* pMP1 = vpKeyFrameMP1[i1];
+			if (!pMP1) continue;
+			if (pMP1->isBad() || pMP2->isBad()) continue;
+			const auto idxs1 = pMP1->GetIndexInKeyFrame(pKF1);
+			const auto idxs2 = pMP2->GetIndexInKeyFrame(pKF2);
+			if (idxs1.empty() || idxs2.empty()) continue;
+			const int indexKF1 = (int)idxs1[0], indexKF2 = (int)idxs2[0];
+			if (indexKF1 < 0 || indexKF2 < 0) continue;
+			sigma2_.push_back(pKF1->GetSigma2(pKF1->GetKeyPoint(indexKF1).octave));
+			sigma2_.push_back(pKF2->GetSigma2(pKF2->GetKeyPoint(indexKF2).octave));
+			cam_.push_back((int32_t)pKF1->keypoint_to_cam.find(indexKF1)->second);
+			cam_.push_back((int32_t)pKF2->keypoint_to_cam.find(indexKF2)->second);
+			const auto X1 = pMP1->GetWorldPos();
+			const auto X2 = pMP2->GetWorldPos();
+			for (int k = 0; k < 3; ++k) Xw_.push_back(Sim3At(X1, k));
+			for (int k = 0; k < 3; ++k) Xw_.push_back(Sim3At(X2, k));
+			index1_.push_back(i1);
+		}
+		const int nr = cs_->GetNrCams();
+		for (KF* k : {pKF1, pKF2}) {
+			const Matx44d inv = InvMat(k->camSystem.M_t);
+			Mt_.insert(Mt_.end(), inv.begin(), inv.end());
+		}
+		for (KF* k : {pKF1, pKF2})
+			for (int c = 0; c < nr; ++c) MtMc_.insert(MtMc_.end(), k->camSystem.MtMc_inv[c].begin(), k->camSystem.MtMc_inv[c].end());
+		SetRansacParameters();
+	}
+	~cSim3Solver() { if (h_) mcs_sim3_destroy(h_); }
+	cSim3Solver(const cSim3Solver&) = delete;
+	cSim3Solver& operator=(const cSim3Solver&) = delete;
+
+	void SetRansacParameters(double probability = 0.99, int minInliers = 6, int maxIterations = 300) {   // :139-165
+		prob_ = probability; minInl_ = minInliers; maxIts_ = maxIterations;
+		if (h_) mcs_throw(mcs_sim3_set_ransac_parameters(h_, &prob_, &minInl_, &maxIts_));
+	}
+	bool iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers, Matx44d& result) {   // :167-254
+		create();
+		uint8_t ok = 0, noMore = 0;
+		int32_t n = 0;
+		std::vector<uint8_t> vb((size_t)std::max(mN1_, 1), 0);
+		Matx44d T = result;
+		mcs_throw(mcs_sim3_iterate(h_, &nIterations, &ok, &noMore, &n, T.data(), vb.data()));
+		bNoMore = noMore != 0;
+		nInliers = n;
+		vbInliers.assign(mN1_, false);
+		for (int i = 0; i < mN1_; ++i) vbInliers[i] = vb[i] != 0;
+		if (ok) result = T;
+		return ok != 0;
+	}
+	bool find(std::vector<bool>& vbInliers12, int& nInliers, Matx44d& result) {   // :256-262
+		create();
+		int32_t its = 0;
+		mcs_throw(mcs_sim3_info(h_, nullptr, &its, nullptr));
+		bool bFlag;
+		return iterate(its, bFlag, vbInliers12, nInliers, result);
+	}
+	std::array<double, 9> GetEstimatedRotation() { std::array<double, 9> R{}; best(R.data(), nullptr, nullptr); return R; }
+	Vec3d GetEstimatedTranslation() { Vec3d t{}; best(nullptr, t.v, nullptr); return t; }
+	double GetEstimatedScale() { double s = 0; best(nullptr, nullptr, &s); return s; }
+	int size() const { return (int)index1_.size(); }   // N: the correspondences the constructor kept
+
+private:
+	void create() {
+		if (h_) return;
+		std::vector<double> Mc;
+		std::vector<mcs_ocam> oc;
+		for (int c = 0; c < cs_->GetNrCams(); ++c) { Mc.insert(Mc.end(), cs_->M_c[c].begin(), cs_->M_c[c].end()); oc.push_back(cs_->camModels[c].ocam); }
+		const int32_t off[2] = {0, (int32_t)index1_.size()};
+		mcs_throw(mcs_sim3_create(ctx_.h, cs_->GetNrCams(), Mc.data(), oc.data(), 1, &mN1_, off, Mt_.data(), MtMc_.data(), &prob_, &minInl_, &maxIts_,
+		                          Xw_.data(), cam_.data(), sigma2_.data(), index1_.data(), seed_, nullptr, &h_));
+	}
+	void best(double* R, double* t, double* s) { create(); mcs_throw(mcs_sim3_best(h_, R, t, s, nullptr, nullptr, nullptr)); }
+	Context& ctx_;
+	cMultiCamSys_* cs_;
+	uint64_t seed_;
+	int32_t mN1_;
+	double prob_ = 0.99;
+	int32_t minInl_ = 6, maxIts_ = 300;
+	std::vector<double> Xw_, sigma2_, Mt_, MtMc_;
+	std::vector<int32_t> cam_, index1_;
+	mcs_sim3* h_ = nullptr;
+};
+
 }  // namespace MultiColSLAM

@@ -34,9 +34,9 @@ extern "C" {
 /* ABI revision of this header: bumped whenever a struct layout or an entry point's signature changes (3: mcs_desc_set carries block_rows / block_pitch_rows
  * since round 2 — callers built against an older header must be recompiled; mcs_describe_fast_table, FAST types 0 / 1 in round 3; 4: mcs_extractor_tie_stats; 5: mcs_copy_narrow,
  * mcs_ctx_result_stream, mcs_ctx_stream_conflicts, mcs_ctx_transfer_stream in round 4; 8: mcs_extractor_set_tie_capture / _patch_ties in round 6;
- * 9: the keyframe database mcs_kfdb_*, mcs_vocabulary_set_words, mcs_bow_vector).  mcs_abi_version() returns
+ * 9: the keyframe database mcs_kfdb_*, mcs_vocabulary_set_words, mcs_bow_vector; 10: the Sim3 RANSAC mcs_sim3_*).  mcs_abi_version() returns
  * the value the LIBRARY was built with: compare it with MCS_ABI_VERSION after dlopen. */
-#define MCS_ABI_VERSION 9
+#define MCS_ABI_VERSION 10
 
 #define MCS_MAX_POLY 16
 #define MCS_MAX_LEVELS 16
@@ -427,6 +427,44 @@ int mcs_kfdb_detect_loop(mcs_kfdb*, int nq, const int64_t* query_ids, const int3
                          const int32_t* connected_offsets, const int64_t* connected_ids, const double* min_scores, mcs_mem_kind kind, int cap,
                          int32_t* cand_count, int64_t* cand_ids, const mcs_kfdb_diag* diag);
 int mcs_kfdb_score(mcs_kfdb*, int nw, const int32_t* word_ids, const double* values, int nkf, const int64_t* kf_ids, mcs_mem_kind kind, double* scores);
+
+/* ------------------------------------------------------------------ cSim3Solver (src/cSim3Solver.cpp, include/cSim3Solver.h) for a batch of loop candidates
+ *   mcs_sim3_create                   one cSim3Solver(pKF1, pKF2, vpMatched12, camSys) per solver (:44-137) + SetRansacParameters(p, minInliers, maxIts) (:139-165).
+ *                                     Local rig (camSysLocal): nr_cams <= 32, M_c [nr_cams][16] row-major, cams [nr_cams].  Per solver s: mN1[s] =
+ *                                     vpMatched12.size(), correspondences [corr_offsets[s], corr_offsets[s+1]), M_t_inv [s][2][16] = invMat(M_t) of KF1, KF2,
+ *                                     MtMc_inv [s][2][nr_cams][16] of KF1, KF2 (cMultiCamSys_::MtMc_inv), probability / min_inliers / max_iterations.
+ *                                     Per correspondence i (the pairs the constructor keeps, in its order; the pointer filtering stays with the caller):
+ *                                     Xw [i][2][3] world positions of the two map points, cam [i][2] keypoint_to_cam of their first index in their keyframe,
+ *                                     sigma2 [i][2] = GetSigma2(octave) of those keypoints, index1 [i] = i1 (mvnIndices1).  seed: see mcs_sim3_draw.  draws: NULL,
+ *                                     or per solver 3 * max(1, max_iterations[s]) values randi in [0, N) (iteration k, pick j at 3k + j) that replace the
+ *                                     generated ones.  A solver with N < 3 correspondences and N >= minInliers is refused (the reference is undefined there).
+ *   mcs_sim3_set_ransac_parameters    SetRansacParameters for every solver: mnIterations = 0, the best-so-far state is kept (as in the reference)
+ *   mcs_sim3_iterate                  iterate(n_iterations[s], bNoMore, vbInliers, nInliers, result) (:167-254) of every solver in one call (= the
+ *                                     reference's sequential round over its candidates: the solvers are independent).  n_iterations[s] <= 0: solver s is
+ *                                     left alone (success / no_more / n_inliers 0, no inliers).  T12 [ns][16] is written only where success[s] (the reference
+ *                                     writes `result` only then); inliers (optional): sum of mN1 bytes, solver s's vbInliers at the sum of the earlier mN1.
+ *   mcs_sim3_best                     GetEstimatedRotation / Translation / Scale (:418-431), mBestT12, mnBestInliers, mnIterations; any output may be NULL.
+ *                                     Before the first iteration the mBest* values are 0 (uninitialised in the reference).
+ *   mcs_sim3_info                     N, mRansacMaxIts (0 where N < minInliers) and mnIterations per solver
+ *   mcs_sim3_hypotheses               diagnostics: the hypotheses of iterations [first, first + count) of one solver, whatever its state: the three picked
+ *                                     correspondences (after the index handling of :207-221), the inlier count, 45 doubles (mT12i[16], mT21i[16], mR12i[9],
+ *                                     mt12i[3], ms12i) and the inlier flags [count][N] (each optional but n_inliers)
+ *   mcs_sim3_draw                     the library's draw randi of (seed, solver, iteration, pick) for N correspondences: output number ctr + 1 of the
+ *                                     splitmix64 stream at seed, ctr = (solver << 32) | (3 * iteration + pick), mapped to [0, N) by (hi32 * N) >> 32.  The
+ *                                     reference seeds std::mt19937 from std::random_device on every iterate() call; its draws cannot be reproduced
+ *                                     (DESIGN.md section 7).  -1 for bad arguments.
+ * All arrays are host memory; every call is synchronous. */
+typedef struct mcs_sim3 mcs_sim3;
+int mcs_sim3_create(mcs_ctx*, int nr_cams, const double* M_c, const mcs_ocam* cams, int n_solvers, const int32_t* mN1, const int32_t* corr_offsets,
+                    const double* M_t_inv, const double* MtMc_inv, const double* probability, const int32_t* min_inliers, const int32_t* max_iterations,
+                    const double* Xw, const int32_t* cam, const double* sigma2, const int32_t* index1, uint64_t seed, const int32_t* draws, mcs_sim3** out);
+int mcs_sim3_destroy(mcs_sim3*);
+int mcs_sim3_set_ransac_parameters(mcs_sim3*, const double* probability, const int32_t* min_inliers, const int32_t* max_iterations);
+int mcs_sim3_iterate(mcs_sim3*, const int32_t* n_iterations, uint8_t* success, uint8_t* no_more, int32_t* n_inliers, double* T12, uint8_t* inliers);
+int mcs_sim3_best(mcs_sim3*, double* R, double* t, double* s, double* T12, int32_t* best_inliers, int32_t* iterations);
+int mcs_sim3_info(const mcs_sim3*, int32_t* n, int32_t* max_its, int32_t* iterations);
+int mcs_sim3_hypotheses(mcs_sim3*, int solver, int first, int count, int32_t* picks, int32_t* n_inliers, double* hyp, uint8_t* inliers);
+int mcs_sim3_draw(uint64_t seed, int solver, int iteration, int pick, int n);
 
 /* self-test of an arithmetic shortcut of the descriptor kernel: the omni model's three divisions by the same norm (src/cam_model_omni.cpp:
  * 146-161) share one refined reciprocal; this runs n pseudo-random (numerator, denominator) pairs of the magnitudes the kernel sees through

@@ -74,6 +74,8 @@ EXPORTS = [
     "mcs_search_by_projection", "mcs_window_match", "mcs_window_best", "mcs_rotation_consistency", "mcs_world_to_cam", "mcs_distinctive_descriptors", "mcs_selftest_shared_reciprocal", "mcs_vocabulary_create", "mcs_vocabulary_destroy", "mcs_bow_transform", "mcs_copy_narrow", "mcs_ctx_result_stream", "mcs_ctx_stream_conflicts", "mcs_ctx_transfer_stream", "mcs_host_alloc", "mcs_host_free",
     "mcs_vocabulary_set_words", "mcs_bow_vector", "mcs_kfdb_create", "mcs_kfdb_destroy", "mcs_kfdb_clear", "mcs_kfdb_size", "mcs_kfdb_add", "mcs_kfdb_erase",
     "mcs_kfdb_set_covisibility", "mcs_kfdb_detect_relocalisation", "mcs_kfdb_detect_loop", "mcs_kfdb_score",
+    "mcs_sim3_create", "mcs_sim3_destroy", "mcs_sim3_set_ransac_parameters", "mcs_sim3_iterate", "mcs_sim3_best", "mcs_sim3_info",
+    "mcs_sim3_hypotheses", "mcs_sim3_draw",
 ]
 
 WINDOW_RATIO, WINDOW_BEST, WINDOW_INITIALIZE = 1, 2, 3
@@ -188,6 +190,14 @@ def lib():
     L.mcs_kfdb_detect_relocalisation.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, C.POINTER(KfdbDiag)]
     L.mcs_kfdb_detect_loop.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, C.POINTER(KfdbDiag)]
     L.mcs_kfdb_score.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp]
+    L.mcs_sim3_create.argtypes = [vp, C.c_int, vp, C.POINTER(Ocam), C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, vp, C.POINTER(vp)]
+    L.mcs_sim3_destroy.argtypes = [vp]
+    L.mcs_sim3_set_ransac_parameters.argtypes = [vp, vp, vp, vp]
+    L.mcs_sim3_iterate.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.mcs_sim3_best.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.mcs_sim3_info.argtypes = [vp, vp, vp, vp]
+    L.mcs_sim3_hypotheses.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.mcs_sim3_draw.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int]
     L.mcs_copy_narrow.argtypes = [vp, vp, vp, C.c_size_t, C.c_int, vp]
     L.mcs_ctx_result_stream.argtypes = [vp, C.POINTER(vp)]
     L.mcs_ctx_stream_conflicts.argtypes = [vp, vp, C.POINTER(C.c_uint)]

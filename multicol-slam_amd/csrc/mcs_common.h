@@ -271,6 +271,27 @@ struct WorldToCamArgs {   // cMultiCamSys_::WorldToCamHom_fast + isPointInMirror
 };
 void launch_world_to_cam(const WorldToCamArgs& a, hipStream_t s);
 
+// include/misc.h:115-122 (zero-padded fixed-length form, see mcs_describe.hip)
+__device__ __forceinline__ double horner_fixed(const double* coeffs, double x) {
+	double res = 0.0;
+#pragma unroll
+	for (int i = MCS_MAX_POLY - 1; i >= 0; i--) res = res * x + coeffs[i];
+	return res;
+}
+
+// cCamModelGeneral_::WorldToImg (src/cam_model_omni.cpp:146-161): the one statement of the omni projection, for k_world_to_cam (mcs_project.hip)
+// and the Sim3 inlier test (mcs_sim3.hip)
+__device__ __forceinline__ void omni_world_to_img(const OcamDev& cam, double x, double y, double z, double& u, double& v) {
+	double norm = sqrt(x * x + y * y);
+	if (norm == 0.0) norm = 1e-14;
+	const double theta = atan(-z / norm);
+	const double rho = horner_fixed(cam.invP, theta);
+	const double uu = x / norm * rho;
+	const double vv = y / norm * rho;
+	u = uu * cam.c + vv * cam.d + cam.u0;
+	v = uu * cam.e + vv + cam.v0;
+}
+
 struct DistinctArgs {   // cMapPoint::ComputeDistinctiveDescriptors for a batch of map points (mcs_distinct.hip)
 	const uint8_t* desc; const uint8_t* mask; int stride; int dim;
 	const int* offsets;   // [npoints + 1] CSR row offsets of the observations of each map point

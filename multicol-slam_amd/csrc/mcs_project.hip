@@ -263,14 +263,6 @@ __global__ __launch_bounds__(64) void k_proj_greedy(ProjArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------- WorldToCamHom_fast
-// include/misc.h:115-122 (zero-padded fixed-length form, see mcs_describe.hip)
-__device__ __forceinline__ double horner_fixed(const double* coeffs, double x) {
-	double res = 0.0;
-#pragma unroll
-	for (int i = MCS_MAX_POLY - 1; i >= 0; i--) res = res * x + coeffs[i];
-	return res;
-}
-
 __global__ __launch_bounds__(64) void k_world_to_cam(WorldToCamArgs a) {
 	const int i = blockIdx.x * 64 + threadIdx.x;
 	if (i >= a.n) return;
@@ -285,15 +277,8 @@ __global__ __launch_bounds__(64) void k_world_to_cam(WorldToCamArgs a) {
 		for (int k = 0; k < 4; ++k) s += M[4 * row + k] * pt4[k];
 		r[row] = s;
 	}
-	const OcamDev& cam = a.cams[c];
-	double norm = sqrt(r[0] * r[0] + r[1] * r[1]);   // cCamModelGeneral_::WorldToImg (src/cam_model_omni.cpp:146-161)
-	if (norm == 0.0) norm = 1e-14;
-	const double theta = atan(-r[2] / norm);
-	const double rho = horner_fixed(cam.invP, theta);
-	const double uu = r[0] / norm * rho;
-	const double vv = r[1] / norm * rho;
-	const double u = uu * cam.c + vv * cam.d + cam.u0;
-	const double v = uu * cam.e + vv + cam.v0;
+	double u, v;
+	omni_world_to_img(a.cams[c], r[0], r[1], r[2], u, v);
 	a.uv[2 * (size_t)i] = u; a.uv[2 * (size_t)i + 1] = v;
 	const int ur = __double2int_rn(u), vr = __double2int_rn(v);
 	unsigned fl = 0;

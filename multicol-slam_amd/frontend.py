@@ -7,6 +7,7 @@
   cMultiCamSys_ (pose, projection)     src/cam_system_omni.cpp:92-133,168-198
   DescriptorDistance64[_Masked]        src/cORBmatcher.cpp:2438-2474
   cMultiKeyFrameDatabase               src/cMultiKeyFrameDatabase.cpp:43-329 (inverted file, relocalisation / loop candidates)
+  cSim3Solver (+ cSim3SolverBatch)     src/cSim3Solver.cpp (the RANSAC of cLoopClosing::ComputeSim3, one round over many candidates per call)
 
 Everything numeric runs in libmcs_hip.so on the GPU; this file only shapes inputs/outputs (numpy stands in for cv::Mat).
 """
@@ -270,6 +271,13 @@ class cMultiKeyFrame:
         self._d, self._m = F.all_descriptors(), F.all_masks()
         self.mBowVec, self.mFeatVec = getattr(F, "mBowVec", None), getattr(F, "mFeatVec", None)
         self.mvpOrderedConnectedKeyFrames = []
+        self.mvLevelSigma2 = list(getattr(F, "mvLevelSigma2", [1.0]))
+
+    def GetSigma2(self, nLevel=1):                  # include/cMultiKeyFrame.h:162-163
+        return self.mvLevelSigma2[nLevel]
+
+    def GetKeyPoint(self, idx):
+        return self.mvKeys[idx]
 
     def GetBestCovisibilityKeyFrames(self, N):      # src/cMultiKeyFrame.cpp:231-240
         return list(self.mvpOrderedConnectedKeyFrames[:N])
@@ -646,6 +654,13 @@ class cMapPoint:
                 return
         self.mObservations.append((pKF, [int(idx)]))
 
+    def GetIndexInKeyFrame(self, pKF):
+        """the feature indices of this point in pKF (empty if it has no observation there)"""
+        for kf, lst in self.mObservations:
+            if kf is pKF:
+                return list(lst)
+        return []
+
     def _observed(self, havingMasks):
         d, m = [], []
         for kf, lst in self.mObservations:
@@ -886,3 +901,175 @@ class cMultiKeyFrameDatabase:
         out = np.zeros(max(len(ids), 1))
         check(lib().mcs_kfdb_score(self.h, len(w), np_ptr(w), np_ptr(v), len(ids), np_ptr(ids), MEM_HOST, np_ptr(out)))
         return out[:len(ids)]
+
+
+class cSim3SolverBatch:
+    """Many cSim3Solver in one device batch (mcs_sim3_*): one iterate() call is one round of cLoopClosing::ComputeSim3 over all its candidates
+    (src/cLoopClosing.cpp:304-330), which equals the reference's sequential round because the solvers are independent.  The solvers' state
+    lives in the batch from here on; solver k draws as solver index k of `seed`."""
+
+    def __init__(self, solvers, ctx=None, seed=None, draws=None):
+        """solvers: cSim3Solver objects sharing one local rig; draws (optional): per solver an int array [max(1, maxIterations)][3] of randi."""
+        self.solvers = list(solvers)
+        s0 = self.solvers[0]
+        self.ctx = ctx or s0.ctx
+        self.seed = int(s0.seed if seed is None else seed)
+        cs = s0.camSysLocal
+        nr = cs.GetNrCams()
+        ns = len(self.solvers)
+        M_c = np.ascontiguousarray(np.stack([np.asarray(m, np.float64) for m in cs.M_c]).reshape(nr, 16))
+        ocs = (type(cs.cams[0].ocam) * nr)(*[cm.ocam for cm in cs.cams])
+        off = np.zeros(ns + 1, np.int32)
+        off[1:] = np.cumsum([s.N for s in self.solvers])
+        cat = lambda name, shape, dt: np.ascontiguousarray(np.concatenate([getattr(s, name) for s in self.solvers]).reshape(shape), dt) if off[-1] else np.zeros(shape, dt)
+        nc = int(off[-1])
+        self._n1 = np.array([s.mN1 for s in self.solvers], np.int32)
+        Xw, cam, sig, idx = cat("_Xw", (nc, 2, 3), np.float64), cat("_cam", (nc, 2), np.int32), cat("_sig", (nc, 2), np.float64), cat("_idx1", (nc,), np.int32)
+        Mt = np.ascontiguousarray(np.stack([s._Mt for s in self.solvers]), np.float64)
+        MtMc = np.ascontiguousarray(np.stack([s._MtMc for s in self.solvers]), np.float64)
+        p, mi, mx = self._params()
+        dr = None
+        if draws is not None:
+            dr = np.ascontiguousarray(np.concatenate([np.asarray(d, np.int32).reshape(-1) for d in draws]), np.int32)
+        self.h = C.c_void_p()
+        check(lib().mcs_sim3_create(self.ctx.h, nr, np_ptr(M_c), ocs, ns, np_ptr(self._n1), np_ptr(off), np_ptr(Mt), np_ptr(MtMc), np_ptr(p), np_ptr(mi),
+                                    np_ptr(mx), np_ptr(Xw), np_ptr(cam), np_ptr(sig), np_ptr(idx), C.c_uint64(self.seed & 0xFFFFFFFFFFFFFFFF),
+                                    np_ptr(dr), C.byref(self.h)))
+        self._keep = (Xw, cam, sig, idx, dr)
+        for k, s in enumerate(self.solvers):
+            s._batch, s._slot = self, k
+
+    def _params(self):
+        return (np.array([s.mRansacProb for s in self.solvers], np.float64), np.array([s.mRansacMinInliers for s in self.solvers], np.int32),
+                np.array([s.mRansacMaxItsParam for s in self.solvers], np.int32))
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().mcs_sim3_destroy(self.h)
+        except Exception:
+            pass
+
+    def SetRansacParameters(self):
+        """push every solver's (probability, minInliers, maxIterations) to the device: mnIterations = 0, the best-so-far state stays"""
+        p, mi, mx = self._params()
+        check(lib().mcs_sim3_set_ransac_parameters(self.h, np_ptr(p), np_ptr(mi), np_ptr(mx)))
+
+    def iterate(self, n):
+        """n: iterations per solver (an int for all, or a list; <= 0 leaves a solver alone) -> [(success, bNoMore, vbInliers, nInliers, T12)], T12 the
+        4x4 result where success, else None (the reference leaves the caller's matrix as it was)"""
+        ns = len(self.solvers)
+        nit = np.ascontiguousarray(np.broadcast_to(np.asarray(n, np.int32), (ns,)), np.int32)
+        succ, nomore, ninl = np.zeros(ns, np.uint8), np.zeros(ns, np.uint8), np.zeros(ns, np.int32)
+        T = np.zeros((ns, 16))
+        vb = np.zeros(max(int(self._n1.sum()), 1), np.uint8)
+        check(lib().mcs_sim3_iterate(self.h, np_ptr(nit), np_ptr(succ), np_ptr(nomore), np_ptr(ninl), np_ptr(T), np_ptr(vb)))
+        out, o = [], 0
+        for k in range(ns):
+            n1 = int(self._n1[k])
+            out.append((bool(succ[k]), bool(nomore[k]), vb[o:o + n1].astype(bool), int(ninl[k]), T[k].reshape(4, 4).copy() if succ[k] else None))
+            o += n1
+        return out
+
+    def best(self):
+        """-> (R [ns,3,3], t [ns,3], s [ns], T12 [ns,4,4], mnBestInliers [ns], mnIterations [ns])"""
+        ns = len(self.solvers)
+        R, t, s, T = np.zeros((ns, 9)), np.zeros((ns, 3)), np.zeros(ns), np.zeros((ns, 16))
+        bi, it = np.zeros(ns, np.int32), np.zeros(ns, np.int32)
+        check(lib().mcs_sim3_best(self.h, np_ptr(R), np_ptr(t), np_ptr(s), np_ptr(T), np_ptr(bi), np_ptr(it)))
+        return R.reshape(ns, 3, 3), t, s, T.reshape(ns, 4, 4), bi, it
+
+    def info(self):
+        """-> (N, mRansacMaxIts, mnIterations) per solver"""
+        ns = len(self.solvers)
+        n, mx, it = np.zeros(ns, np.int32), np.zeros(ns, np.int32), np.zeros(ns, np.int32)
+        check(lib().mcs_sim3_info(self.h, np_ptr(n), np_ptr(mx), np_ptr(it)))
+        return n, mx, it
+
+    def hypotheses(self, solver, first, count, masks=True):
+        """diagnostics: the hypotheses of iterations [first, first + count) of one solver -> dict(picks [count,3], n_inliers [count],
+        T12 / T21 [count,4,4], R [count,3,3], t [count,3], s [count], inliers [count,N] bool or None)"""
+        N = int(self.solvers[solver].N)
+        picks, cnt, hyp = np.zeros((max(count, 1), 3), np.int32), np.zeros(max(count, 1), np.int32), np.zeros((max(count, 1), 45))
+        inl = np.zeros((max(count, 1), max(N, 1)), np.uint8) if masks else None
+        check(lib().mcs_sim3_hypotheses(self.h, int(solver), int(first), int(count), np_ptr(picks), np_ptr(cnt), np_ptr(hyp), np_ptr(inl)))
+        hyp = hyp[:count]
+        return dict(picks=picks[:count], n_inliers=cnt[:count], T12=hyp[:, :16].reshape(-1, 4, 4), T21=hyp[:, 16:32].reshape(-1, 4, 4),
+                    R=hyp[:, 32:41].reshape(-1, 3, 3), t=hyp[:, 41:44], s=hyp[:, 44], inliers=None if inl is None else inl[:count, :N].astype(bool))
+
+
+class cSim3Solver:
+    """cSim3Solver (include/cSim3Solver.h, src/cSim3Solver.cpp): the constructor's pointer filtering runs here, everything numeric in the library
+    (mcs_sim3_*).  Keyframes need GetMapPointMatches(), GetKeyPoint(i)["octave"], GetSigma2(level), keypoint_to_cam and camSystem (M_t_inv,
+    MtMc_inv); map points isBad(), GetIndexInKeyFrame(pKF), GetWorldPos().  camSys: the local rig (cMultiCamSys_, its M_c and camera models)."""
+
+    def __init__(self, pKF1, pKF2, vpMatched12, camSys, ctx=None, seed=0):
+        self.ctx = ctx or default_context()
+        self.seed = int(seed)
+        self.camSysLocal = camSys
+        self.mpKF1, self.mpKF2 = pKF1, pKF2
+        self.mvpMatches12 = list(vpMatched12)
+        self.mN1 = len(self.mvpMatches12)
+        vpKeyFrameMP1 = pKF1.GetMapPointMatches()
+        X, cams, sig, idx1 = [], [], [], []
+        for i1, pMP2 in enumerate(self.mvpMatches12):   # :71-134
+            if pMP2 is None:
+                continue
+            pMP1 = vpKeyFrameMP1[i1]
+            if pMP1 is None:
+                continue
+            if pMP1.isBad() or pMP2.isBad():
+                continue
+            idxs1, idxs2 = pMP1.GetIndexInKeyFrame(pKF1), pMP2.GetIndexInKeyFrame(pKF2)
+            if len(idxs1) == 0 or len(idxs2) == 0:
+                continue
+            indexKF1, indexKF2 = int(idxs1[0]), int(idxs2[0])   # the first index only
+            if indexKF1 < 0 or indexKF2 < 0:
+                continue
+            sig.append((float(pKF1.GetSigma2(int(pKF1.GetKeyPoint(indexKF1)["octave"]))), float(pKF2.GetSigma2(int(pKF2.GetKeyPoint(indexKF2)["octave"])))))
+            cams.append((int(pKF1.keypoint_to_cam[indexKF1]), int(pKF2.keypoint_to_cam[indexKF2])))
+            X.append(np.concatenate([np.asarray(pMP1.GetWorldPos(), np.float64).reshape(-1)[:3], np.asarray(pMP2.GetWorldPos(), np.float64).reshape(-1)[:3]]))
+            idx1.append(i1)
+        self.N = len(idx1)
+        self._Xw = np.asarray(X, np.float64).reshape(self.N, 2, 3)
+        self._cam = np.asarray(cams, np.int32).reshape(self.N, 2)
+        self._sig = np.asarray(sig, np.float64).reshape(self.N, 2)
+        self._idx1 = np.asarray(idx1, np.int32)
+        self.mvnIndices1 = self._idx1
+        nr = camSys.GetNrCams()
+        self._Mt = np.stack([np.asarray(k.camSystem.M_t_inv, np.float64).reshape(16) for k in (pKF1, pKF2)])
+        self._MtMc = np.stack([np.stack([np.asarray(m, np.float64).reshape(16) for m in k.camSystem.MtMc_inv[:nr]]) for k in (pKF1, pKF2)])
+        self._batch, self._slot = None, 0
+        self.SetRansacParameters()
+
+    def SetRansacParameters(self, probability=0.99, minInliers=6, maxIterations=300):   # :139-165
+        self.mRansacProb, self.mRansacMinInliers, self.mRansacMaxItsParam = float(probability), int(minInliers), int(maxIterations)
+        if self._batch is not None:
+            self._batch.SetRansacParameters()
+
+    def _b(self):
+        if self._batch is None:
+            cSim3SolverBatch([self], self.ctx, self.seed)
+        return self._batch
+
+    def iterate(self, nIterations):
+        """-> (success, bNoMore, vbInliers [mN1] bool, nInliers, T12 4x4 or None)"""
+        b = self._b()
+        n = [0] * len(b.solvers)
+        n[self._slot] = int(nIterations)
+        return b.iterate(n)[self._slot]
+
+    def find(self):   # :256-262 -> (success, vbInliers12, nInliers, T12)
+        b = self._b()
+        mx = int(b.info()[1][self._slot])
+        ok, _, vb, n, T = self.iterate(mx)
+        return ok, vb, n, T
+
+    def GetEstimatedRotation(self):
+        return self._b().best()[0][self._slot]
+
+    def GetEstimatedTranslation(self):
+        return self._b().best()[1][self._slot]
+
+    def GetEstimatedScale(self):
+        return float(self._b().best()[2][self._slot])
