@@ -786,4 +786,106 @@ private:
 	mcs_sim3* h_ = nullptr;
 };
 
+// cLocalMapping::CreateNewMapPoints (src/cLocalMapping.cpp:223-381) over mcs_create_new_map_points: the current keyframe against its neighbours in the
+// given order (GetBestCovisibilityKeyFrames), ONE device call — every neighbour is searched with the features that earlier neighbours gave a map point
+// taken out.  KF: the caller's keyframe type with camSystem (a cMultiCamSys_ of this header), GetMapPointMatches() (a vector of MP*), GetKeyPoints() (a
+// vector of 28-byte cv::KeyPoint-layout records), GetKeyPointsRays() (Vec3d or anything indexable by 0..2), keypoint_to_cam and
+// cont_idx_to_local_cam_idx (find(i)->second), GetDescriptorRowPtr(cam, row) and, with havingMasks, GetDescriptorMaskRowPtr(cam, row)
+// (src/cMultiKeyFrame.cpp:356-364); MP: GetWorldPos().  Per neighbour the accepted matches come back in the reference's order with their points; the
+// map-point surgery (new cMapPoint, AddObservation, AddMapPoint, ComputeDistinctiveDescriptors, UpdateNormalAndDepth, :362-377) stays with the caller.
+struct NewMapPoints {
+	struct Neighbour {
+		std::vector<std::pair<size_t, size_t>> vMatchedIndices;   // accepted (idx1, idx2), ascending idx1
+		std::vector<Vec3d> x3D;                                    // their points, world frame
+		std::vector<int32_t> match12, verdict;                     // per feature of the current keyframe: the search's match, MCS_NP_*
+		int nmatches = 0, fallbacks = 0;
+		double baseline = 0, medianDepth = 0;
+		bool skipped = false;                                      // baseline / medianDepth < 0.01 (:250-254)
+	};
+	std::vector<Neighbour> neighbours;
+	std::vector<uint8_t> valid1;   // "has no map point yet" of the current keyframe after the loop
+};
+
+template <class KF, class MP>
+NewMapPoints CreateNewMapPoints(Context& ctx, KF* pKF, const std::vector<KF*>& vpNeighKFs, bool checkOrientation = false, int descDim = 32,
+                                bool havingMasks = false, double cosThresh = std::cos(3.0 * 3.14159265358979323846 / 180.0), double maxDIST = 25.0, int K = 16) {
+	struct Flat {   // one keyframe as the call reads it
+		std::vector<double> MtMc, MtMcInv, rays, mpPos;
+		std::vector<mcs_ocam> cams;
+		std::vector<mcs_keypoint> keys;
+		std::vector<int32_t> cam, mpCam;
+		std::vector<uint8_t> desc, mask, valid;
+		mcs_kf_geom g{};
+		mcs_desc_set d{};
+	};
+	auto flatten = [&](KF* kf, Flat& f, bool withMp) {
+		cMultiCamSys_& cs = kf->camSystem;
+		const int nr = cs.GetNrCams();
+		for (int c = 0; c < nr; ++c) {
+			f.MtMc.insert(f.MtMc.end(), cs.MtMc[c].begin(), cs.MtMc[c].end());
+			f.MtMcInv.insert(f.MtMcInv.end(), cs.MtMc_inv[c].begin(), cs.MtMc_inv[c].end());
+			f.cams.push_back(cs.camModels[c].ocam);
+		}
+		const auto keys = kf->GetKeyPoints();
+		const auto rays = kf->GetKeyPointsRays();
+		const std::vector<MP*> mps = kf->GetMapPointMatches();
+		const size_t n = keys.size();
+		f.keys.resize(n); f.cam.resize(n); f.valid.resize(n); f.rays.resize(3 * n);
+		f.desc.resize(n * (size_t)descDim);
+		if (havingMasks) f.mask.resize(n * (size_t)descDim);
+		for (size_t i = 0; i < n; ++i) {
+			static_assert(sizeof(keys[0]) == sizeof(mcs_keypoint), "GetKeyPoints() must hold cv::KeyPoint-layout records");
+			std::memcpy(&f.keys[i], &keys[i], sizeof(mcs_keypoint));
+			for (int k = 0; k < 3; ++k) f.rays[3 * i + k] = Sim3At(rays[i], k);
+			const int c = (int)kf->keypoint_to_cam.find(i)->second, row = (int)kf->cont_idx_to_local_cam_idx.find(i)->second;
+			f.cam[i] = c;
+			std::memcpy(&f.desc[i * (size_t)descDim], kf->GetDescriptorRowPtr(c, row), (size_t)descDim);
+			if (havingMasks) std::memcpy(&f.mask[i * (size_t)descDim], kf->GetDescriptorMaskRowPtr(c, row), (size_t)descDim);
+			f.valid[i] = mps[i] ? 0 : 1;   // "if (pMP1) continue", src/cORBmatcher.cpp:1017-1020
+			if (withMp && mps[i]) {
+				const auto X = mps[i]->GetWorldPos();
+				for (int k = 0; k < 3; ++k) f.mpPos.push_back(Sim3At(X, k));
+				f.mpCam.push_back(c);
+			}
+		}
+		f.g.MtMc = f.MtMc.data(); f.g.MtMc_inv = f.MtMcInv.data(); f.g.M_t = cs.M_t.data(); f.g.cams = f.cams.data();
+		f.g.rays = f.rays.data(); f.g.keys = f.keys.data(); f.g.cam = f.cam.data(); f.g.n = (int32_t)n; f.g.nr_cams = nr;
+		f.g.mp_pos = f.mpPos.data(); f.g.mp_cam = f.mpCam.data(); f.g.n_mp = (int32_t)f.mpCam.size();
+		f.d.desc = f.desc.data(); f.d.mask = havingMasks ? f.mask.data() : nullptr; f.d.valid = f.valid.data(); f.d.group = f.cam.data();
+		f.d.n = (int32_t)n; f.d.stride = descDim;
+	};
+	NewMapPoints out;
+	const int ns = (int)vpNeighKFs.size();
+	Flat cur;
+	flatten(pKF, cur, false);
+	const size_t n1 = (size_t)cur.g.n;
+	out.valid1 = cur.valid;
+	if (ns == 0) return out;
+	std::vector<Flat> nb((size_t)ns);
+	std::vector<mcs_kf_geom> g2((size_t)ns);
+	std::vector<mcs_desc_set> d2((size_t)ns);
+	for (int s = 0; s < ns; ++s) { flatten(vpNeighKFs[s], nb[s], true); g2[s] = nb[s].g; d2[s] = nb[s].d; }
+	const size_t rows = std::max<size_t>(n1 * (size_t)ns, 1);
+	std::vector<int32_t> verdict(rows), cnt((size_t)ns), a1(rows), a2(rows), m12(rows, -1), nm((size_t)ns), fb((size_t)ns);
+	std::vector<double> x3D(3 * rows), ax(3 * rows), bl((size_t)ns), md((size_t)ns);
+	std::vector<uint8_t> sk((size_t)ns), v1(std::max<size_t>(n1, 1));
+	mcs_newpoints_out o{verdict.data(), x3D.data(), cnt.data(), a1.data(), a2.data(), ax.data()};
+	mcs_throw(mcs_create_new_map_points(ctx.h, ns, &cur.g, &cur.d, g2.data(), d2.data(), nullptr, 0, descDim, K, checkOrientation ? 1 : 0, cosThresh, maxDIST,
+	                                    MCS_MEM_HOST, m12.data(), nm.data(), fb.data(), bl.data(), md.data(), sk.data(), v1.data(), &o));
+	out.valid1.assign(v1.begin(), v1.begin() + (std::ptrdiff_t)n1);
+	out.neighbours.resize((size_t)ns);
+	for (int s = 0; s < ns; ++s) {
+		NewMapPoints::Neighbour& r = out.neighbours[s];
+		const size_t lo = (size_t)s * n1;
+		r.match12.assign(m12.begin() + (std::ptrdiff_t)lo, m12.begin() + (std::ptrdiff_t)(lo + n1));
+		r.verdict.assign(verdict.begin() + (std::ptrdiff_t)lo, verdict.begin() + (std::ptrdiff_t)(lo + n1));
+		r.nmatches = nm[s]; r.fallbacks = fb[s]; r.baseline = bl[s]; r.medianDepth = md[s]; r.skipped = sk[s] != 0;
+		for (int k = 0; k < cnt[s]; ++k) {
+			r.vMatchedIndices.emplace_back((size_t)a1[lo + k], (size_t)a2[lo + k]);
+			r.x3D.push_back(Vec3d{{ax[3 * (lo + k)], ax[3 * (lo + k) + 1], ax[3 * (lo + k) + 2]}});
+		}
+	}
+	return out;
+}
+
 }  // namespace MultiColSLAM

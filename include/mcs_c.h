@@ -466,6 +466,63 @@ int mcs_sim3_info(const mcs_sim3*, int32_t* n, int32_t* max_its, int32_t* iterat
 int mcs_sim3_hypotheses(mcs_sim3*, int solver, int first, int count, int32_t* picks, int32_t* n_inliers, double* hyp, uint8_t* inliers);
 int mcs_sim3_draw(uint64_t seed, int solver, int iteration, int pick, int n);
 
+/* ------------------------------------------------------------------ cLocalMapping::CreateNewMapPoints (src/cLocalMapping.cpp:223-381): new map points on the device
+ * A keyframe as the loop reads it.  Every POINTER of the struct lives where the call's `kind` says (the matrices and camera models too, so a device-kind call touches
+ * no host memory); the struct itself and its counts are host values.
+ *   MtMc / MtMc_inv   cMultiCamSys_::Get_MtMc(c) / Get_MtMc_inv(c), 4x4 row-major per camera (the reference reads both cached, :285-288)
+ *   M_t               the rig pose; GetCameraCenter() = Hom2T(M_t) (src/cMultiKeyFrame.cpp:156-162)
+ *   cams              the camera models of camSystem (WorldToCamHom_fast, src/cam_system_omni.cpp:92-112; only the backward polynomial is read)
+ *   rays / keys / cam GetKeyPointsRays() (3 doubles per feature), GetKeyPoints() (pt.x, pt.y, angle are read), keypoint_to_cam
+ *   mp_pos / mp_cam   neighbours of mcs_create_new_map_points only: GetWorldPos() and keypoint_to_cam of the n_mp features that hold a map point, in feature
+ *                     order (ComputeSceneMedianDepth, src/cMultiKeyFrame.cpp:747-778) */
+typedef struct {
+	const double* MtMc; const double* MtMc_inv; const double* M_t; const mcs_ocam* cams;
+	const double* rays; const mcs_keypoint* keys; const int32_t* cam; int32_t n; int32_t nr_cams;
+	const double* mp_pos; const int32_t* mp_cam; int32_t n_mp;
+} mcs_kf_geom;
+/* Per (pair s, feature i of the first keyframe), n1 features per pair:
+ *   verdict[s*n1 + i]  MCS_NP_*: where the loop body :272-361 left the match
+ *   x3D[(s*n1 + i)*3]  the triangulated point in the world frame (:310-314) of every match that passed the parallax check, whatever became of it; zeros otherwise
+ * Per pair: acc_count[s] accepted matches in the reference's order (ascending idx1, src/cORBmatcher.cpp:1140-1152) as acc_idx1 / acc_idx2[s*n1 + k],
+ * acc_x3D[(s*n1 + k)*3] — the arguments of `new cMapPoint(x3D, ...)`, AddObservation and AddMapPoint (:362-368), which stay with the caller. */
+typedef struct {
+	int32_t* verdict; double* x3D; int32_t* acc_count; int32_t* acc_idx1; int32_t* acc_idx2; double* acc_x3D;
+} mcs_newpoints_out;
+#define MCS_NP_NO_MATCH 0
+#define MCS_NP_ACCEPTED 1
+#define MCS_NP_PARALLAX 2   /* cosParallax < 0 || cosParallax > cosThresh, :303 */
+#define MCS_NP_BEHIND_1 3   /* WorldToCamHom_fast into the current keyframe reports z <= 0, :323-325 */
+#define MCS_NP_REPROJ_1 4   /* sqrt(errX1^2 + errY1^2) > 4.0, :327-330 */
+#define MCS_NP_BEHIND_2 5   /* :337-339 */
+#define MCS_NP_REPROJ_2 6   /* :341-344 */
+#define MCS_NP_DISTANCE 7   /* dist1 == 0 || dist2 == 0 || dist1 > maxDIST || dist2 > maxDIST, :359-361 */
+#define MCS_NP_SKIPPED 8    /* the pair was gated (baseline / median depth < 0.01, :250-254) */
+/* mcs_triangulate_matches   the loop body of CreateNewMapPoints (src/cLocalMapping.cpp:269-361, triangulate_point of src/misc.cpp:25-50) for nsets independent
+ *     (kf1[s], kf2[s]) pairs with GIVEN matches: match12[s*n1 + i] = feature of kf2[s] matched to feature i of kf1[s], or -1 (n1 = kf1[s].n, the same for every s).
+ *     skipped (optional, [nsets]): pairs that read "pair skipped".  cosThresh / maxDIST: the reference's constants are cos(3 degrees) and 25.0 (:39-43).
+ *     The comparisons are the reference's as written: a NaN passes every one of them, so a degenerate pair can be accepted with a NaN point; ratio1 and
+ *     sigmaSquare1 / 2 are dead there and not computed.  A match12 entry or camera index out of range reads "no match" (host-kind: MCS_ERR_INVALID).
+ * mcs_create_new_map_points the whole neighbour loop :239-381: the current keyframe kf1 against nsets neighbours in the caller's order
+ *     (GetBestCovisibilityKeyFrames).  Once: per neighbour the essential matrices ComputeE(kf1.MtMc_inv[c1], kf2.MtMc[c2]) (src/misc.cpp:71-85 as
+ *     src/cORBmatcher.cpp:988-999 calls it; or the caller's own E blocks, laid out as mcs_search_triangulation_sweep takes them), baseline = norm(Ow2 - Ow1) and
+ *     median_depth = ComputeSceneMedianDepth(2); skipped[s] = (baseline / median_depth < 0.01), which a negative median satisfies too.  Then per neighbour, in
+ *     order: SearchForTriangulationRaw (mcs_search_triangulation: kf*_desc are its sets, valid = "has NO map point yet", group = keypoint_to_cam, contiguous
+ *     rows) with the current keyframe's valid flags read from the working copy valid1 (initialised from kf1_desc->valid; it may be that very array), with
+ *     check_orientation the rotation filter (mcs_rotation_consistency variant 3), and the loop body above, which clears valid1[idx1] of every accepted match
+ *     (AddMapPoint(pMP, idx1), :367) before the next neighbour is searched.  A skipped neighbour changes nothing: its match12 reads -1, its verdicts
+ *     MCS_NP_SKIPPED, its counts 0.  Outputs: match12[nsets*n1], nmatches[nsets] (after the rotation filter), fallbacks[nsets] (optional), baseline /
+ *     median_depth / skipped[nsets], valid1[n1] as the loop leaves it (so the rest of a neighbour list can follow in a second call), and `out`.
+ *     A neighbour without a map point is refused with MCS_ERR_INVALID before anything runs (the reference indexes an empty vector there).  Refused with
+ *     MCS_ERR_UNSUPPORTED while deferred searches are on (mcs_ctx_set_async_search).
+ * kind: where every array (behind the structs too) lives.  DEVICE: the call only enqueues work, and all its outputs are complete in the order of the context's
+ * stream when it returns (no mcs_ctx_join needed). */
+int mcs_triangulate_matches(mcs_ctx*, int nsets, const mcs_kf_geom* kf1, const mcs_kf_geom* kf2, const int32_t* match12, const uint8_t* skipped,
+                            double cosThresh, double maxDIST, mcs_mem_kind kind, const mcs_newpoints_out* out);
+int mcs_create_new_map_points(mcs_ctx*, int nsets, const mcs_kf_geom* kf1, const mcs_desc_set* kf1_desc, const mcs_kf_geom* kf2 /* [nsets] */,
+                              const mcs_desc_set* kf2_desc /* [nsets] */, const double* E /* optional */, size_t E_set_pitch, int dim, int K,
+                              int check_orientation, double cosThresh, double maxDIST, mcs_mem_kind kind, int32_t* match12, int32_t* nmatches,
+                              int32_t* fallbacks, double* baseline, double* median_depth, uint8_t* skipped, uint8_t* valid1, const mcs_newpoints_out* out);
+
 /* self-test of an arithmetic shortcut of the descriptor kernel: the omni model's three divisions by the same norm (src/cam_model_omni.cpp:
  * 146-161) share one refined reciprocal; this runs n pseudo-random (numerator, denominator) pairs of the magnitudes the kernel sees through
  * both forms on the device and returns the number of results that are not bit-identical to a / d (must be 0). */

@@ -76,6 +76,7 @@ EXPORTS = [
     "mcs_kfdb_set_covisibility", "mcs_kfdb_detect_relocalisation", "mcs_kfdb_detect_loop", "mcs_kfdb_score",
     "mcs_sim3_create", "mcs_sim3_destroy", "mcs_sim3_set_ransac_parameters", "mcs_sim3_iterate", "mcs_sim3_best", "mcs_sim3_info",
     "mcs_sim3_hypotheses", "mcs_sim3_draw",
+    "mcs_triangulate_matches", "mcs_create_new_map_points",
 ]
 
 WINDOW_RATIO, WINDOW_BEST, WINDOW_INITIALIZE = 1, 2, 3
@@ -101,6 +102,20 @@ class FrameView(C.Structure):
 class KfdbDiag(C.Structure):
     _fields_ = [("cap", C.c_int32), ("count", C.c_void_p), ("kf_id", C.c_void_p), ("words", C.c_void_p), ("score", C.c_void_p), ("acc", C.c_void_p),
                 ("best", C.c_void_p)]
+
+
+class KfGeom(C.Structure):   # mcs_kf_geom: a keyframe as cLocalMapping::CreateNewMapPoints reads it (src/cLocalMapping.cpp:223-381)
+    _fields_ = [("MtMc", C.c_void_p), ("MtMc_inv", C.c_void_p), ("M_t", C.c_void_p), ("cams", C.c_void_p), ("rays", C.c_void_p), ("keys", C.c_void_p),
+                ("cam", C.c_void_p), ("n", C.c_int32), ("nr_cams", C.c_int32), ("mp_pos", C.c_void_p), ("mp_cam", C.c_void_p), ("n_mp", C.c_int32)]
+
+
+class NewPointsOut(C.Structure):   # mcs_newpoints_out
+    _fields_ = [("verdict", C.c_void_p), ("x3D", C.c_void_p), ("acc_count", C.c_void_p), ("acc_idx1", C.c_void_p), ("acc_idx2", C.c_void_p),
+                ("acc_x3D", C.c_void_p)]
+
+
+# verdict codes of mcs_triangulate_matches / mcs_create_new_map_points (MCS_NP_* of include/mcs_c.h)
+NP_NO_MATCH, NP_ACCEPTED, NP_PARALLAX, NP_BEHIND_1, NP_REPROJ_1, NP_BEHIND_2, NP_REPROJ_2, NP_DISTANCE, NP_SKIPPED = range(9)
 
 
 _lib = None
@@ -198,6 +213,9 @@ def lib():
     L.mcs_sim3_info.argtypes = [vp, vp, vp, vp]
     L.mcs_sim3_hypotheses.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     L.mcs_sim3_draw.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.mcs_triangulate_matches.argtypes = [vp, C.c_int, C.POINTER(KfGeom), C.POINTER(KfGeom), vp, vp, C.c_double, C.c_double, C.c_int, C.POINTER(NewPointsOut)]
+    L.mcs_create_new_map_points.argtypes = [vp, C.c_int, C.POINTER(KfGeom), C.POINTER(DescSet), C.POINTER(KfGeom), C.POINTER(DescSet), vp, C.c_size_t, C.c_int,
+                                            C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.POINTER(NewPointsOut)]
     L.mcs_copy_narrow.argtypes = [vp, vp, vp, C.c_size_t, C.c_int, vp]
     L.mcs_ctx_result_stream.argtypes = [vp, C.POINTER(vp)]
     L.mcs_ctx_stream_conflicts.argtypes = [vp, vp, C.POINTER(C.c_uint)]

@@ -386,7 +386,7 @@ int mcs_ctx_destroy(mcs_ctx* c) {
 	while (!c->extractors.empty()) (void)mcs_extractor_destroy(c->extractors.back());   // an extractor must not outlive the stream it runs on
 	for (auto& kv : c->timers) { if (kv.second.a) { (void)hipEventDestroy(kv.second.a); (void)hipEventDestroy(kv.second.b); } }
 	(void)hipFree(c->partial); (void)hipFree(c->partialCount); (void)hipFree(c->stage); (void)hipFree(c->dscalar);
-	(void)hipFree(c->topKeys); (void)hipFree(c->topKeys2); (void)hipFree(c->topCnt); (void)hipFree(c->exA); (void)hipFree(c->exW); (void)hipFree(c->exRows); (void)hipFree(c->stageOut); (void)hipFree(c->arena); if (c->pinned) (void)hipHostFree(c->pinned);
+	(void)hipFree(c->topKeys); (void)hipFree(c->topKeys2); (void)hipFree(c->topCnt); (void)hipFree(c->exA); (void)hipFree(c->exW); (void)hipFree(c->exRows); (void)hipFree(c->stageOut); (void)hipFree(c->arena); (void)hipFree(c->npBuf); if (c->pinned) (void)hipHostFree(c->pinned);
 	if (c->side) {
 		(void)hipStreamSynchronize(c->side);
 		(void)hipStreamSynchronize(c->side2);

@@ -54,6 +54,7 @@ struct mcs_ctx {
 	uint8_t* stageOut = nullptr; size_t stageOutCap = 0;
 	uint8_t* pinned = nullptr; size_t pinnedCap = 0;      // page-locked host mirror of the arena's staged inputs (PinnedUpload)
 	uint8_t* arena = nullptr; size_t arenaCap = 0;        // scratch + host-kind staging of the window / projection / map-point entry points (mcs_capi_window.hip)
+	uint8_t* npBuf = nullptr; size_t npBufCap = 0;        // mcs_create_new_map_points: essential matrices, depths, the rotation filter's counter (mcs_newpoints.hip)
 	// Second HIP stream for the latency-bound / independent kernels (blur next to FAST+oct-tree, the greedy resolution next to the
 	// following batch's extraction): they leave most CUs idle, so overlapping them with the VALU-bound kernels is free throughput.
 	hipStream_t side = nullptr;    // extraction fork: resize chain + blur beside FAST + oct-tree

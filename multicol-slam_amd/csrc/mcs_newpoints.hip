@@ -1,0 +1,548 @@
+// mcs_newpoints.hip — cLocalMapping::CreateNewMapPoints (src/cLocalMapping.cpp:223-381): the mapping thread's chain, keyframe in, new map points out.
+//   k_np_setup        per neighbour, once: z = row 2 of MtMc_inv[cam(i)] (X, 1) of every feature that holds a map point (ComputeSceneMedianDepth,
+//                     src/cMultiKeyFrame.cpp:747-778); workgroup 0 also forms the nrCams x nrCams essential matrices ComputeE(kf1.MtMc_inv[c1], kf2.MtMc[c2])
+//                     (src/misc.cpp:71-85, as src/cORBmatcher.cpp:988-999 calls it) and baseline = norm(Ow2 - Ow1) (:246-248)
+//   k_np_median       thread per depth: its rank among all depths; the one of rank (n - 1) / 2 is vDepths[(n - 1) / 2] of the ascending sort (a value
+//                     selection: equal depths are the same double), and with it the gate baseline / median < 0.01 (:250-254)
+//   k_np_triangulate  thread per feature of the current keyframe that has a match: the loop body :272-361 statement by statement (parallax, relOri,
+//                     triangulate_point of src/misc.cpp:25-50, both reprojections through omni_world_to_img, the distance check); in the chain it also clears
+//                     valid1[idx1] of an accepted match (AddMapPoint(pMP, idx1), :367) and the matches of a gated neighbour
+//   k_np_compact      one workgroup per pair: the accepted matches in the reference's order (ascending idx1, src/cORBmatcher.cpp:1140-1152)
+// mcs_create_new_map_points enqueues, per neighbour in the caller's order, the triangulation search (csrc/mcs_capi_match.hip) with the query side's valid flags read
+// from a device working copy, then k_np_triangulate + k_np_compact behind the search's greedy pass (an event, no host wait); the next neighbour's search is enqueued
+// behind them on the context's stream.  FP64 throughout, no contraction (-ffp-contract=off): every product and sum is the reference's, in its order; the OpenCV
+// pieces are restated as DESIGN.md section 7 lists them.
+#include "mcs_host.h"
+#include <algorithm>
+#include <cstddef>
+
+namespace mcs {
+void launch_rotation_consistency(int variant, const float* angleSlot, int strideSlot, const float* anglePartner, int stridePartner, const int* accepted, int* match,
+                                 int n, int swapped, int* removed, hipStream_t s);
+
+struct NpKf {   // device view of one keyframe (mcs_kf_geom with every pointer on the GPU)
+	const double* MtMc; const double* MtMcInv; const double* Mt; const mcs_ocam* cams;
+	const double* rays; const mcs_keypoint* keys; const int* cam; int n, nrCams;
+};
+
+struct NpSetupArgs {
+	NpKf k1, k2;
+	const double* mpPos; const int* mpCam; int nmp;   // the neighbour's features that hold a map point: world position, camera
+	double* z;                                        // [nmp] scratch
+	double* E;                                        // [nrCams * nrCams][9] or nullptr (the caller's own blocks are used)
+	double* baseline; double* median; uint8_t* skip;  // this neighbour's entries
+};
+
+struct NpTriArgs {
+	NpKf k1, k2;
+	const int* match12;     // [n1] feature of keyframe 2 matched to feature i, or -1
+	int* matchClear;        // chain only: the same array, cleared for a gated neighbour
+	const uint8_t* skip;    // this pair's "skipped" flag, or nullptr
+	uint8_t* valid1;        // chain only: working copy of the current keyframe's "has no map point yet"
+	double cosThresh, maxDist;
+	int* verdict; double* x3D;
+};
+
+// cv::norm(Vec3d): sqrt(((0 + a0^2) + a1^2) + a2^2)
+__device__ __forceinline__ double np_norm3(const double* v) {
+	double s = 0;
+	for (int k = 0; k < 3; ++k) s += v[k] * v[k];
+	return sqrt(s);
+}
+// Matx::dot / Vec::dot: s = 0; s += a(k) * b(k)
+__device__ __forceinline__ double np_dot3(const double* a, const double* b) {
+	double s = 0;
+	for (int k = 0; k < 3; ++k) s += a[k] * b[k];
+	return s;
+}
+// top-left 3x3 of a row-major 4x4 (or a 3x3 with ld = 3) times a 3-vector: s = 0; s += a(i,k) * b(k)
+__device__ __forceinline__ void np_mat3_vec3(const double* M, int ld, const double* p, double* r) {
+	for (int i = 0; i < 3; ++i) {
+		double s = 0;
+		for (int k = 0; k < 3; ++k) s += M[ld * i + k] * p[k];
+		r[i] = s;
+	}
+}
+__device__ __forceinline__ void np_mat4_vec4(const double* M, const double* p, double* r) {
+	for (int i = 0; i < 4; ++i) {
+		double s = 0;
+		for (int k = 0; k < 4; ++k) s += M[4 * i + k] * p[k];
+		r[i] = s;
+	}
+}
+
+// cv::Matx33d ComputeE(const cv::Matx44d& T1, const cv::Matx44d& T2) (src/misc.cpp:71-85)
+__device__ void np_compute_E(const double* T1, const double* T2, double* E) {
+	double R12[9], N[9], t12[3];
+	for (int i = 0; i < 3; ++i)
+		for (int j = 0; j < 3; ++j) {   // R1w * R2w.t() and (-R1w) * R2w.t()
+			double s = 0, sn = 0;
+			for (int k = 0; k < 3; ++k) { s += T1[4 * i + k] * T2[4 * j + k]; sn += (-T1[4 * i + k]) * T2[4 * j + k]; }
+			R12[3 * i + j] = s; N[3 * i + j] = sn;
+		}
+	const double t1w[3] = {T1[3], T1[7], T1[11]}, t2w[3] = {T2[3], T2[7], T2[11]};
+	np_mat3_vec3(N, 3, t2w, t12);
+	for (int i = 0; i < 3; ++i) t12[i] = t12[i] + t1w[i];
+	const double ialpha = 1. / np_norm3(t12);   // Vec operator/=(double) of OpenCV 3.x: a multiplication by 1./alpha
+	for (int i = 0; i < 3; ++i) t12[i] = t12[i] * ialpha;
+	const double S[9] = {0.0, -t12[2], t12[1], t12[2], 0.0, -t12[0], -t12[1], t12[0], 0.0};   // Skew (include/misc.h:58-64)
+	for (int i = 0; i < 3; ++i)
+		for (int j = 0; j < 3; ++j) {
+			double s = 0;
+			for (int k = 0; k < 3; ++k) s += S[3 * i + k] * R12[3 * k + j];
+			E[3 * i + j] = s;
+		}
+}
+
+__global__ __launch_bounds__(256) void k_np_setup(NpSetupArgs a) {
+	const int g = blockIdx.x * 256 + threadIdx.x;
+	if (g < a.nmp) {   // src/cMultiKeyFrame.cpp:764-771
+		const int c = a.mpCam[g];
+		double z = __longlong_as_double(0x7FF8000000000000ll);   // a camera index outside the rig: no depth
+		if (c >= 0 && c < a.k2.nrCams) {
+			const double x4[4] = {a.mpPos[3 * (size_t)g], a.mpPos[3 * (size_t)g + 1], a.mpPos[3 * (size_t)g + 2], 1.0};
+			double r[4];
+			np_mat4_vec4(a.k2.MtMcInv + 16 * (size_t)c, x4, r);
+			z = r[2];
+		}
+		a.z[g] = z;
+	}
+	if (blockIdx.x != 0) return;
+	if (a.E) {
+		const int nr = a.k1.nrCams;
+		for (int t = threadIdx.x; t < nr * nr; t += 256)
+			np_compute_E(a.k1.MtMcInv + 16 * (size_t)(t / nr), a.k2.MtMc + 16 * (size_t)(t % nr), a.E + 9 * (size_t)t);
+	}
+	if (threadIdx.x == 0) {   // src/cLocalMapping.cpp:230, 246-248; GetCameraCenter = Hom2T(M_t)
+		double vb[3];
+		for (int k = 0; k < 3; ++k) vb[k] = a.k2.Mt[4 * k + 3] - a.k1.Mt[4 * k + 3];
+		*a.baseline = np_norm3(vb);
+		*a.median = __longlong_as_double(0x7FF8000000000000ll);   // stays NaN only when no depth has the wanted rank (a NaN depth: the reference's sort is undefined then)
+		*a.skip = 0;
+	}
+}
+
+__global__ __launch_bounds__(256) void k_np_median(const double* __restrict__ z, int n, const double* __restrict__ baseline, double* median, uint8_t* skip) {
+	__shared__ double tile[256];
+	const int j = blockIdx.x * 256 + threadIdx.x;
+	const double zj = j < n ? z[j] : 0.0;
+	int less = 0, leq = 0;
+	for (int base = 0; base < n; base += 256) {
+		__syncthreads();
+		if (base + (int)threadIdx.x < n) tile[threadIdx.x] = z[base + threadIdx.x];
+		__syncthreads();
+		const int m = min(256, n - base);
+		for (int k = 0; k < m; ++k) { const double v = tile[k]; less += v < zj; leq += v <= zj; }
+	}
+	const int r = (n - 1) / 2;   // vDepths[(vDepths.size() - 1) / q], q = 2
+	if (j < n && less <= r && r < leq) {   // every thread that gets here holds the same double
+		*median = zj;
+		const double ratioBaselineDepth = *baseline / zj;
+		*skip = ratioBaselineDepth < 0.01 ? 1 : 0;
+	}
+}
+
+// bool cMultiCamSys_::WorldToCamHom_fast(int c, cv::Vec4d&, cv::Vec2d&) (src/cam_system_omni.cpp:92-112, the flagMcMt branch)
+__device__ __noinline__ bool np_world_to_cam(const NpKf& kf, int c, const double* pt4, double& u, double& v) {
+	double r[4];
+	np_mat4_vec4(kf.MtMcInv + 16 * (size_t)c, pt4, r);
+	const mcs_ocam& m = kf.cams[c];
+	OcamDev o;
+	o.c = m.c; o.d = m.d; o.e = m.e; o.u0 = m.u0; o.v0 = m.v0;
+	const int deg = m.invP_deg;
+	for (int k = 0; k < MCS_MAX_POLY; ++k) o.invP[k] = k < deg ? m.invP[k] : 0.0;
+	omni_world_to_img(o, r[0], r[1], r[2], u, v);
+	return r[2] <= 0.0;
+}
+
+enum { NP_NONE = 0, NP_ACCEPTED = 1, NP_PARALLAX = 2, NP_BEHIND1 = 3, NP_REPROJ1 = 4, NP_BEHIND2 = 5, NP_REPROJ2 = 6, NP_DISTANCE = 7, NP_SKIPPED = 8 };
+
+__global__ __launch_bounds__(128) void k_np_triangulate(NpTriArgs a) {
+	const int i = blockIdx.x * 128 + threadIdx.x;
+	if (i >= a.k1.n) return;
+	double* X = a.x3D + 3 * (size_t)i;
+	X[0] = 0.0; X[1] = 0.0; X[2] = 0.0;   // cv::Vec3d x3D(0.0, 0.0, 0.0), :283
+	if (a.skip && *a.skip) {   // :253-254, the neighbour changes nothing
+		if (a.matchClear) a.matchClear[i] = -1;
+		a.verdict[i] = NP_SKIPPED;
+		return;
+	}
+	const int idx2 = a.match12[i];
+	if (idx2 < 0 || idx2 >= a.k2.n) { a.verdict[i] = NP_NONE; return; }
+	const int camIdx1 = a.k1.cam[i], camIdx2 = a.k2.cam[idx2];   // :275-276
+	if (camIdx1 < 0 || camIdx1 >= a.k1.nrCams || camIdx2 < 0 || camIdx2 >= a.k2.nrCams) { a.verdict[i] = NP_NONE; return; }
+	const double* Tcw1 = a.k1.MtMc + 16 * (size_t)camIdx1;      // :285-288
+	const double* Tcw1inv = a.k1.MtMcInv + 16 * (size_t)camIdx1;
+	const double* Tcw2 = a.k2.MtMc + 16 * (size_t)camIdx2;
+	double ray1[3], ray2[3];
+	for (int k = 0; k < 3; ++k) { ray1[k] = a.k1.rays[3 * (size_t)i + k]; ray2[k] = a.k2.rays[3 * (size_t)idx2 + k]; }
+	double rayRot1[3], rayRot2[3];
+	np_mat3_vec3(Tcw1, 4, ray1, rayRot1);   // :297-298
+	np_mat3_vec3(Tcw2, 4, ray2, rayRot2);
+	const double cosParallax = np_dot3(rayRot1, rayRot2) / (np_norm3(rayRot1) * np_norm3(rayRot2));   // :300-301
+	if (cosParallax < 0 || cosParallax > a.cosThresh) { a.verdict[i] = NP_PARALLAX; return; }         // :303
+	double R12[9], t12[3];   // relOri = Tcw1inv * Tcw2 (:306), Hom2T / Hom2R (:307-308)
+	for (int r = 0; r < 3; ++r)
+		for (int j = 0; j < 4; ++j) {
+			double s = 0;
+			for (int k = 0; k < 4; ++k) s += Tcw1inv[4 * r + k] * Tcw2[4 * k + j];
+			if (j < 3) R12[3 * r + j] = s; else t12[r] = s;
+		}
+	// triangulate_point(t12, R12, ray1, ray2) (src/misc.cpp:25-50)
+	double f2[3];
+	np_mat3_vec3(R12, 3, ray2, f2);
+	const double b0 = np_dot3(t12, ray1), b1 = np_dot3(t12, f2);
+	const double a00 = np_dot3(ray1, ray1), a10 = np_dot3(ray1, f2), a01 = -a10, a11 = -np_dot3(f2, f2);
+	double i00 = 0.0, i01 = 0.0, i10 = 0.0, i11 = 0.0;   // Matx22d::inv(), OpenCV 3.x's closed form: a zero determinant gives the zero matrix
+	double d = a00 * a11 - a01 * a10;
+	if (d != 0) {
+		d = 1. / d;
+		i11 = a00 * d; i00 = a11 * d; i01 = -a01 * d; i10 = -a10 * d;
+	}
+	double l0 = 0, l1 = 0;
+	l0 += i00 * b0; l0 += i01 * b1;
+	l1 += i10 * b0; l1 += i11 * b1;
+	double x3[3];
+	for (int k = 0; k < 3; ++k) {
+		const double xm = l0 * ray1[k];
+		const double xn = t12[k] + l1 * f2[k];
+		x3[k] = (xm + xn) / 2.0;
+	}
+	const double p4[4] = {x3[0], x3[1], x3[2], 1.0};
+	double x3D4[4];
+	np_mat4_vec4(Tcw1, p4, x3D4);   // :312-314
+	X[0] = x3D4[0]; X[1] = x3D4[1]; X[2] = x3D4[2];
+	double u, v;
+	if (np_world_to_cam(a.k1, camIdx1, x3D4, u, v)) { a.verdict[i] = NP_BEHIND1; return; }   // :323-325
+	{
+		const double errX1 = u - (double)a.k1.keys[i].x, errY1 = v - (double)a.k1.keys[i].y;   // :327-330
+		if (sqrt(errX1 * errX1 + errY1 * errY1) > 4.0) { a.verdict[i] = NP_REPROJ1; return; }
+	}
+	if (np_world_to_cam(a.k2, camIdx2, x3D4, u, v)) { a.verdict[i] = NP_BEHIND2; return; }   // :337-339
+	{
+		const double errX2 = u - (double)a.k2.keys[idx2].x, errY2 = v - (double)a.k2.keys[idx2].y;   // :341-344
+		if (sqrt(errX2 * errX2 + errY2 * errY2) > 4.0) { a.verdict[i] = NP_REPROJ2; return; }
+	}
+	double normal1[3], normal2[3];   // :347-351
+	for (int k = 0; k < 3; ++k) { normal1[k] = x3D4[k] - a.k1.Mt[4 * k + 3]; normal2[k] = x3D4[k] - a.k2.Mt[4 * k + 3]; }
+	const double dist1 = np_norm3(normal1), dist2 = np_norm3(normal2);
+	if (dist1 == 0 || dist2 == 0 || dist1 > a.maxDist || dist2 > a.maxDist) { a.verdict[i] = NP_DISTANCE; return; }   // :359-361
+	a.verdict[i] = NP_ACCEPTED;
+	if (a.valid1) a.valid1[i] = 0;   // mpCurrentMultiKeyFrame->AddMapPoint(pMP, idx1), :367
+}
+
+// accepted matches of one pair in ascending idx1; nmatches = the matches the loop body saw (every verdict but "no match" and "pair skipped")
+__global__ __launch_bounds__(1024) void k_np_compact(const int* __restrict__ match12, const int* __restrict__ verdict, const double* __restrict__ x3D, int n1,
+                                                     int* nmatches, int* accCount, int* accIdx1, int* accIdx2, double* accX) {
+	__shared__ int waveAcc[16], waveM[16];
+	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	int base = 0, mtotal = 0;
+	for (int start = 0; start < n1; start += 1024) {
+		const int i = start + tid;
+		const int vd = i < n1 ? verdict[i] : NP_NONE;
+		const bool acc = vd == NP_ACCEPTED, m = vd != NP_NONE && vd != NP_SKIPPED;
+		const unsigned long long bacc = __ballot(acc), bm = __ballot(m);
+		__syncthreads();
+		if (lane == 0) { waveAcc[wave] = __popcll(bacc); waveM[wave] = __popcll(bm); }
+		__syncthreads();
+		int before = 0, total = 0;
+		for (int w = 0; w < 16; ++w) { if (w < wave) before += waveAcc[w]; total += waveAcc[w]; mtotal += waveM[w]; }
+		if (acc) {
+			const int k = base + before + __popcll(bacc & ((1ull << lane) - 1ull));
+			accIdx1[k] = i; accIdx2[k] = match12[i];
+			for (int q = 0; q < 3; ++q) accX[3 * (size_t)k + q] = x3D[3 * (size_t)i + q];
+		}
+		base += total;
+	}
+	if (tid == 0) { *accCount = base; if (nmatches) *nmatches = mtotal; }
+}
+
+}  // namespace mcs
+using namespace mcs;
+
+// ------------------------------------------------------------------------------------------------ C ABI
+static inline size_t np_al(size_t v) { return (v + 255) / 256 * 256; }
+
+static int np_ensure(mcs_ctx* c, size_t need) {
+	if (c->npBuf && c->npBufCap >= need) return MCS_OK;
+	if (c->npBuf) (void)hipFree(c->npBuf);   // waits for the device: no earlier call still reads it
+	c->npBuf = nullptr; c->npBufCap = 0;
+	const size_t want = need + need / 2 + 256;
+	HIPCHK(hipMalloc((void**)&c->npBuf, want));
+	c->npBufCap = want;
+	return MCS_OK;
+}
+
+static int np_check_geom(const mcs_kf_geom& g, bool withMp) {
+	if (g.n < 0 || g.nr_cams < 1 || g.nr_cams > 32) return fail(MCS_ERR_INVALID, "keyframe: n >= 0 and 1 <= nr_cams <= 32");
+	if (!g.MtMc || !g.MtMc_inv || !g.M_t || !g.cams) return fail(MCS_ERR_INVALID, "keyframe: null matrices / camera models");
+	if (g.n > 0 && (!g.rays || !g.keys || !g.cam)) return fail(MCS_ERR_INVALID, "keyframe: null rays / keypoints / keypoint_to_cam");
+	if (withMp) {
+		// ComputeSceneMedianDepth indexes vDepths[(0 - 1) / 2] of an empty vector when the keyframe holds no map point (src/cMultiKeyFrame.cpp:777)
+		if (g.n_mp < 1) return fail(MCS_ERR_INVALID, "neighbour without a map point: its median depth is undefined in the reference");
+		if (!g.mp_pos || !g.mp_cam) return fail(MCS_ERR_INVALID, "neighbour: null map point positions / cameras");
+	}
+	return MCS_OK;
+}
+
+static NpKf np_view(const mcs_kf_geom& g) {
+	NpKf k;
+	k.MtMc = g.MtMc; k.MtMcInv = g.MtMc_inv; k.Mt = g.M_t; k.cams = g.cams; k.rays = g.rays; k.keys = g.keys; k.cam = g.cam; k.n = g.n; k.nrCams = g.nr_cams;
+	return k;
+}
+
+// host-kind calls: the caller's arrays copied into one device block
+struct NpBump {
+	uint8_t* base = nullptr; size_t used = 0, cap = 0; hipStream_t s = nullptr; hipError_t err = hipSuccess;
+	void* put(const void* src, size_t bytes) {
+		void* p = base + used;
+		if (used + np_al(bytes) > cap) { err = hipErrorOutOfMemory; return base; }   // the block is sized from the same counts: never taken
+		used += np_al(bytes);
+		if (src && bytes && err == hipSuccess) err = hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, s);
+		return p;
+	}
+	~NpBump() { if (base) (void)hipFree(base); }
+};
+static size_t np_geom_bytes(const mcs_kf_geom& g, bool withMp) {
+	const size_t nc = (size_t)g.nr_cams, n = (size_t)g.n;
+	return 2 * np_al(nc * 128) + np_al(128) + np_al(nc * sizeof(mcs_ocam)) + np_al(n * 24) + np_al(n * sizeof(mcs_keypoint)) + np_al(n * 4) +
+	       (withMp ? np_al((size_t)g.n_mp * 24) + np_al((size_t)g.n_mp * 4) : 0);
+}
+static int np_check_host_geom(const mcs_kf_geom& g, bool withMp) {
+	for (int c = 0; c < g.nr_cams; ++c)
+		if (g.cams[c].invP_deg < 1 || g.cams[c].invP_deg > MCS_MAX_POLY) return fail(MCS_ERR_INVALID, "bad polynomial degree");
+	for (int i = 0; i < g.n; ++i)
+		if (g.cam[i] < 0 || g.cam[i] >= g.nr_cams) return fail(MCS_ERR_INVALID, "keypoint_to_cam outside the rig");
+	if (withMp)
+		for (int i = 0; i < g.n_mp; ++i)
+			if (g.mp_cam[i] < 0 || g.mp_cam[i] >= g.nr_cams) return fail(MCS_ERR_INVALID, "map point camera outside the rig");
+	return MCS_OK;
+}
+static mcs_kf_geom np_stage_geom(NpBump& b, const mcs_kf_geom& g, bool withMp) {
+	mcs_kf_geom d = g;
+	const size_t nc = (size_t)g.nr_cams, n = (size_t)g.n;
+	d.MtMc = (const double*)b.put(g.MtMc, nc * 128); d.MtMc_inv = (const double*)b.put(g.MtMc_inv, nc * 128); d.M_t = (const double*)b.put(g.M_t, 128);
+	d.cams = (const mcs_ocam*)b.put(g.cams, nc * sizeof(mcs_ocam));
+	d.rays = (const double*)b.put(g.rays, n * 24); d.keys = (const mcs_keypoint*)b.put(g.keys, n * sizeof(mcs_keypoint)); d.cam = (const int32_t*)b.put(g.cam, n * 4);
+	if (withMp) { d.mp_pos = (const double*)b.put(g.mp_pos, (size_t)g.n_mp * 24); d.mp_cam = (const int32_t*)b.put(g.mp_cam, (size_t)g.n_mp * 4); }
+	else { d.mp_pos = nullptr; d.mp_cam = nullptr; d.n_mp = 0; }
+	return d;
+}
+
+static bool np_out_ok(const mcs_newpoints_out* o) { return o && o->verdict && o->x3D && o->acc_count && o->acc_idx1 && o->acc_idx2 && o->acc_x3D; }
+
+static void np_launch_pair(const NpTriArgs& t, int n1, int* nmatches, int* accCount, int* accIdx1, int* accIdx2, double* accX, hipStream_t s) {
+	if (n1 > 0) hipLaunchKernelGGL(k_np_triangulate, dim3((n1 + 127) / 128), dim3(128), 0, s, t);
+	hipLaunchKernelGGL(k_np_compact, dim3(1), dim3(1024), 0, s, t.match12, (const int*)t.verdict, (const double*)t.x3D, n1, nmatches, accCount, accIdx1, accIdx2, accX);
+}
+
+// every pointer on the device
+static int np_triangulate_device(mcs_ctx* c, int nsets, const mcs_kf_geom* kf1, const mcs_kf_geom* kf2, const int32_t* match12, const uint8_t* skipped,
+                                 double cosThresh, double maxDIST, const mcs_newpoints_out* out) {
+	hipStream_t s = c->stream;
+	if (c->side && c->greedyPending) { HIPCHK(hipStreamWaitEvent(s, c->evGreedy, 0)); c->greedyPending = false; }   // match12 may come from a search whose greedy pass runs beside
+	const int n1 = kf1[0].n;
+	for (int p = 0; p < nsets; ++p) {
+		NpTriArgs t{};
+		t.k1 = np_view(kf1[p]); t.k2 = np_view(kf2[p]);
+		t.match12 = match12 + (size_t)p * n1; t.skip = skipped ? skipped + p : nullptr;
+		t.cosThresh = cosThresh; t.maxDist = maxDIST;
+		t.verdict = out->verdict + (size_t)p * n1; t.x3D = out->x3D + 3 * (size_t)p * n1;
+		np_launch_pair(t, n1, nullptr, out->acc_count + p, out->acc_idx1 + (size_t)p * n1, out->acc_idx2 + (size_t)p * n1, out->acc_x3D + 3 * (size_t)p * n1, s);
+	}
+	HIPCHK(hipGetLastError());
+	return MCS_OK;
+}
+
+static int np_chain_device(mcs_ctx* c, int nsets, const mcs_kf_geom* kf1, const mcs_desc_set* d1, const mcs_kf_geom* kf2, const mcs_desc_set* d2, const double* E,
+                           size_t Epitch, int dim, int K, int checkOri, double cosThresh, double maxDIST, int32_t* match12, int32_t* nmatches, int32_t* fallbacks,
+                           double* baseline, double* median, uint8_t* skipped, uint8_t* valid1, const mcs_newpoints_out* out) {
+	hipStream_t s = c->stream;
+	const int n1 = kf1->n, nr = kf1->nr_cams;
+	int maxMp = 0;
+	for (int p = 0; p < nsets; ++p) maxMp = std::max(maxMp, kf2[p].n_mp);
+	const size_t eBlock = (size_t)nr * nr * 9;
+	const size_t oE = 0, oZ = oE + (E ? 0 : np_al(eBlock * 8 * nsets)), oR = oZ + np_al((size_t)maxMp * 8), oF = oR + 256, total = oF + np_al((size_t)nsets * 4);
+	if (int r = np_ensure(c, total)) return r;
+	double* Ework = E ? nullptr : (double*)(c->npBuf + oE);
+	double* z = (double*)(c->npBuf + oZ);
+	int* removed = (int*)(c->npBuf + oR);
+	if (!fallbacks) fallbacks = (int32_t*)(c->npBuf + oF);
+	if (c->side && c->greedyPending) { HIPCHK(hipStreamWaitEvent(s, c->evGreedy, 0)); c->greedyPending = false; }   // an earlier search's greedy pass may still read valid1
+	if (n1 > 0 && valid1 != d1->valid) {
+		if (d1->valid) HIPCHK(hipMemcpyAsync(valid1, d1->valid, (size_t)n1, hipMemcpyDeviceToDevice, s));
+		else HIPCHK(hipMemsetAsync(valid1, 1, (size_t)n1, s));
+	}
+	for (int p = 0; p < nsets; ++p) {   // setup, once: the z scratch is reused in stream order
+		NpSetupArgs a{};
+		a.k1 = np_view(*kf1); a.k2 = np_view(kf2[p]);
+		a.mpPos = kf2[p].mp_pos; a.mpCam = kf2[p].mp_cam; a.nmp = kf2[p].n_mp; a.z = z;
+		a.E = Ework ? Ework + eBlock * p : nullptr;
+		a.baseline = baseline + p; a.median = median + p; a.skip = skipped + p;
+		const int blocks = (a.nmp + 255) / 256;
+		hipLaunchKernelGGL(k_np_setup, dim3(blocks), dim3(256), 0, s, a);
+		hipLaunchKernelGGL(k_np_median, dim3(blocks), dim3(256), 0, s, (const double*)z, a.nmp, (const double*)a.baseline, a.median, a.skip);
+	}
+	HIPCHK(hipGetLastError());
+	const size_t angleOff = offsetof(mcs_keypoint, angle);
+	for (int p = 0; p < nsets; ++p) {
+		mcs_desc_set q = *d1;
+		q.valid = valid1;   // the working copy: features that got a map point from an earlier neighbour are no longer searched (src/cORBmatcher.cpp:1017-1020)
+		int32_t* m12 = match12 + (size_t)p * n1;
+		const double* Ep = E ? E + Epitch * p : Ework + eBlock * p;
+		// lists on the context's stream (behind the previous neighbour's k_np_triangulate), greedy pass on the side stream behind the lists
+		if (int r = mcs_search_triangulation(c, 1, &q, 0, &d2[p], 0, kf1->rays, kf2[p].rays, Ep, nr, dim, K, MCS_MEM_DEVICE, m12, nmatches + p, fallbacks + p)) return r;
+		if (c->side && c->greedyPending) { HIPCHK(hipStreamWaitEvent(s, c->evGreedy, 0)); c->greedyPending = false; }   // match12 is complete behind the greedy pass
+		if (checkOri && n1 > 0 && kf2[p].n > 0)
+			launch_rotation_consistency(3, (const float*)((const uint8_t*)kf1->keys + angleOff), (int)sizeof(mcs_keypoint),
+			                            (const float*)((const uint8_t*)kf2[p].keys + angleOff), (int)sizeof(mcs_keypoint), nullptr, m12, n1, 0, removed, s);
+		NpTriArgs t{};
+		t.k1 = np_view(*kf1); t.k2 = np_view(kf2[p]);
+		t.match12 = m12; t.matchClear = m12; t.skip = skipped + p; t.valid1 = valid1;
+		t.cosThresh = cosThresh; t.maxDist = maxDIST;
+		t.verdict = out->verdict + (size_t)p * n1; t.x3D = out->x3D + 3 * (size_t)p * n1;
+		np_launch_pair(t, n1, nmatches + p, out->acc_count + p, out->acc_idx1 + (size_t)p * n1, out->acc_idx2 + (size_t)p * n1, out->acc_x3D + 3 * (size_t)p * n1, s);
+		HIPCHK(hipGetLastError());
+	}
+	c->lastResultStream = s;   // every output of the chain is complete on the context's stream
+	return MCS_OK;
+}
+
+// device copies of the per-pair outputs of a host-kind call
+struct NpOutDev {
+	mcs_newpoints_out d{};
+	void carve(NpBump& b, size_t rows, int nsets) {
+		d.verdict = (int32_t*)b.put(nullptr, rows * 4); d.x3D = (double*)b.put(nullptr, rows * 24); d.acc_count = (int32_t*)b.put(nullptr, (size_t)nsets * 4);
+		d.acc_idx1 = (int32_t*)b.put(nullptr, rows * 4); d.acc_idx2 = (int32_t*)b.put(nullptr, rows * 4); d.acc_x3D = (double*)b.put(nullptr, rows * 24);
+	}
+	static size_t bytes(size_t rows, int nsets) { return 3 * np_al(rows * 4) + 2 * np_al(rows * 24) + np_al((size_t)nsets * 4); }
+	hipError_t download(const mcs_newpoints_out* o, size_t rows, int nsets, hipStream_t s) const {
+		hipError_t e = hipSuccess;
+		auto dl = [&](void* dst, const void* src, size_t bytes) { if (bytes && e == hipSuccess) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s); };
+		dl(o->verdict, d.verdict, rows * 4); dl(o->x3D, d.x3D, rows * 24); dl(o->acc_count, d.acc_count, (size_t)nsets * 4);
+		dl(o->acc_idx1, d.acc_idx1, rows * 4); dl(o->acc_idx2, d.acc_idx2, rows * 4); dl(o->acc_x3D, d.acc_x3D, rows * 24);
+		return e;
+	}
+};
+
+extern "C" {
+
+int mcs_triangulate_matches(mcs_ctx* c, int nsets, const mcs_kf_geom* kf1, const mcs_kf_geom* kf2, const int32_t* match12, const uint8_t* skipped,
+                            double cosThresh, double maxDIST, mcs_mem_kind kind, const mcs_newpoints_out* out) {
+	if (!c || !kf1 || !kf2 || !np_out_ok(out)) return fail(MCS_ERR_INVALID, "null argument");
+	if (nsets < 1) return fail(MCS_ERR_INVALID, "nsets must be >= 1");
+	const int n1 = kf1[0].n;
+	for (int p = 0; p < nsets; ++p) {
+		if (int r = np_check_geom(kf1[p], false)) return r;
+		if (int r = np_check_geom(kf2[p], false)) return r;
+		if (kf1[p].n != n1) return fail(MCS_ERR_INVALID, "every pair's first keyframe must have the same number of features");
+	}
+	if (n1 > 0 && !match12) return fail(MCS_ERR_INVALID, "null match12");
+	HIPCHK(hipSetDevice(c->device));
+	if (kind == MCS_MEM_DEVICE) return np_triangulate_device(c, nsets, kf1, kf2, match12, skipped, cosThresh, maxDIST, out);
+	const size_t rows = (size_t)nsets * n1;
+	size_t need = np_al(rows * 4) + np_al((size_t)nsets) + NpOutDev::bytes(rows, nsets);
+	for (int p = 0; p < nsets; ++p) {
+		if (int r = np_check_host_geom(kf1[p], false)) return r;
+		if (int r = np_check_host_geom(kf2[p], false)) return r;
+		for (int i = 0; i < n1; ++i)
+			if (match12[(size_t)p * n1 + i] >= kf2[p].n) return fail(MCS_ERR_INVALID, "match12 entry outside the second keyframe");
+		need += np_geom_bytes(kf1[p], false) + np_geom_bytes(kf2[p], false);
+	}
+	NpBump b;
+	b.s = c->stream;
+	HIPCHK(hipMalloc((void**)&b.base, need + 256));
+	b.cap = need + 256;
+	std::vector<mcs_kf_geom> g1(nsets), g2(nsets);
+	for (int p = 0; p < nsets; ++p) {
+		// the same keyframe behind several pairs (the current keyframe of a neighbour loop) is staged once
+		int same = -1;
+		for (int q = 0; q < p && same < 0; ++q) if (memcmp(&kf1[q], &kf1[p], sizeof(mcs_kf_geom)) == 0) same = q;
+		g1[p] = same >= 0 ? g1[same] : np_stage_geom(b, kf1[p], false);
+		g2[p] = np_stage_geom(b, kf2[p], false);
+	}
+	const int32_t* dm = (const int32_t*)b.put(match12, rows * 4);
+	const uint8_t* dskip = skipped ? (const uint8_t*)b.put(skipped, (size_t)nsets) : nullptr;
+	NpOutDev od;
+	od.carve(b, rows, nsets);
+	auto done = [&](int rc) { (void)hipStreamSynchronize(c->stream); return rc; };
+	if (b.err != hipSuccess) return done(fail(MCS_ERR_HIP, "H2D copy failed"));
+	if (int r = np_triangulate_device(c, nsets, g1.data(), g2.data(), dm, dskip, cosThresh, maxDIST, &od.d)) return done(r);
+	if (od.download(out, rows, nsets, c->stream) != hipSuccess) return done(fail(MCS_ERR_HIP, "D2H copy failed"));
+	HIPCHK(hipStreamSynchronize(c->stream));
+	return MCS_OK;
+}
+
+int mcs_create_new_map_points(mcs_ctx* c, int nsets, const mcs_kf_geom* kf1, const mcs_desc_set* kf1_desc, const mcs_kf_geom* kf2, const mcs_desc_set* kf2_desc,
+                              const double* E, size_t E_set_pitch, int dim, int K, int check_orientation, double cosThresh, double maxDIST, mcs_mem_kind kind,
+                              int32_t* match12, int32_t* nmatches, int32_t* fallbacks, double* baseline, double* median_depth, uint8_t* skipped, uint8_t* valid1,
+                              const mcs_newpoints_out* out) {
+	if (!c || !kf1 || !kf1_desc || !kf2 || !kf2_desc || !np_out_ok(out)) return fail(MCS_ERR_INVALID, "null argument");
+	if (nsets < 1) return fail(MCS_ERR_INVALID, "nsets must be >= 1");
+	if (!nmatches || !baseline || !median_depth || !skipped) return fail(MCS_ERR_INVALID, "null output");
+	if (int r = np_check_geom(*kf1, false)) return r;
+	const int n1 = kf1->n, nr = kf1->nr_cams;
+	if (n1 > 0 && (!match12 || !valid1)) return fail(MCS_ERR_INVALID, "null output");
+	if (kf1_desc->n != n1 || kf1_desc->block_rows != 0 || (n1 > 0 && !kf1_desc->group)) return fail(MCS_ERR_INVALID, "current keyframe: descriptor set and geometry disagree (contiguous rows, group = keypoint_to_cam)");
+	if (E && E_set_pitch != 0 && E_set_pitch < (size_t)nr * nr * 9) return fail(MCS_ERR_INVALID, "E_set_pitch smaller than one block of essential matrices");
+	for (int p = 0; p < nsets; ++p) {   // before anything runs
+		if (int r = np_check_geom(kf2[p], true)) return r;
+		if (kf2[p].nr_cams != nr) return fail(MCS_ERR_INVALID, "neighbour with another number of cameras");
+		if (kf2_desc[p].n != kf2[p].n || kf2_desc[p].block_rows != 0 || (kf2[p].n > 0 && !kf2_desc[p].group)) return fail(MCS_ERR_INVALID, "neighbour: descriptor set and geometry disagree (contiguous rows, group = keypoint_to_cam)");
+		if (kf2_desc[p].stride != kf2_desc[0].stride || (kf2_desc[p].mask == nullptr) != (kf1_desc->mask == nullptr)) return fail(MCS_ERR_INVALID, "neighbour: descriptor stride / masks differ");
+	}
+	if (c->asyncSearch) return fail(MCS_ERR_UNSUPPORTED, "the neighbour chain runs in order: switch deferred searches off (mcs_ctx_set_async_search)");
+	HIPCHK(hipSetDevice(c->device));
+	if (kind == MCS_MEM_DEVICE)
+		return np_chain_device(c, nsets, kf1, kf1_desc, kf2, kf2_desc, E, E_set_pitch, dim, K, check_orientation, cosThresh, maxDIST, match12, nmatches, fallbacks,
+		                       baseline, median_depth, skipped, valid1, out);
+	const size_t rows = (size_t)nsets * n1, eDoubles = E ? E_set_pitch * (size_t)(nsets - 1) + (size_t)nr * nr * 9 : 0;
+	if (int r = np_check_host_geom(*kf1, false)) return r;
+	auto set_bytes = [](const mcs_desc_set& d) { const size_t n = (size_t)d.n; return np_al(n * d.stride) * (d.mask ? 2 : 1) + np_al(n) + np_al(n * 4); };
+	size_t need = np_geom_bytes(*kf1, false) + set_bytes(*kf1_desc) + np_al(eDoubles * 8) + NpOutDev::bytes(rows, nsets) + np_al(rows * 4) + 2 * np_al((size_t)nsets * 4) +
+	              2 * np_al((size_t)nsets * 8) + np_al((size_t)nsets) + np_al((size_t)n1);
+	for (int p = 0; p < nsets; ++p) {
+		if (int r = np_check_host_geom(kf2[p], true)) return r;
+		need += np_geom_bytes(kf2[p], true) + set_bytes(kf2_desc[p]);
+	}
+	NpBump b;
+	b.s = c->stream;
+	HIPCHK(hipMalloc((void**)&b.base, need + 256));
+	b.cap = need + 256;
+	auto stage_set = [&](const mcs_desc_set& d, const int32_t* group) {
+		mcs_desc_set o = d;
+		const size_t n = (size_t)d.n;
+		o.desc = (const uint8_t*)b.put(d.desc, n * d.stride);
+		o.mask = d.mask ? (const uint8_t*)b.put(d.mask, n * d.stride) : nullptr;
+		o.valid = d.valid ? (const uint8_t*)b.put(d.valid, n) : nullptr;
+		o.group = group;
+		return o;
+	};
+	const mcs_kf_geom g1 = np_stage_geom(b, *kf1, false);
+	const mcs_desc_set s1 = stage_set(*kf1_desc, kf1_desc->group == kf1->cam ? g1.cam : (const int32_t*)b.put(kf1_desc->group, (size_t)n1 * 4));
+	std::vector<mcs_kf_geom> g2(nsets);
+	std::vector<mcs_desc_set> s2(nsets);
+	for (int p = 0; p < nsets; ++p) {
+		g2[p] = np_stage_geom(b, kf2[p], true);
+		s2[p] = stage_set(kf2_desc[p], kf2_desc[p].group == kf2[p].cam ? g2[p].cam : (const int32_t*)b.put(kf2_desc[p].group, (size_t)kf2[p].n * 4));
+	}
+	const double* dE = E ? (const double*)b.put(E, eDoubles * 8) : nullptr;
+	NpOutDev od;
+	od.carve(b, rows, nsets);
+	int32_t* dM = (int32_t*)b.put(nullptr, rows * 4); int32_t* dN = (int32_t*)b.put(nullptr, (size_t)nsets * 4); int32_t* dF = (int32_t*)b.put(nullptr, (size_t)nsets * 4);
+	double* dB = (double*)b.put(nullptr, (size_t)nsets * 8); double* dMed = (double*)b.put(nullptr, (size_t)nsets * 8);
+	uint8_t* dS = (uint8_t*)b.put(nullptr, (size_t)nsets); uint8_t* dV = (uint8_t*)b.put(nullptr, (size_t)n1);
+	hipStream_t s = c->stream;
+	auto done = [&](int rc) { (void)mcs_ctx_synchronize(c); return rc; };
+	if (b.err != hipSuccess) return done(fail(MCS_ERR_HIP, "H2D copy failed"));
+	if (int r = np_chain_device(c, nsets, &g1, &s1, g2.data(), s2.data(), dE, E_set_pitch, dim, K, check_orientation, cosThresh, maxDIST, dM, dN, dF, dB, dMed, dS, dV, &od.d))
+		return done(r);
+	hipError_t e = od.download(out, rows, nsets, s);
+	auto dl = [&](void* dst, const void* src, size_t bytes) { if (dst && bytes && e == hipSuccess) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s); };
+	dl(match12, dM, rows * 4); dl(nmatches, dN, (size_t)nsets * 4); dl(fallbacks, dF, (size_t)nsets * 4); dl(baseline, dB, (size_t)nsets * 8);
+	dl(median_depth, dMed, (size_t)nsets * 8); dl(skipped, dS, (size_t)nsets); dl(valid1, dV, (size_t)n1);
+	if (e != hipSuccess) return done(fail(MCS_ERR_HIP, "D2H copy failed"));
+	return done(MCS_OK);
+}
+
+}  // extern "C"

@@ -8,6 +8,7 @@
   DescriptorDistance64[_Masked]        src/cORBmatcher.cpp:2438-2474
   cMultiKeyFrameDatabase               src/cMultiKeyFrameDatabase.cpp:43-329 (inverted file, relocalisation / loop candidates)
   cSim3Solver (+ cSim3SolverBatch)     src/cSim3Solver.cpp (the RANSAC of cLoopClosing::ComputeSim3, one round over many candidates per call)
+  CreateNewMapPoints                   src/cLocalMapping.cpp:223-381 (the mapping thread's neighbour loop: search, triangulation and checks in one call)
 
 Everything numeric runs in libmcs_hip.so on the GPU; this file only shapes inputs/outputs (numpy stands in for cv::Mat).
 """
@@ -293,6 +294,18 @@ class cMultiKeyFrame:
 
     def GetKeyPointsRays(self):
         return self.mvKeysRays
+
+    def GetCameraCenter(self):                      # src/cMultiKeyFrame.cpp:156-162: Hom2T(M_t)
+        return self.camSystem.M_t[:3, 3].copy()
+
+    def ComputeSceneMedianDepth(self, q=2):         # src/cMultiKeyFrame.cpp:747-778 (host restatement; the device computes it inside CreateNewMapPoints)
+        z = []
+        for i, mp in enumerate(self.mvpMapPoints):
+            if mp is not None:
+                x4 = np.append(np.asarray(mp.GetWorldPos(), np.float64)[:3], 1.0).reshape(4, 1)
+                z.append(_matx_mul(self.camSystem.MtMc_inv[int(self.keypoint_to_cam[i])], x4)[2, 0])
+        z.sort()
+        return z[(len(z) - 1) // q]                 # the reference indexes an empty vector when the keyframe holds no map point; here: IndexError
 
 
 def _good(mp):
@@ -595,6 +608,77 @@ class cORBmatcher:
         i1 = [p[0] for p in pairs]
         i2 = [p[1] for p in pairs]
         return int(nm[0]), pKF1.mvKeys[i1], pKF1.mvKeysRays[i1], pKF2.mvKeys[i2], pKF2.mvKeysRays[i2], pairs
+
+
+COS_THRESH = float(np.cos(3.0 * np.pi / 180.0))   # src/cLocalMapping.cpp:39
+MAX_DIST = 25.0                                   # :43
+
+
+def _kf_geom(pKF, with_mp):
+    """mcs_kf_geom of a keyframe (host arrays) -> (struct, keepalive)"""
+    from ._capi import KfGeom
+    cs = pKF.camSystem
+    nr = cs.GetNrCams()
+    ocs = (type(cs.cams[0].ocam) * nr)(*[cm.ocam for cm in cs.cams])
+    keep = [np.ascontiguousarray(np.stack(cs.MtMc).reshape(nr, 16)), np.ascontiguousarray(np.stack(cs.MtMc_inv).reshape(nr, 16)),
+            np.ascontiguousarray(cs.M_t, np.float64), ocs, np.ascontiguousarray(pKF.mvKeysRays, np.float64).reshape(-1, 3),
+            np.ascontiguousarray(pKF.mvKeys), np.ascontiguousarray(pKF.keypoint_to_cam, np.int32)]
+    g = KfGeom()
+    g.MtMc, g.MtMc_inv, g.M_t, g.cams = keep[0].ctypes.data, keep[1].ctypes.data, keep[2].ctypes.data, C.addressof(ocs)
+    g.rays, g.keys, g.cam, g.n, g.nr_cams = keep[4].ctypes.data, keep[5].ctypes.data, keep[6].ctypes.data, len(keep[5]), nr
+    if with_mp:
+        idx = [i for i, mp in enumerate(pKF.mvpMapPoints) if mp is not None]
+        pos = np.ascontiguousarray(np.array([np.asarray(pKF.mvpMapPoints[i].GetWorldPos(), np.float64)[:3] for i in idx]).reshape(-1, 3))
+        cam = np.ascontiguousarray(keep[6][idx], np.int32)
+        keep += [pos, cam]
+        g.mp_pos, g.mp_cam, g.n_mp = pos.ctypes.data, cam.ctypes.data, len(idx)
+    return g, keep
+
+
+def CreateNewMapPoints(pKF, vpNeighKFs, checkOrientation=False, featDim=32, havingMasks=False, cosThresh=COS_THRESH, maxDIST=MAX_DIST, ctx=None, K=16,
+                       valid1=None):
+    """cLocalMapping::CreateNewMapPoints (src/cLocalMapping.cpp:223-381) in ONE device call (mcs_create_new_map_points): the current keyframe against its
+    neighbours in the given order (GetBestCovisibilityKeyFrames), every neighbour searched with the features that earlier neighbours gave a map point
+    taken out.  -> (per neighbour dict(idx1, idx2, x3D: the accepted matches in the reference's order; verdict, x3D_all, match12, nmatches, fallbacks,
+    baseline, medianDepth, skipped), final valid1).  Creating the cMapPoint objects (new cMapPoint, AddObservation, AddMapPoint, :362-377) stays with
+    the caller; valid1 (default: "has no map point yet") lets a second call continue a neighbour list."""
+    from ._capi import KfGeom, NewPointsOut
+    ns = len(vpNeighKFs)
+    if ns == 0:
+        return [], np.array([m is None for m in pKF.mvpMapPoints], bool)
+    ctx = ctx or default_context()
+    g1, keep = _kf_geom(pKF, False)
+    n1 = g1.n
+
+    def dset(kf, g, valid):
+        d = np.ascontiguousarray(kf._d, np.uint8)
+        m = np.ascontiguousarray(kf._m, np.uint8) if havingMasks else None
+        v = np.ascontiguousarray(valid, np.uint8)
+        keep.extend([d, m, v])
+        return DescSet(np_ptr(d), np_ptr(m), np_ptr(v), g.cam, len(d), featDim)
+
+    s1 = dset(pKF, g1, [m is None for m in pKF.mvpMapPoints] if valid1 is None else valid1)
+    g2, s2 = (KfGeom * ns)(), (DescSet * ns)()
+    for s, kf in enumerate(vpNeighKFs):
+        g, k = _kf_geom(kf, True)
+        keep.append(k)
+        g2[s], s2[s] = g, dset(kf, g, [m is None for m in kf.mvpMapPoints])
+    rows = max(ns * n1, 1)
+    verdict, x3D, cnt = np.zeros(rows, np.int32), np.zeros((rows, 3)), np.zeros(ns, np.int32)
+    a1, a2, ax = np.zeros(rows, np.int32), np.zeros(rows, np.int32), np.zeros((rows, 3))
+    out = NewPointsOut(np_ptr(verdict).value, np_ptr(x3D).value, np_ptr(cnt).value, np_ptr(a1).value, np_ptr(a2).value, np_ptr(ax).value)
+    m12, nm, fb = np.full(rows, -1, np.int32), np.zeros(ns, np.int32), np.zeros(ns, np.int32)
+    bl, md, sk, v1 = np.zeros(ns), np.zeros(ns), np.zeros(ns, np.uint8), np.zeros(max(n1, 1), np.uint8)
+    check(lib().mcs_create_new_map_points(ctx.h, ns, C.byref(g1), C.byref(s1), g2, s2, None, 0, featDim, max(K, 16), int(bool(checkOrientation)),
+                                          float(cosThresh), float(maxDIST), MEM_HOST, np_ptr(m12), np_ptr(nm), np_ptr(fb), np_ptr(bl), np_ptr(md), np_ptr(sk),
+                                          np_ptr(v1), C.byref(out)))
+    res = []
+    for s in range(ns):
+        k, lo = int(cnt[s]), s * n1
+        res.append(dict(idx1=a1[lo:lo + k].copy(), idx2=a2[lo:lo + k].copy(), x3D=ax[lo:lo + k].copy(), verdict=verdict[lo:lo + n1].copy(),
+                        x3D_all=x3D[lo:lo + n1].copy(), match12=m12[lo:lo + n1].copy(), nmatches=int(nm[s]), fallbacks=int(fb[s]), baseline=float(bl[s]),
+                        medianDepth=float(md[s]), skipped=bool(sk[s])))
+    return res, v1[:n1].astype(bool)
 
 
 def DescriptorDistance64(descr_i, descr_j, dim=32, ctx=None):
