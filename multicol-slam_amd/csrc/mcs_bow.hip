@@ -120,22 +120,12 @@ int mcs_bow_transform(mcs_vocabulary* v, const uint8_t* desc, int n, int stride,
 	mcs_ctx* c = v->ctx;
 	HIPCHK(hipSetDevice(c->device));
 	hipStream_t s = c->stream;
-	BowArgs a{v->nodeDesc, v->childOff, v->childIdx, v->L, desc, n, stride, levelsup, leaf_node, node_at_level};
-	uint8_t* buf = nullptr;
-	const bool host = kind == MCS_MEM_HOST;
-	if (host) {
-		HIPCHK(ctx_arena(c, (size_t)n * stride + (size_t)n * 8, &buf));
-		if (hipMemcpyAsync(buf, desc, (size_t)n * stride, hipMemcpyHostToDevice, s) != hipSuccess) return fail(MCS_ERR_HIP, "H2D copy failed");
-		a.desc = buf; a.leaf = (int*)(buf + (size_t)n * stride); a.nid = a.leaf + n;
-	}
+	BowArgs a{v->nodeDesc, v->childOff, v->childIdx, v->L, nullptr, n, stride, levelsup, nullptr, nullptr};
+	Staging st(c, kind == MCS_MEM_HOST);
+	st.in(&a.desc, desc, (size_t)n * stride); st.out(&a.leaf, leaf_node, (size_t)n * 4); st.out(&a.nid, node_at_level, (size_t)n * 4);
+	if (int r = st.commit()) return r;
 	hipLaunchKernelGGL(k_bow_transform, dim3((n + 255) / 256), dim3(256), 0, s, a);
-	hipError_t e = hipGetLastError();
-	if (host) {
-		if (e == hipSuccess) e = hipMemcpyAsync(leaf_node, a.leaf, (size_t)n * 4, hipMemcpyDeviceToHost, s);
-		if (e == hipSuccess) e = hipMemcpyAsync(node_at_level, a.nid, (size_t)n * 4, hipMemcpyDeviceToHost, s);
-		const hipError_t e2 = hipStreamSynchronize(s);
-		if (e == hipSuccess) e = e2;
-	}
+	const hipError_t e = hipGetLastError();
 	if (e != hipSuccess) return fail(MCS_ERR_HIP, std::string("bow transform: ") + hipGetErrorString(e));
-	return MCS_OK;
+	return st.finish(MCS_OK);
 }

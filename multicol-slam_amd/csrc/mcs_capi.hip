@@ -278,7 +278,7 @@ struct mcs_extractor {
 	std::vector<CamFast> camCache;
 	double* d_gTab = nullptr;
 	// host-kind input staging: the caller's image / mask block as it lies in host memory (same pitch and stride), grown on demand
-	uint8_t *d_inImg = nullptr, *d_inMask = nullptr; size_t inImgCap = 0, inMaskCap = 0;
+	DevBuf inImg, inMask;
 	// host-kind output staging
 	int* d_nkp = nullptr; mcs_keypoint* d_kps = nullptr; uint8_t *d_odesc = nullptr, *d_omask = nullptr; double* d_rays = nullptr;
 	ExtractBuffers last{};
@@ -313,7 +313,6 @@ int mcs_ctx_create(int device, void* hip_stream, mcs_ctx** out) {
 	c->device = device;
 	if (hip_stream) c->stream = (hipStream_t)hip_stream;
 	else { HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)); c->ownStream = true; }
-	HIPCHK(hipMalloc(&c->dscalar, 64));
 	if (getenv("MCS_NO_OVERLAP") == nullptr) {
 		// (stream priorities — resize chain urgent, deferred matcher least urgent or most urgent, and every other combination — change nothing measurable)
 		HIPCHK(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
@@ -356,8 +355,7 @@ int mcs_ctx_create(int device, void* hip_stream, mcs_ctx** out) {
 // make the context's main stream wait for everything queued on the side stream (outputs of the searches are written there)
 int mcs_ctx_join(mcs_ctx* c) {
 	if (!c) return fail(MCS_ERR_INVALID, "null ctx");
-	if (c->side && c->greedyPending) { HIPCHK(hipStreamWaitEvent(c->stream, c->evGreedy, 0)); c->greedyPending = false; }
-	return MCS_OK;
+	return ctx_join_greedy(c, c->stream);
 }
 
 int mcs_ctx_set_async_search(mcs_ctx* c, int on) {
@@ -385,8 +383,6 @@ int mcs_ctx_destroy(mcs_ctx* c) {
 	(void)hipStreamSynchronize(c->stream);
 	while (!c->extractors.empty()) (void)mcs_extractor_destroy(c->extractors.back());   // an extractor must not outlive the stream it runs on
 	for (auto& kv : c->timers) { if (kv.second.a) { (void)hipEventDestroy(kv.second.a); (void)hipEventDestroy(kv.second.b); } }
-	(void)hipFree(c->partial); (void)hipFree(c->partialCount); (void)hipFree(c->stage); (void)hipFree(c->dscalar);
-	(void)hipFree(c->topKeys); (void)hipFree(c->topKeys2); (void)hipFree(c->topCnt); (void)hipFree(c->exA); (void)hipFree(c->exW); (void)hipFree(c->exRows); (void)hipFree(c->stageOut); (void)hipFree(c->arena); (void)hipFree(c->npBuf); if (c->pinned) (void)hipHostFree(c->pinned);
 	if (c->side) {
 		(void)hipStreamSynchronize(c->side);
 		(void)hipStreamSynchronize(c->side2);
@@ -400,7 +396,7 @@ int mcs_ctx_destroy(mcs_ctx* c) {
 	}
 	for (hipStream_t ps : c->probed) { (void)hipStreamSynchronize(ps); (void)hipStreamDestroy(ps); }
 	if (c->ownStream) (void)hipStreamDestroy(c->stream);
-	delete c;
+	delete c;   // frees the context's device buffers and the mirror (mcs_host.h)
 	return MCS_OK;
 }
 
@@ -697,7 +693,7 @@ int mcs_extractor_destroy(mcs_extractor* e) {
 	}
 	void* ptrs[] = {e->d_desc, e->d_cells, e->d_taps, e->d_maskMap, e->d_pyr, e->d_blur, e->d_slots, e->d_dense, e->d_knode,
 	                e->d_sel, e->d_cellCount, e->d_denseCount, e->d_selCount, e->d_status, e->d_cams, e->d_nkp, e->d_kps, e->d_odesc,
-	                e->d_omask, e->d_rays, e->d_inImg, e->d_inMask, e->d_fbCount, e->d_fbList, e->d_preList, e->d_fbStats, e->d_tieMin, e->d_aux, e->d_gTab, e->d_selAngle, e->d_tieList};
+	                e->d_omask, e->d_rays, e->d_fbCount, e->d_fbList, e->d_preList, e->d_fbStats, e->d_tieMin, e->d_aux, e->d_gTab, e->d_selAngle, e->d_tieList};
 	for (void* p : ptrs) (void)hipFree(p);
 	for (mcs_extractor::Graph& g : e->graphs) (void)hipGraphExecDestroy(g.exec);
 	(void)hipFree(e->d_resMask);
@@ -722,15 +718,6 @@ int mcs_extractor_levels(const mcs_extractor* e, int* nlevels, int* widths, int*
 		if (heights) heights[l] = e->hd.lv[l].h;
 		if (features_per_level) features_per_level[l] = e->hd.lv[l].nfeat;
 	}
-	return MCS_OK;
-}
-
-static int grow(uint8_t** p, size_t* cap, size_t need) {   // device buffer of at least `need` bytes (host-kind calls end with a stream sync, so it is idle here)
-	if (*cap >= need) return MCS_OK;
-	if (*p) (void)hipFree(*p);
-	*p = nullptr; *cap = 0;
-	HIPCHK(hipMalloc((void**)p, need + need / 4));
-	*cap = need + need / 4;
 	return MCS_OK;
 }
 
@@ -913,15 +900,15 @@ static int extract_impl(mcs_extractor* e, int nimg, const uint8_t* images, size_
 		// ONE linear copy per block, in the caller's own layout; the kernels take any pitch / stride for level 0.  (A pitched hipMemcpy2D from pageable
 		// host memory is carried out row by row by the runtime: 2 x 480 small transfers per image, ~9 ms per image.)
 		const size_t imgSpan = (size_t)(nimg - 1) * image_pitch + (size_t)(hd.height - 1) * image_stride + hd.width;
-		if (int r = grow(&e->d_inImg, &e->inImgCap, imgSpan)) return r;
-		HIPCHK(hipMemcpyAsync(e->d_inImg, images, imgSpan, hipMemcpyHostToDevice, s));
-		b.img0 = e->d_inImg; b.img0Pitch = image_pitch; b.img0Stride = image_stride;
+		HIPCHK(e->inImg.reserve(imgSpan));   // (host-kind calls end with a stream sync, so it is idle here)
+		HIPCHK(hipMemcpyAsync(e->inImg.p, images, imgSpan, hipMemcpyHostToDevice, s));
+		b.img0 = e->inImg.p; b.img0Pitch = image_pitch; b.img0Stride = image_stride;
 		if (resMask) { b.mask0 = masks; b.mask0Pitch = mask_pitch; b.mask0Stride = mask_stride; }
 		else if (masks) {
 			const size_t maskSpan = (size_t)(nimg - 1) * mask_pitch + (size_t)(hd.height - 1) * mask_stride + hd.width;
-			if (int r = grow(&e->d_inMask, &e->inMaskCap, maskSpan)) return r;
-			HIPCHK(hipMemcpyAsync(e->d_inMask, masks, maskSpan, hipMemcpyHostToDevice, s));
-			b.mask0 = e->d_inMask; b.mask0Pitch = mask_pitch; b.mask0Stride = mask_stride;
+			HIPCHK(e->inMask.reserve(maskSpan));
+			HIPCHK(hipMemcpyAsync(e->inMask.p, masks, maskSpan, hipMemcpyHostToDevice, s));
+			b.mask0 = e->inMask.p; b.mask0Pitch = mask_pitch; b.mask0Stride = mask_stride;
 		}
 		b.nkp = e->d_nkp; b.kps = e->d_kps; b.out_desc = e->d_odesc; b.out_mask = e->d_omask; b.rays = rays ? e->d_rays : nullptr;
 	} else {
@@ -934,13 +921,8 @@ static int extract_impl(mcs_extractor* e, int nimg, const uint8_t* images, size_
 		std::vector<int> which(nimg), uniq;   // uniq: the cache entries this batch uses, in order of first use (their tables are uploaded once each)
 		for (int i = 0; i < nimg; ++i) {
 			const mcs_ocam& m = cams[i];
-			if (m.p_deg < 1 || m.p_deg > MCS_MAX_POLY || m.invP_deg < 1 || m.invP_deg > MCS_MAX_POLY) return fail(MCS_ERR_INVALID, "bad polynomial degree");
 			OcamDev& o = hc[i];
-			memset(&o, 0, sizeof(o));
-			o.c = m.c; o.d = m.d; o.e = m.e; o.u0 = m.u0; o.v0 = m.v0; o.invAffine = m.c - m.d * m.e;
-			for (int k = 0; k < m.p_deg; ++k) o.p[k] = m.p[k];
-			for (int k = 0; k < m.invP_deg; ++k) o.invP[k] = m.invP[k];
-			o.p_deg = m.p_deg; o.invP_deg = m.invP_deg;
+			if (int r = ocam_to_dev(m, &o)) return r;
 			// the camera's G(s) table and its bounds: built once per distinct camera
 			int w = -1;
 			for (size_t k = 0; k < e->camCache.size() && w < 0; ++k) if (memcmp(&e->camCache[k].key, &o, sizeof(o)) == 0) w = (int)k;
@@ -1339,30 +1321,21 @@ int mcs_describe_fast_table_packed(const mcs_ocam* cam, void* packed, int* row_b
 
 int mcs_selftest_describe_fast(mcs_ctx* c, const mcs_ocam* cam, uint64_t seed, int n, double* max_abs_diff) {
 	if (!c || !cam || !max_abs_diff || n < 1) return fail(MCS_ERR_INVALID, "bad argument");
-	if (cam->p_deg < 1 || cam->p_deg > MCS_MAX_POLY || cam->invP_deg < 1 || cam->invP_deg > MCS_MAX_POLY) return fail(MCS_ERR_INVALID, "bad polynomial degree");
-	HIPCHK(hipSetDevice(c->device));
 	OcamDev o;
-	memset(&o, 0, sizeof(o));
-	o.c = cam->c; o.d = cam->d; o.e = cam->e; o.u0 = cam->u0; o.v0 = cam->v0; o.invAffine = cam->c - cam->d * cam->e;
-	for (int k = 0; k < cam->p_deg; ++k) o.p[k] = cam->p[k];
-	for (int k = 0; k < cam->invP_deg; ++k) o.invP[k] = cam->invP[k];
-	o.p_deg = cam->p_deg; o.invP_deg = cam->invP_deg; o.fastOk = 1;
+	if (int r = ocam_to_dev(*cam, &o)) return r;
+	o.fastOk = 1;
+	HIPCHK(hipSetDevice(c->device));
 	std::vector<double> tab(kGTabDoubles, 0.0);
 	if (!std::isfinite(build_g_table(*cam, tab.data()).tailU)) return fail(MCS_ERR_UNSUPPORTED, "the fast pass does not serve this camera");
-	uint8_t* buf = nullptr;
-	HIPCHK(hipStreamSynchronize(c->stream));
-	const size_t tabOff = (64 + sizeof(OcamDev) + 63) / 64 * 64;
 	std::vector<double> packed(kGDevDoubles);
 	pack_g_table(tab.data(), reinterpret_cast<uint8_t*>(packed.data()));
-	HIPCHK(ctx_arena(c, tabOff + kGDevDoubles * sizeof(double), &buf));
-	unsigned long long zero = 0, got = 0;
-	HIPCHK(hipMemcpy(buf, &zero, sizeof(zero), hipMemcpyHostToDevice));
-	HIPCHK(hipMemcpy(buf + 64, &o, sizeof(o), hipMemcpyHostToDevice));
-	HIPCHK(hipMemcpy(buf + tabOff, packed.data(), kGDevDoubles * sizeof(double), hipMemcpyHostToDevice));
-	launch_selftest_fast_model((const OcamDev*)(buf + 64), (const double*)(buf + tabOff), seed, n, cam->width, cam->height, (unsigned long long*)buf, c->stream);
+	unsigned long long got = 0; unsigned long long* dMax = nullptr; const OcamDev* dCam = nullptr; const double* dTab = nullptr;
+	Staging st(c, true);
+	st.inout(&dMax, &got, sizeof(got)); st.in(&dCam, &o, sizeof(o)); st.in(&dTab, packed.data(), kGDevDoubles * sizeof(double));
+	if (int r = st.commit()) return r;
+	launch_selftest_fast_model(dCam, dTab, seed, n, cam->width, cam->height, dMax, c->stream);
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipStreamSynchronize(c->stream));
-	HIPCHK(hipMemcpy(&got, buf, sizeof(got), hipMemcpyDeviceToHost));
+	if (int r = st.finish(MCS_OK)) return r;
 	memcpy(max_abs_diff, &got, sizeof(double));
 	return MCS_OK;
 }

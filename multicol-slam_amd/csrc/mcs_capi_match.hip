@@ -13,22 +13,12 @@ void launch_rig_rows_valid(const uint8_t* blocks, int nimg, int cap, int rowStri
 }
 using namespace mcs;
 
-static int ensure(void** p, size_t* cap, size_t need) {
-	if (*cap >= need && *p) return MCS_OK;
-	if (*p) (void)hipFree(*p);
-	*p = nullptr; *cap = 0;
-	size_t want = need + need / 2 + 256;
-	HIPCHK(hipMalloc(p, want));
-	*cap = want;
-	return MCS_OK;
-}
-
 struct DevSets {   // device views of a (query sets, train sets) pair
 	const uint8_t *qd, *qm, *qvalid; const int* qgroup;
 	const uint8_t *td, *tm, *tvalid; const int* tgroup;
+	size_t qInter, tInter;   // host kind, descriptor | mask interleaved in one row: the mask's offset in the staged row
+	void resolve() { if (qInter) qm = qd + qInter; if (tInter) tm = td + tInter; }   // after Staging::commit
 };
-
-static inline size_t al256(size_t v) { return (v + 255) / 256 * 256; }
 
 // How the nsets (query set, train set) pairs of one call map onto the caller's arrays: pair s reads query set (s % qmod) and train set (s / tdiv);
 // nq_sets / nt_sets = number of distinct sets behind each pointer (what a host-kind call has to stage).
@@ -69,51 +59,22 @@ static void launch_search_out(int* dm, const int* sm, size_t n, int* dn, const i
 	hipLaunchKernelGGL(mcs::k_search_out, dim3(blocks), dim3(256), 0, s, dm, sm, n, dn, sn, df, sf, nsets);
 }
 
-// host pointers -> staged device copies (on the context's stream); device pointers pass through
-static int stage_sets(mcs_ctx* c, const SetGrid& sg, const mcs_desc_set* q, size_t qpitch, const mcs_desc_set* t, size_t tpitch, mcs_mem_kind kind,
-                      DevSets* out, const double** rays1, const double** rays2, const double** E, size_t nE) {
-	if (kind == MCS_MEM_DEVICE) {
-		out->qd = q->desc; out->qm = q->mask; out->qvalid = q->valid; out->qgroup = q->group;
-		out->td = t->desc; out->tm = t->mask; out->tvalid = t->valid; out->tgroup = t->group;
-		return MCS_OK;
-	}
-	hipStream_t s = c->stream;
+// host kind: the sets' arrays (and the rays / essential matrices of the triangulation search) declared on the call's staging; device pointers pass through
+static int stage_sets(Staging& st, const SetGrid& sg, const mcs_desc_set* q, size_t qpitch, const mcs_desc_set* t, size_t tpitch, DevSets* out,
+                      const double** rays1, const double** rays2, const double** E, size_t nE) {
 	const size_t qRows = qpitch * (sg.nq_sets - 1) + set_span(q), tRows = tpitch * (sg.nt_sets - 1) + set_span(t);
-	size_t need = 0;
-	const size_t oQd = need; need += al256(qRows * q->stride);
 	// descriptor | mask interleaved in one row (the rig's exchange blocks): the mask rides along with the descriptor copy
-	const bool qInter = q->mask && q->mask > q->desc && q->mask - q->desc < q->stride, tInter = t->mask && t->mask > t->desc && t->mask - t->desc < t->stride;
-	const size_t oQm = need; need += (q->mask && !qInter) ? al256(qRows * q->stride) : 0;
-	const size_t oQv = need; need += q->valid ? al256(qRows) : 0;
-	const size_t oQg = need; need += q->group ? al256(qRows * 4) : 0;
-	const size_t oTd = need; need += al256(tRows * t->stride);
-	const size_t oTm = need; need += (t->mask && !tInter) ? al256(tRows * t->stride) : 0;
-	const size_t oTv = need; need += t->valid ? al256(tRows) : 0;
-	const size_t oTg = need; need += t->group ? al256(tRows * 4) : 0;
-	const size_t oR1 = need; need += (rays1 && *rays1) ? al256(qRows * 24) : 0;
-	const size_t oR2 = need; need += (rays2 && *rays2) ? al256(tRows * 24) : 0;
-	const size_t oE = need; need += (E && *E) ? al256(nE * 8) : 0;
-	HIPCHK(hipStreamSynchronize(s));   // staging buffer may still be in use by an earlier call
-	if (int r = ensure((void**)&c->stage, &c->stageCap, need)) return r;
-	uint8_t* st = c->stage;
-	PinnedUpload up;   // all inputs in one H2D copy (every host-kind search ends with a stream synchronisation)
-	HIPCHK(up.begin(c, st, need));
-	if (qRows) up.put(oQd, q->desc, qRows * q->stride);
-	if (q->mask && !qInter && qRows) up.put(oQm, q->mask, qRows * q->stride);
-	if (q->valid && qRows) up.put(oQv, q->valid, qRows);
-	if (q->group && qRows) up.put(oQg, q->group, qRows * 4);
-	if (tRows) up.put(oTd, t->desc, tRows * t->stride);
-	if (t->mask && !tInter && tRows) up.put(oTm, t->mask, tRows * t->stride);
-	if (t->valid && tRows) up.put(oTv, t->valid, tRows);
-	if (t->group && tRows) up.put(oTg, t->group, tRows * 4);
-	out->qd = st + oQd; out->qm = q->mask ? (qInter ? st + oQd + (q->mask - q->desc) : st + oQm) : nullptr; out->qvalid = q->valid ? st + oQv : nullptr;
-	out->qgroup = q->group ? (const int*)(st + oQg) : nullptr;
-	out->td = st + oTd; out->tm = t->mask ? (tInter ? st + oTd + (t->mask - t->desc) : st + oTm) : nullptr; out->tvalid = t->valid ? st + oTv : nullptr;
-	out->tgroup = t->group ? (const int*)(st + oTg) : nullptr;
-	if (rays1 && *rays1) { if (qRows) up.put(oR1, *rays1, qRows * 24); *rays1 = (const double*)(st + oR1); }
-	if (rays2 && *rays2) { if (tRows) up.put(oR2, *rays2, tRows * 24); *rays2 = (const double*)(st + oR2); }
-	if (E && *E) { up.put(oE, *E, nE * 8); *E = (const double*)(st + oE); }
-	HIPCHK(up.flush(s));
+	const bool qInter = st.host && q->mask && q->mask > q->desc && q->mask - q->desc < q->stride, tInter = st.host && t->mask && t->mask > t->desc && t->mask - t->desc < t->stride;
+	st.in(&out->qd, q->desc, qRows * q->stride);
+	if (qInter) out->qInter = q->mask - q->desc; else st.in(&out->qm, q->mask, qRows * q->stride);
+	st.in(&out->qvalid, q->valid, qRows); st.in(&out->qgroup, q->group, qRows * 4);
+	st.in(&out->td, t->desc, tRows * t->stride);
+	if (tInter) out->tInter = t->mask - t->desc; else st.in(&out->tm, t->mask, tRows * t->stride);
+	st.in(&out->tvalid, t->valid, tRows); st.in(&out->tgroup, t->group, tRows * 4);
+	if (rays1) st.in(rays1, *rays1, qRows * 24);
+	if (rays2) st.in(rays2, *rays2, tRows * 24);
+	if (E) st.in(E, *E, nE * 8);
+	if (st.host) HIPCHK(hipStreamSynchronize(st.c->stream));   // device-kind work enqueued earlier completes before the block may regrow (part of the measured latency path)
 	return MCS_OK;
 }
 
@@ -127,9 +88,10 @@ static int run_topk(mcs_ctx* c, const DevSets& d, const SetGrid& sg, const mcs_d
 	// caller enqueues next (started 40 us later it found the chip full of the next batch's FAST workgroups: 0.72 instead of 0.30 ms)
 	const bool deferred = ls != nullptr;
 	if (!deferred) ls = c->stream;
-	if (!deferred && c->side && c->greedyPending) { HIPCHK(hipStreamWaitEvent(c->stream, c->evGreedy, 0)); c->greedyPending = false; }
-	if (int r = ensure((void**)(slot ? &c->topKeys2 : &c->topKeys), slot ? &c->topKeys2Cap : &c->topKeysCap, std::max<size_t>((size_t)nsets * q->n, 1) * K * sizeof(uint32_t))) return r;
-	a.keys = slot ? c->topKeys2 : c->topKeys;
+	if (!deferred) if (int r = ctx_join_greedy(c, c->stream)) return r;   // the previous search's greedy pass still reads the list buffer
+	DevBuf& keys = slot ? c->topKeys2 : c->topKeys;
+	HIPCHK(keys.reserve(std::max<size_t>((size_t)nsets * q->n, 1) * K * sizeof(uint32_t)));
+	a.keys = keys.as<uint32_t>();
 	a.qd = d.qd; a.qm = d.qm; a.qvalid = d.qvalid; a.qgroup = d.qgroup; a.td = d.td; a.tm = d.tm; a.tvalid = d.tvalid; a.tgroup = d.tgroup;
 	a.nq = q->n; a.nt = t->n; a.qstride = q->stride; a.tstride = t->stride; a.qpitch = qpitch; a.tpitch = tpitch;
 	a.nsets = nsets; a.qmod = sg.qmod; a.tdiv = sg.tdiv; a.dim = dim; a.K = K; a.countThresh = count_thresh;
@@ -145,10 +107,10 @@ static int run_topk(mcs_ctx* c, const DevSets& d, const SetGrid& sg, const mcs_d
 	splits = std::max(1, std::min(splits, (t->n + 255) / 256));
 	a.splits = splits;
 	if (splits > 1) {
-		if (int r = ensure((void**)&c->partial, &c->partialCap, outRows * splits * K * sizeof(uint32_t))) return r;
-		if (int r = ensure((void**)&c->partialCount, &c->partialCountCap, outRows * splits * sizeof(int))) return r;
+		HIPCHK(c->partial.reserve(outRows * splits * K * sizeof(uint32_t)));
+		HIPCHK(c->partialCount.reserve(outRows * splits * sizeof(int)));
 	}
-	a.partial = c->partial; a.partialCount = c->partialCount;
+	a.partial = c->partial.as<uint32_t>(); a.partialCount = c->partialCount.as<int>();
 	a.outDist = outDist; a.outIdx = outIdx; a.outCount = outCount;
 	if (match_mfma_shape(a) && t->n > 0) {
 		// the matrix-core matcher reads train sets that one pass has compacted and expanded (256 bytes per masked 32-byte row); beyond kExpandCap the v_bcnt kernel serves
@@ -156,10 +118,8 @@ static int run_topk(mcs_ctx* c, const DevSets& d, const SetGrid& sg, const mcs_d
 		size_t bA = 0, bW = 0;
 		match_mfma_scratch(a, sg.nt_sets, &bA, &bW, &a.exStages);
 		if (bA <= kExpandCap) {
-			if (int r = ensure((void**)&c->exA, &c->exACap, bA)) return r;
-			if (int r = ensure((void**)&c->exW, &c->exWCap, bW)) return r;
-			if (int r = ensure((void**)&c->exRows, &c->exRowsCap, (size_t)sg.nt_sets * sizeof(int))) return r;
-			a.exA = (uint4*)c->exA; a.exW = (float*)c->exW; a.exRows = c->exRows; a.tsets = sg.nt_sets;
+			HIPCHK(c->exA.reserve(bA)); HIPCHK(c->exW.reserve(bW)); HIPCHK(c->exRows.reserve((size_t)sg.nt_sets * sizeof(int)));
+			a.exA = c->exA.as<uint4>(); a.exW = c->exW.as<float>(); a.exRows = c->exRows.as<int>(); a.tsets = sg.nt_sets;
 		}
 	}
 	c->tic("match");
@@ -191,18 +151,14 @@ int mcs_match_topk_batched(mcs_ctx* c, int nsets, const mcs_desc_set* q, size_t 
 	HIPCHK(hipSetDevice(c->device));
 	DevSets d{};
 	const SetGrid sg = grid_batched(nsets, qpitch, tpitch);
-	if (int r = stage_sets(c, sg, q, qpitch, t, tpitch, kind, &d, nullptr, nullptr, nullptr, 0)) return r;
+	Staging st(c, kind == MCS_MEM_HOST);
+	if (int r = stage_sets(st, sg, q, qpitch, t, tpitch, &d, nullptr, nullptr, nullptr, 0)) return r;
 	const size_t outRows = (size_t)nsets * q->n;
-	if (kind == MCS_MEM_DEVICE) return run_topk(c, d, sg, q, qpitch, t, tpitch, dim, K, count_thresh, 0x7FFFFFFF, out_dist, out_idx, out_count_le);
-	const size_t oD = 0, oI = al256(outRows * K * 4), oC = oI + al256(outRows * K * 4);
-	if (int r = ensure((void**)&c->stageOut, &c->stageOutCap, oC + al256(outRows * 4))) return r;
-	uint8_t* so = c->stageOut;
-	if (int r = run_topk(c, d, sg, q, qpitch, t, tpitch, dim, K, count_thresh, 0x7FFFFFFF, (int*)(so + oD), (int*)(so + oI), (int*)(so + oC))) return r;
-	HIPCHK(hipMemcpyAsync(out_dist, so + oD, outRows * K * 4, hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(hipMemcpyAsync(out_idx, so + oI, outRows * K * 4, hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(hipMemcpyAsync(out_count_le, so + oC, outRows * 4, hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(hipStreamSynchronize(c->stream));
-	return MCS_OK;
+	int *dDist = nullptr, *dIdx = nullptr, *dCount = nullptr;
+	st.out(&dDist, out_dist, outRows * K * 4); st.out(&dIdx, out_idx, outRows * K * 4); st.out(&dCount, out_count_le, outRows * 4);
+	if (int r = st.commit()) return r;
+	d.resolve();
+	return st.finish(run_topk(c, d, sg, q, qpitch, t, tpitch, dim, K, count_thresh, 0x7FFFFFFF, dDist, dIdx, dCount));
 }
 
 int mcs_match_topk(mcs_ctx* c, const mcs_desc_set* q, const mcs_desc_set* t, int dim, int K, int count_thresh, mcs_mem_kind kind,
@@ -227,21 +183,23 @@ static int search_common(mcs_ctx* c, int mode, const SetGrid& sg, const mcs_desc
 	const bool deferred = kind == MCS_MEM_DEVICE && c->overlap() && c->asyncSearch;
 	if (deferred) {
 		if (q->n == 0) { HIPCHK(hipEventRecord(c->evMatch, s)); HIPCHK(hipStreamWaitEvent(c->side2, c->evMatch, 0)); }   // otherwise in run_topk
-	} else if (c->side && c->greedyPending) {   // the previous search's greedy pass (side stream) still reads the shared list buffers
-		HIPCHK(hipStreamWaitEvent(s, c->evGreedy, 0));
-		c->greedyPending = false;
-	}
+	} else if (int r = ctx_join_greedy(c, s)) return r;   // the previous search's greedy pass (side stream) still reads the shared list buffers
 	const bool havingMasks = q->mask != nullptr;
 	// thresholds of cORBmatcher::cORBmatcher (src/cORBmatcher.cpp:46-65); only TH_LOW_ is used by these three searches
 	const int thLow = havingMasks ? (int)floor((double)dim) : 2 * dim;
 	DevSets d{};
-	if (int r = stage_sets(c, sg, q, qpitch, t, tpitch, kind, &d, mode == 2 ? &rays1 : nullptr, mode == 2 ? &rays2 : nullptr,
+	Staging st(c, kind == MCS_MEM_HOST);
+	if (int r = stage_sets(st, sg, q, qpitch, t, tpitch, &d, mode == 2 ? &rays1 : nullptr, mode == 2 ? &rays2 : nullptr,
 	                       mode == 2 ? &E : nullptr, Epitch * (size_t)(nsets - 1) + (size_t)nrCams * nrCams * 9)) return r;
-	const size_t rows = (size_t)nsets * q->n;
+	const size_t rows = (size_t)nsets * q->n, outN = (size_t)nsets * (mode == 1 ? t->n : q->n);
+	GreedyArgs g{};
+	st.out(&g.outMatch, out_match, outN * 4); st.out(&g.outCount, out_nmatches, (size_t)nsets * 4); st.out(&g.outFallbacks, out_fallbacks, (size_t)nsets * 4);
+	if (int r = st.commit()) return r;   // (a device-kind search declares nothing: no claim, no wait)
+	d.resolve();
 	// deferred: two list buffers in turn, the greedy pass on a stream of its own — it is a chain of dependent round trips with a few waves per CU, the matcher waits
 	// 45 % of its cycles: side by side (greedy pass of search n, lists of search n + 1) the greedy pass disappears from the matcher stream's critical path
 	const int slot = deferred ? (int)(c->searchSeq & 1) : 0;
-	if (int r = ensure((void**)&c->topCnt, &c->topCntCap, std::max<size_t>(rows, 1) * 4)) return r;
+	HIPCHK(c->topCnt.reserve(std::max<size_t>(rows, 1) * 4));
 	{
 		// Rows that can never influence a decision stay out of the lists: SearchByBoW needs best <= TH_LOW and, for the ratio
 		// test, seconds up to the largest d with nnratio*d <= TH_LOW (any farther second passes best < nnratio*second for every
@@ -249,20 +207,17 @@ static int search_common(mcs_ctx* c, int mode, const SetGrid& sg, const mcs_desc
 		int maxDist = thLow;
 		if (mode != 2) while (maxDist < 8 * dim && nnratio * static_cast<double>(maxDist + 1) <= static_cast<double>(thLow)) ++maxDist;
 		if (q->n > 0)
-			if (int r = run_topk(c, d, sg, q, qpitch, t, tpitch, dim, K, -1, maxDist, nullptr, nullptr, c->topCnt, deferred ? c->side2 : nullptr, slot)) return r;
+			if (int r = run_topk(c, d, sg, q, qpitch, t, tpitch, dim, K, -1, maxDist, nullptr, nullptr, c->topCnt.as<int>(), deferred ? c->side2 : nullptr, slot)) return r;
 	}
-	GreedyArgs g{};
 	g.qd = d.qd; g.qm = d.qm; g.qvalid = d.qvalid; g.qgroup = d.qgroup; g.td = d.td; g.tm = d.tm; g.tvalid = d.tvalid; g.tgroup = d.tgroup;
 	g.nq = q->n; g.nt = t->n; g.qstride = q->stride; g.tstride = t->stride; g.qpitch = qpitch; g.tpitch = tpitch;
-	g.nsets = nsets; g.qmod = sg.qmod; g.tdiv = sg.tdiv; g.dim = dim; g.K = K; g.keys = slot ? c->topKeys2 : c->topKeys;
+	g.nsets = nsets; g.qmod = sg.qmod; g.tdiv = sg.tdiv; g.dim = dim; g.K = K; g.keys = (slot ? c->topKeys2 : c->topKeys).as<uint32_t>();
 	g.qblk = q->block_rows; g.qbpitch = (size_t)q->block_pitch_rows; g.tblk = t->block_rows; g.tbpitch = (size_t)t->block_pitch_rows;
 	g.toff = sg.toff; g.tmod = sg.tmod;
 	g.thLow = thLow; g.thInclusive = mode == 1 ? 1 : 0; g.ratio = nnratio; g.mode = mode;
 	g.rays1 = rays1; g.rays2 = rays2; g.E = E; g.Epitch = Epitch; g.nrCams = nrCams;
 	{ static const int ms = getenv("MCS_JACOBI_MAX_SWEEPS") ? atoi(getenv("MCS_JACOBI_MAX_SWEEPS")) : 0; g.jacMaxSweeps = ms; }
-	const size_t outN = (size_t)nsets * (mode == 1 ? t->n : q->n);
 	if (kind == MCS_MEM_DEVICE) {
-		g.outMatch = out_match; g.outCount = out_nmatches; g.outFallbacks = out_fallbacks;
 		if (deferred) {
 			if (q->n > 0) HIPCHK(hipStreamWaitEvent(c->side3, c->evLists, 0));
 			else HIPCHK(hipStreamWaitEvent(c->side3, c->evMatch, 0));
@@ -287,28 +242,17 @@ static int search_common(mcs_ctx* c, int mode, const SetGrid& sg, const mcs_desc
 		HIPCHK(hipGetLastError());
 		return MCS_OK;
 	}
-	const size_t oM = 0, oN = al256(std::max<size_t>(outN, 1) * 4), oF = oN + al256((size_t)nsets * 4);
-	if (int r = ensure((void**)&c->stageOut, &c->stageOutCap, oF + al256((size_t)nsets * 4))) return r;
-	uint8_t* so = c->stageOut;
-	g.outMatch = (int*)(so + oM); g.outCount = (int*)(so + oN); g.outFallbacks = (int*)(so + oF);
 	c->tic("greedy"); launch_greedy(g, s); c->toc("greedy");
 	HIPCHK(hipGetLastError());
-	{
-		// page-locked outputs: one launch instead of three copies (mcs_host.h device_view)
-		static const bool outKernel = !(getenv("MCS_OUT_KERNEL") && atoi(getenv("MCS_OUT_KERNEL")) == 0);
-		int* dm = (int*)device_view(out_match); int* dn = (int*)device_view(out_nmatches); int* df = (int*)device_view(out_fallbacks);
-		if (outKernel && dm && dn && (df || !out_fallbacks)) {
-			launch_search_out(dm, (const int*)(so + oM), outN, dn, (const int*)(so + oN), df, (const int*)(so + oF), nsets, s);
-			HIPCHK(hipGetLastError());
-			HIPCHK(hipStreamSynchronize(s));
-			return MCS_OK;
-		}
+	// page-locked outputs: one launch instead of three copies (mcs_host.h device_view)
+	static const bool outKernel = !(getenv("MCS_OUT_KERNEL") && atoi(getenv("MCS_OUT_KERNEL")) == 0);
+	int* dm = (int*)device_view(out_match); int* dn = (int*)device_view(out_nmatches); int* df = (int*)device_view(out_fallbacks);
+	const bool viaKernel = outKernel && dm && dn && (df || !out_fallbacks);
+	if (viaKernel) {
+		launch_search_out(dm, g.outMatch, outN, dn, g.outCount, df, g.outFallbacks, nsets, s);
+		HIPCHK(hipGetLastError());
 	}
-	if (outN) HIPCHK(hipMemcpyAsync(out_match, so + oM, outN * 4, hipMemcpyDeviceToHost, s));
-	HIPCHK(hipMemcpyAsync(out_nmatches, so + oN, (size_t)nsets * 4, hipMemcpyDeviceToHost, s));
-	if (out_fallbacks) HIPCHK(hipMemcpyAsync(out_fallbacks, so + oF, (size_t)nsets * 4, hipMemcpyDeviceToHost, s));
-	HIPCHK(hipStreamSynchronize(s));
-	return MCS_OK;
+	return st.finish(MCS_OK, !viaKernel);
 }
 
 int mcs_search_kf_kf(mcs_ctx* c, int nsets, const mcs_desc_set* kf1, size_t pitch1, const mcs_desc_set* kf2, size_t pitch2, int dim, double nnratio,
@@ -357,79 +301,6 @@ int mcs_search_triangulation_sweep(mcs_ctx* c, int nsets, const mcs_desc_set* kf
 	return search_common(c, 2, grid_batched(nsets, pitch1, pitch2), kf1, pitch1, kf2, pitch2, dim, 0.0, K, kind, rays1, rays2, E, E_set_pitch, nrCams, match12, nmatches, fallbacks);
 }
 
-int mcs_search_by_projection(mcs_ctx* c, const mcs_projection_set* mp, const mcs_frame_view* f, double th, double nnratio, int dim, mcs_mem_kind kind,
-                             int32_t* match, int32_t* nmatches) {
-	if (!c || !mp || !f || !match || !nmatches) return fail(MCS_ERR_INVALID, "null argument");
-	if (dim != 16 && dim != 32 && dim != 64) return fail(MCS_ERR_INVALID, "dim must be 16, 32 or 64");
-	if (mp->n < 0 || f->n < 0 || f->n > 65536 || f->nr_cams < 1 || f->nlevels < 1) return fail(MCS_ERR_INVALID, "bad sizes (frame features must be <= 65536)");
-	if ((mp->mask == nullptr) != (f->mask == nullptr)) return fail(MCS_ERR_INVALID, "masks must be given for both sides or neither");
-	if (mp->stride < dim || f->stride < dim || (mp->stride & 3) || (f->stride & 3)) return fail(MCS_ERR_INVALID, "descriptor stride must be >= dim and a multiple of 4");
-	if (kind == MCS_MEM_HOST)   // level[] indexes scale_factors on the device
-		for (int i = 0; i < mp->n; ++i)
-			if (mp->level[i] < 0 || mp->level[i] >= f->nlevels) return fail(MCS_ERR_INVALID, "projection level outside [0, nlevels)");
-	HIPCHK(hipSetDevice(c->device));
-	hipStream_t s = c->stream;
-	if (c->side && c->greedyPending) { HIPCHK(hipStreamWaitEvent(s, c->evGreedy, 0)); c->greedyPending = false; }
-	const bool havingMasks = mp->mask != nullptr;
-	ProjArgs a{};
-	a.nproj = mp->n; a.pstride = mp->stride; a.nfeat = f->n; a.fstride = f->stride; a.nrCams = f->nr_cams;
-	a.th = th; a.ratio = nnratio; a.dim = dim; a.rule = 0; a.cap = kProjListK;
-	a.thHigh = havingMasks ? (int)floor(1.5 * dim) : 3 * dim;   // TH_HIGH_ (src/cORBmatcher.cpp:46-65)
-	const size_t np = std::max(mp->n, 1), nf = std::max(f->n, 1);
-	// scratch: lists + counts (+ staged inputs / outputs for host pointers), one allocation per call (this row is not a bench path)
-	size_t need = al256(np * kProjListK * 8) + al256(np * 4);
-	const size_t oLists = 0, oCounts = al256(np * kProjListK * 8);
-	size_t o = need;
-	auto reserve = [&](size_t bytes) { const size_t at = o; o += al256(bytes); return at; };
-	size_t oPx = 0, oPy = 0, oVc = 0, oLv = 0, oPc = 0, oPd = 0, oPm = 0, oKeys = 0, oFd = 0, oFm = 0, oFc = 0, oAs = 0, oW = 0, oH = 0, oSc = 0, oMatch = 0, oNm = 0;
-	const bool host = kind == MCS_MEM_HOST;
-	if (host) {
-		oPx = reserve(np * 8); oPy = reserve(np * 8); oVc = reserve(np * 8); oLv = reserve(np * 4); oPc = reserve(np * 4);
-		oPd = reserve(np * mp->stride); oPm = reserve(np * mp->stride); oKeys = reserve(nf * sizeof(mcs_keypoint));
-		oFd = reserve(nf * f->stride); oFm = reserve(nf * f->stride); oFc = reserve(nf * 4); oAs = reserve(nf);
-		oW = reserve((size_t)f->nr_cams * 4); oH = reserve((size_t)f->nr_cams * 4); oSc = reserve((size_t)f->nlevels * 8);
-		oMatch = reserve(np * 4); oNm = reserve(4);
-	}
-	uint8_t* buf = nullptr;
-	HIPCHK(ctx_arena(c, o, &buf));   // persistent per context (a hipMalloc / hipFree pair per call cost more than the kernels)
-	auto done = [&](int rc) { (void)hipStreamSynchronize(s); return rc; };
-	a.lists = (unsigned long long*)(buf + oLists); a.counts = (int*)(buf + oCounts);
-	if (host) {
-		PinnedUpload up;   // one H2D copy for all inputs
-		HIPCHK(up.begin(c, buf, o));
-#define UP(off, src, bytes) up.put((off), (src), (bytes))
-		UP(oPx, mp->proj_x, (size_t)mp->n * 8); UP(oPy, mp->proj_y, (size_t)mp->n * 8); UP(oVc, mp->view_cos, (size_t)mp->n * 8);
-		UP(oLv, mp->level, (size_t)mp->n * 4); UP(oPc, mp->cam, (size_t)mp->n * 4); UP(oPd, mp->desc, (size_t)mp->n * mp->stride);
-		if (havingMasks) { UP(oPm, mp->mask, (size_t)mp->n * mp->stride); UP(oFm, f->mask, (size_t)f->n * f->stride); }
-		UP(oKeys, f->keys, (size_t)f->n * sizeof(mcs_keypoint)); UP(oFd, f->desc, (size_t)f->n * f->stride); UP(oFc, f->cam, (size_t)f->n * 4);
-		UP(oAs, f->assigned, (size_t)f->n); UP(oW, f->width, (size_t)f->nr_cams * 4); UP(oH, f->height, (size_t)f->nr_cams * 4);
-		UP(oSc, f->scale_factors, (size_t)f->nlevels * 8);
-#undef UP
-		if (up.flush(s) != hipSuccess) return done(fail(MCS_ERR_HIP, "H2D copy failed"));
-		a.px = (const double*)(buf + oPx); a.py = (const double*)(buf + oPy); a.vcos = (const double*)(buf + oVc); a.level = (const int*)(buf + oLv);
-		a.pcam = (const int*)(buf + oPc); a.pdesc = buf + oPd; a.pmask = havingMasks ? buf + oPm : nullptr;
-		a.keys = (const mcs_keypoint*)(buf + oKeys); a.fdesc = buf + oFd; a.fmask = havingMasks ? buf + oFm : nullptr; a.fcam = (const int*)(buf + oFc);
-		a.assigned = buf + oAs; a.width = (const int*)(buf + oW); a.height = (const int*)(buf + oH); a.scales = (const double*)(buf + oSc);
-		a.match = (int*)(buf + oMatch); a.nmatches = (int*)(buf + oNm);
-	} else {
-		a.px = mp->proj_x; a.py = mp->proj_y; a.vcos = mp->view_cos; a.level = mp->level; a.pcam = mp->cam; a.pdesc = mp->desc; a.pmask = mp->mask;
-		a.keys = f->keys; a.fdesc = f->desc; a.fmask = f->mask; a.fcam = f->cam; a.assigned = f->assigned; a.width = f->width; a.height = f->height;
-		a.scales = f->scale_factors; a.match = match; a.nmatches = nmatches;
-	}
-	if (mp->n > 0) launch_projection(a, s);
-	else if (!host) { HIPCHK(hipMemsetAsync(nmatches, 0, 4, s)); }
-	if (hipGetLastError() != hipSuccess) return done(fail(MCS_ERR_HIP, "projection kernels failed to launch"));
-	if (host) {
-		*nmatches = 0;
-		if (mp->n > 0) {
-			if (hipMemcpyAsync(match, buf + oMatch, (size_t)mp->n * 4, hipMemcpyDeviceToHost, s) != hipSuccess) return done(fail(MCS_ERR_HIP, "D2H"));
-			if (hipMemcpyAsync(nmatches, buf + oNm, 4, hipMemcpyDeviceToHost, s) != hipSuccess) return done(fail(MCS_ERR_HIP, "D2H"));
-			if (hipMemcpyAsync(f->assigned, buf + oAs, (size_t)f->n, hipMemcpyDeviceToHost, s) != hipSuccess) return done(fail(MCS_ERR_HIP, "D2H"));
-		}
-	}
-	return done(MCS_OK);   // synchronises: the scratch is freed here (DEVICE kind therefore blocks too; this row is not on the bench path)
-}
-
 int mcs_rows_valid(mcs_ctx* c, const int32_t* nkp_dev, int nimg, int cap, uint8_t* valid_dev) {
 	if (!c || !nkp_dev || !valid_dev || nimg < 1 || cap < 1) return fail(MCS_ERR_INVALID, "bad argument");
 	HIPCHK(hipSetDevice(c->device));
@@ -457,16 +328,13 @@ int mcs_rig_rows_valid(mcs_ctx* c, const uint8_t* blocks_dev, int nimg, int cap,
 static int single_distance(mcs_ctx* c, const uint8_t* a, const uint8_t* b, const uint8_t* ma, const uint8_t* mb, int dim, int* out) {
 	if (!c || !a || !b || !out || (dim != 16 && dim != 32 && dim != 64)) return fail(MCS_ERR_INVALID, "bad argument");
 	HIPCHK(hipSetDevice(c->device));
-	uint8_t* buf = nullptr;
-	HIPCHK(hipStreamSynchronize(c->stream));
-	HIPCHK(ctx_arena(c, 4 * 64, &buf));   // the context's persistent scratch
-	HIPCHK(hipMemcpy(buf, a, dim, hipMemcpyHostToDevice));
-	HIPCHK(hipMemcpy(buf + 64, b, dim, hipMemcpyHostToDevice));
-	if (ma) { HIPCHK(hipMemcpy(buf + 128, ma, dim, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(buf + 192, mb, dim, hipMemcpyHostToDevice)); }
-	launch_single_distance(buf, buf + 64, ma ? buf + 128 : nullptr, ma ? buf + 192 : nullptr, dim, c->dscalar, c->stream);
-	HIPCHK(hipStreamSynchronize(c->stream));
-	HIPCHK(hipMemcpy(out, c->dscalar, sizeof(int), hipMemcpyDeviceToHost));
-	return MCS_OK;
+	Staging st(c, true);
+	const uint8_t *da = nullptr, *db = nullptr, *dma = nullptr, *dmb = nullptr; int* dOut = nullptr;
+	st.in(&da, a, dim); st.in(&db, b, dim); st.in(&dma, ma, dim); st.in(&dmb, ma ? mb : nullptr, dim); st.out(&dOut, out, sizeof(int));
+	if (int r = st.commit()) return r;
+	launch_single_distance(da, db, dma, dmb, dim, dOut, c->stream);
+	HIPCHK(hipGetLastError());
+	return st.finish(MCS_OK);
 }
 
 int mcs_descriptor_distance(mcs_ctx* c, const uint8_t* a, const uint8_t* b, int dim, int* out) { return single_distance(c, a, b, nullptr, nullptr, dim, out); }

@@ -1,6 +1,8 @@
 // mcs_host.h — host-side internals shared by the C-ABI translation units (context, error plumbing).
 #pragma once
 #include "mcs_common.h"
+#include "mcs_carve.h"
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <map>
@@ -33,6 +35,26 @@ inline void* device_view(const void* host) {
 	return a.devicePointer;
 }
 
+// Grow-only device buffer: at least `bytes` long after reserve(), contents lost when it grows.  Growing goes through hipFree, which waits for the device, so
+// nothing still reads the old allocation.  Freed with its owner (context, extractor, keyframe database), whose destroy call has set the device (mcs_ctx_destroy does before `delete c`: keep it that way).
+struct DevBuf {
+	uint8_t* p = nullptr; size_t cap = 0;
+	DevBuf() = default;
+	DevBuf(const DevBuf&) = delete;
+	DevBuf& operator=(const DevBuf&) = delete;
+	~DevBuf() { if (p) (void)hipFree(p); }
+	hipError_t reserve(size_t bytes) {
+		if (p && cap >= bytes) return hipSuccess;
+		if (p) (void)hipFree(p);
+		p = nullptr; cap = 0;
+		const size_t want = bytes + bytes / 2 + 256;
+		const hipError_t e = hipMalloc((void**)&p, want);
+		if (e == hipSuccess) cap = want;
+		return e;
+	}
+	template <class T> T* as() const { return (T*)p; }
+};
+
 struct mcs_ctx {
 	int device = 0;
 	std::vector<mcs_extractor*> extractors;   // live extractors built on this context: mcs_ctx_destroy releases them (their buffers and stream are the context's)
@@ -41,20 +63,22 @@ struct mcs_ctx {
 	bool timing = false;
 	std::map<std::string, Timer> timers;
 	// matcher scratch
-	uint32_t* partial = nullptr; size_t partialCap = 0;
-	int* partialCount = nullptr; size_t partialCountCap = 0;
-	uint8_t* stage = nullptr; size_t stageCap = 0;   // host-kind staging for the matcher
-	int* dscalar = nullptr;
-	uint32_t* topKeys = nullptr; size_t topKeysCap = 0;   // packed [set][K][nq] top-K lists feeding the greedy kernels
-	uint32_t* topKeys2 = nullptr; size_t topKeys2Cap = 0; // second list buffer of the deferred searches: the greedy pass of search n reads one while the matcher of search n + 1 fills the other
-	int* topCnt = nullptr; size_t topCntCap = 0;
-	uint8_t* exA = nullptr; size_t exACap = 0;            // train sets expanded to matrix-core operands (mcs_match_mfma.hip), per call
-	uint8_t* exW = nullptr; size_t exWCap = 0;
-	int* exRows = nullptr; size_t exRowsCap = 0;
-	uint8_t* stageOut = nullptr; size_t stageOutCap = 0;
-	uint8_t* pinned = nullptr; size_t pinnedCap = 0;      // page-locked host mirror of the arena's staged inputs (PinnedUpload)
-	uint8_t* arena = nullptr; size_t arenaCap = 0;        // scratch + host-kind staging of the window / projection / map-point entry points (mcs_capi_window.hip)
-	uint8_t* npBuf = nullptr; size_t npBufCap = 0;        // mcs_create_new_map_points: essential matrices, depths, the rotation filter's counter (mcs_newpoints.hip)
+	DevBuf partial, partialCount;   // uint32_t / int
+	DevBuf topKeys;    // uint32_t: packed [set][K][nq] top-K lists feeding the greedy kernels
+	DevBuf topKeys2;   // second list buffer of the deferred searches: the greedy pass of search n reads one while the matcher of search n + 1 fills the other
+	DevBuf topCnt;     // int
+	DevBuf exA, exW, exRows;   // train sets expanded to matrix-core operands (mcs_match_mfma.hip), per call
+	// The ONE block of a call's staged arrays and scratch, and its page-locked mirror (struct Staging below).  No call reads a piece while something else
+	// writes it: the pieces of one call are disjoint by construction; a call claims the block (`staging`) before it lays it out and a second claim is an
+	// error, so a nested device-kind call (the searches inside mcs_create_new_map_points) cannot carve it again; and the claim is only released behind a
+	// synchronisation of the context's stream, so no kernel or copy of an earlier call is still running when the next call overwrites or regrows it.
+	DevBuf block;
+	uint8_t* mirror = nullptr; size_t mirrorCap = 0;
+	bool staging = false;
+	// mcs_create_new_map_points: essential matrices, depths, the rotation filter's counter (mcs_newpoints.hip).  A buffer of its own: a device-kind chain
+	// returns without a host wait while its kernels (and the greedy pass on the side stream) still use it, so it cannot live in a block that the next
+	// call lays out afresh.
+	DevBuf npBuf;
 	// Second HIP stream for the latency-bound / independent kernels (blur next to FAST+oct-tree, the greedy resolution next to the
 	// following batch's extraction): they leave most CUs idle, so overlapping them with the VALU-bound kernels is free throughput.
 	hipStream_t side = nullptr;    // extraction fork: resize chain + blur beside FAST + oct-tree
@@ -84,42 +108,97 @@ struct mcs_ctx {
 		(void)hipEventRecord(t.b, stream);
 		t.used = true;
 	}
+	~mcs_ctx() { if (mirror) (void)hipHostFree(mirror); }
 };
 
-// The context's persistent scratch buffer, at least `bytes` long.  Every call on a context runs on the context's stream, so a later call's copies and
-// kernels are ordered behind the earlier call's use of it; growing goes through hipFree, which waits for the device.
-inline hipError_t ctx_arena(mcs_ctx* c, size_t bytes, uint8_t** out) {
-	if (c->arenaCap < bytes) {
-		if (c->arena) (void)hipFree(c->arena);
-		c->arena = nullptr; c->arenaCap = 0;
-		const hipError_t e = hipMalloc((void**)&c->arena, bytes + bytes / 2);
-		if (e != hipSuccess) return e;
-		c->arenaCap = bytes + bytes / 2;
-	}
-	*out = c->arena;
-	return hipSuccess;
+// make stream `s` wait for the greedy pass that the latest search left on the side stream (its outputs and the buffers it reads are complete behind it)
+inline int ctx_join_greedy(mcs_ctx* c, hipStream_t s) {
+	if (c->side && c->greedyPending) { HIPCHK(hipStreamWaitEvent(s, c->evGreedy, 0)); c->greedyPending = false; }
+	return MCS_OK;
 }
 
-// Host-kind inputs of one call, gathered in a page-locked mirror of the arena and sent with ONE H2D copy: a dozen small hipMemcpyAsync calls from
-// pageable memory cost ~20 us of runtime overhead each, more than the kernels of a single multi-frame.  Only for calls that end with a stream
-// synchronisation (the mirror is reused by the next call).
-struct PinnedUpload {
-	uint8_t* dev = nullptr; uint8_t* pin = nullptr; size_t lo = ~size_t(0), hi = 0;
-	hipError_t begin(mcs_ctx* c, uint8_t* devBase, size_t total) {
-		if (c->pinnedCap < total) {
-			if (c->pinned) (void)hipHostFree(c->pinned);
-			c->pinned = nullptr; c->pinnedCap = 0;
-			const hipError_t e = hipHostMalloc((void**)&c->pinned, total + total / 2, hipHostMallocDefault);
-			if (e != hipSuccess) return e;
-			c->pinnedCap = total + total / 2;
+// mcs_ocam -> the kernels' camera model (fastOk / tabIdx stay 0: the extractor sets them)
+inline int ocam_to_dev(const mcs_ocam& m, mcs::OcamDev* o) {
+	if (m.p_deg < 1 || m.p_deg > MCS_MAX_POLY || m.invP_deg < 1 || m.invP_deg > MCS_MAX_POLY) return fail(MCS_ERR_INVALID, "bad polynomial degree");
+	memset(o, 0, sizeof(*o));
+	o->c = m.c; o->d = m.d; o->e = m.e; o->u0 = m.u0; o->v0 = m.v0; o->invAffine = m.c - m.d * m.e;
+	for (int k = 0; k < m.p_deg; ++k) o->p[k] = m.p[k];
+	for (int k = 0; k < m.invP_deg; ++k) o->invP[k] = m.invP[k];
+	o->p_deg = m.p_deg; o->invP_deg = m.invP_deg;
+	return MCS_OK;
+}
+
+// The arrays and the scratch of ONE call, laid out in the context's block.  A piece is declared once (size, pointer to bind, optional host source and
+// destination); commit() claims the block, places the pieces (those with a source first, so the copy carries nothing else), binds every pointer and sends
+// all sources with ONE H2D copy from the page-locked mirror (a dozen small
+// hipMemcpyAsync calls from pageable memory cost ~20 us of runtime overhead each, more than the kernels of a single multi-frame; a hipMalloc / hipFree pair
+// per call cost more still); finish() brings the destinations back.  Block and mirror are reused by the next call, so whichever way the call ends after
+// commit(), finish() or the destructor synchronises the context's stream before the claim is released.
+//   host = false (device-kind call): in() / out() / inout() bind the caller's pointer and declare nothing; only scratch() takes room.  A call without
+//   pieces claims nothing and never waits.
+//   A piece of zero bytes is legal: it gets an aligned slot of its own (a distinct, valid address) and is never copied.
+struct Staging {
+	mcs_ctx* c; bool host;
+	Carve lay;   // the block's size, known before commit() places the pieces: a slot's size depends on its bytes only, so the sum is the same in any order
+	struct Piece { size_t off, bytes; const void* src; void* dst; void** bind; };
+	std::vector<Piece> pieces;
+	uint8_t* base = nullptr; bool claimed = false;
+	Staging(mcs_ctx* ctx, bool hostKind) : c(ctx), host(hostKind) {}
+	Staging(const Staging&) = delete;
+	Staging& operator=(const Staging&) = delete;
+	~Staging() { (void)release(); }
+
+	template <class P> void scratch(P** p, size_t bytes) { add((void**)p, bytes, nullptr, nullptr); }
+	template <class P, class T> void upload(P** p, const T* src, size_t bytes) { add((void**)p, bytes, src, nullptr); }   // a host value for either kind
+	template <class P, class T> void download(P** p, T* dst, size_t bytes) { add((void**)p, bytes, nullptr, dst); }       // a host result for either kind
+	template <class P, class T> void in(P** p, const T* src, size_t bytes) { if (host && src) add((void**)p, bytes, src, nullptr); else *p = (P*)src; }
+	template <class P, class T> void out(P** p, T* dst, size_t bytes) { if (host) add((void**)p, bytes, nullptr, dst); else *p = (P*)dst; }   // host, dst null: scratch
+	template <class P, class T> void inout(P** p, T* io, size_t bytes) { if (host && io) add((void**)p, bytes, io, io); else *p = (P*)io; }
+	size_t bytes() const { return lay.total; }
+
+	// `into`: a device allocation of the caller, bytes() long, instead of the context's block (an object that keeps what it uploads)
+	int commit(uint8_t* into = nullptr) {
+		if (pieces.empty()) return MCS_OK;
+		if (c->staging) return fail(MCS_ERR_UNSUPPORTED, "the context's staging block is in use by the enclosing call");
+		if (!into) { HIPCHK(c->block.reserve(lay.total)); into = c->block.p; }
+		base = into;
+		// the pieces with a source lie first, whatever the order of declaration: the one copy carries nothing else and the mirror covers nothing else
+		Carve at;
+		size_t hi = 0;
+		for (Piece& x : pieces) if (x.src) { x.off = at.take(x.bytes); if (x.bytes) hi = x.off + x.bytes; }
+		for (Piece& x : pieces) if (!x.src) x.off = at.take(x.bytes);
+		for (const Piece& x : pieces) *x.bind = into + x.off;
+		if (c->mirrorCap < hi) {
+			if (c->mirror) (void)hipHostFree(c->mirror);
+			c->mirror = nullptr; c->mirrorCap = 0;
+			HIPCHK(hipHostMalloc((void**)&c->mirror, hi + hi / 2, hipHostMallocDefault));
+			c->mirrorCap = hi + hi / 2;
 		}
-		dev = devBase; pin = c->pinned;
-		return hipSuccess;
+		c->staging = claimed = true;
+		for (const Piece& x : pieces)
+			if (x.src && x.bytes) memcpy(c->mirror + x.off, x.src, x.bytes);
+		if (hi) HIPCHK(hipMemcpyAsync(into, c->mirror, hi, hipMemcpyHostToDevice, c->stream));
+		return MCS_OK;
 	}
-	void put(size_t off, const void* src, size_t bytes) {
-		if (!bytes) return;
-		memcpy(pin + off, src, bytes);
-		lo = off < lo ? off : lo; hi = off + bytes > hi ? off + bytes : hi;
+	// rc == MCS_OK: every destination is downloaded (download = false: the caller has brought them back itself); then the stream is synchronised
+	int finish(int rc, bool download = true) {
+		if (!claimed) return rc;
+		hipError_t e = hipSuccess;
+		if (rc == MCS_OK && download)
+			for (const Piece& x : pieces)
+				if (x.dst && x.bytes && e == hipSuccess) e = hipMemcpyAsync(x.dst, base + x.off, x.bytes, hipMemcpyDeviceToHost, c->stream);
+		const hipError_t e2 = release();
+		if (rc != MCS_OK) return rc;
+		if (e != hipSuccess || e2 != hipSuccess) return fail(MCS_ERR_HIP, std::string("staged call: ") + hipGetErrorString(e != hipSuccess ? e : e2));
+		return MCS_OK;
 	}
-	hipError_t flush(hipStream_t s) { return hi > lo ? hipMemcpyAsync(dev + lo, pin + lo, hi - lo, hipMemcpyHostToDevice, s) : hipSuccess; }
+
+private:
+	void add(void** bind, size_t bytes, const void* src, void* dst) { lay.take(bytes); pieces.push_back(Piece{0, bytes, src, dst, bind}); }
+	hipError_t release() {
+		if (!claimed) return hipSuccess;
+		const hipError_t e = hipStreamSynchronize(c->stream);
+		c->staging = claimed = false;
+		return e;
+	}
 };

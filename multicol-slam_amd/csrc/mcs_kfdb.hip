@@ -410,7 +410,7 @@ struct mcs_kfdb {
 	double* stS[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
 	size_t stCap = 0;
 	// scratch of one batch
-	uint8_t* scratch = nullptr; size_t scratchCap = 0;
+	DevBuf scratch;
 };
 
 static int kfdb_slot(mcs_kfdb* db, int64_t kid) {
@@ -499,7 +499,6 @@ int mcs_kfdb_destroy(mcs_kfdb* db) {
 	(void)hipFree(db->dAddSeq); (void)hipFree(db->dId);
 	for (int m = 0; m < 2; ++m)
 		for (int b = 0; b < 2; ++b) { (void)hipFree(db->stQ[m][b]); (void)hipFree(db->stW[m][b]); (void)hipFree(db->stS[m][b]); }
-	(void)hipFree(db->scratch);
 	delete db;
 	return MCS_OK;
 }
@@ -644,18 +643,16 @@ static int kfdb_detect(mcs_kfdb* db, int loop, int nq, const int64_t* query_ids,
 	}
 	const int dcap = diag ? std::max(diag->cap, 0) : 0;
 	const size_t NS = (size_t)nq * S;
-	// scratch layout (8-byte aligned pieces)
-	size_t o = 0;
-	auto take = [&](size_t bytes) { const size_t r = o; o += (bytes + 255) & ~size_t(255); return r; };
-	const size_t oBm = take((size_t)nq * db->bmWords * 4), oErr = take(4), oQOff = take(((size_t)nq + 1) * 4), oQId = take((size_t)nq * 8),
-	             oMinS = take((size_t)nq * 8), oMinC = take((size_t)nq * 4), oNApp = take((size_t)nq * 4), oCnt = take(NS * 4), oMinw = take(NS * 4),
-	             oWA = take(NS * 4), oFl = take(NS), oSc = take(NS * 8), oConn = take(loop ? NS : 1), oLSlot = take(NS * 4), oLKey = take(NS * 8),
-	             oLAcc = take(NS * 8), oLBest = take(NS * 4), oLOrd = take(NS * 4), oSeen = take(NS), oCandN = take((size_t)nq * 4),
-	             oCand = take((size_t)nq * std::max(cap, 1) * 8), oDN = take((size_t)nq * 4), oDId = take((size_t)nq * std::max(dcap, 1) * 8),
-	             oDW = take((size_t)nq * std::max(dcap, 1) * 4), oDS = take((size_t)nq * std::max(dcap, 1) * 8), oDA = take((size_t)nq * std::max(dcap, 1) * 8),
-	             oDB = take((size_t)nq * std::max(dcap, 1) * 8), oQW = take(host ? total * 4 : 8), oQV = take(host ? total * 8 : 8);
-	HIPCHK(grow(&db->scratch, db->scratchCap, o, 0));
-	uint8_t* X = db->scratch;
+	Carve cv;   // scratch layout
+	const size_t oBm = cv.take((size_t)nq * db->bmWords * 4), oErr = cv.take(4), oQOff = cv.take(((size_t)nq + 1) * 4), oQId = cv.take((size_t)nq * 8),
+	             oMinS = cv.take((size_t)nq * 8), oMinC = cv.take((size_t)nq * 4), oNApp = cv.take((size_t)nq * 4), oCnt = cv.take(NS * 4), oMinw = cv.take(NS * 4),
+	             oWA = cv.take(NS * 4), oFl = cv.take(NS), oSc = cv.take(NS * 8), oConn = cv.take(loop ? NS : 1), oLSlot = cv.take(NS * 4), oLKey = cv.take(NS * 8),
+	             oLAcc = cv.take(NS * 8), oLBest = cv.take(NS * 4), oLOrd = cv.take(NS * 4), oSeen = cv.take(NS), oCandN = cv.take((size_t)nq * 4),
+	             oCand = cv.take((size_t)nq * std::max(cap, 1) * 8), oDN = cv.take((size_t)nq * 4), oDId = cv.take((size_t)nq * std::max(dcap, 1) * 8),
+	             oDW = cv.take((size_t)nq * std::max(dcap, 1) * 4), oDS = cv.take((size_t)nq * std::max(dcap, 1) * 8), oDA = cv.take((size_t)nq * std::max(dcap, 1) * 8),
+	             oDB = cv.take((size_t)nq * std::max(dcap, 1) * 8), oQW = cv.take(host ? total * 4 : 8), oQV = cv.take(host ? total * 8 : 8);
+	HIPCHK(db->scratch.reserve(cv.total));
+	uint8_t* X = db->scratch.p;
 	const int* dQWords = host ? (const int*)(X + oQW) : word_ids;
 	const double* dQVals = host ? (const double*)(X + oQV) : values;
 	HIPCHK(hipMemcpyAsync(X + oQOff, off.data(), ((size_t)nq + 1) * 4, hipMemcpyHostToDevice, st));
@@ -769,22 +766,13 @@ int mcs_kfdb_score(mcs_kfdb* db, int nw, const int32_t* word_ids, const double* 
 	}
 	int rc = kfdb_sync(db);
 	if (rc != MCS_OK) return rc;
-	size_t o = 0;
-	auto take = [&](size_t bytes) { const size_t r = o; o += (bytes + 255) & ~size_t(255); return r; };
-	const size_t oS = take((size_t)nkf * 4), oOut = take((size_t)nkf * 8), oW = take(host ? (size_t)nw * 4 : 8), oV = take(host ? (size_t)nw * 8 : 8);
-	HIPCHK(grow(&db->scratch, db->scratchCap, o, 0));
-	uint8_t* X = db->scratch;
-	HIPCHK(hipMemcpyAsync(X + oS, slots.data(), (size_t)nkf * 4, hipMemcpyHostToDevice, st));
-	if (host && nw) {
-		HIPCHK(hipMemcpyAsync(X + oW, word_ids, (size_t)nw * 4, hipMemcpyHostToDevice, st));
-		HIPCHK(hipMemcpyAsync(X + oV, values, (size_t)nw * 8, hipMemcpyHostToDevice, st));
-	}
-	hipLaunchKernelGGL(k_score_list, dim3((nkf + 255) / 256), dim3(256), 0, st, host ? (const int*)(X + oW) : word_ids, host ? (const double*)(X + oV) : values,
-	                   nw, (const int*)(X + oS), nkf, db->dRowOff, db->dRowLen, db->words, db->vals, host ? (double*)(X + oOut) : scores);
+	const int *dSlots = nullptr, *dW = nullptr; const double* dV = nullptr; double* dOut = nullptr;
+	Staging stg(c, host);
+	stg.upload(&dSlots, slots.data(), (size_t)nkf * 4); stg.in(&dW, word_ids, (size_t)nw * 4); stg.in(&dV, values, (size_t)nw * 8); stg.out(&dOut, scores, (size_t)nkf * 8);
+	if (int r = stg.commit()) return r;
+	hipLaunchKernelGGL(k_score_list, dim3((nkf + 255) / 256), dim3(256), 0, st, dW, dV, nw, dSlots, nkf, db->dRowOff, db->dRowLen, db->words, db->vals, dOut);
 	HIPCHK(hipGetLastError());
-	if (host) HIPCHK(hipMemcpyAsync(scores, X + oOut, (size_t)nkf * 8, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipStreamSynchronize(st));
-	return MCS_OK;
+	return stg.finish(MCS_OK);
 }
 
 int mcs_vocabulary_set_words(mcs_vocabulary* v, const int32_t* word_id_per_node, const double* weight_per_node) {
@@ -804,23 +792,18 @@ int mcs_bow_vector(mcs_vocabulary* v, const int32_t* leaf_nodes, int n, mcs_mem_
 	hipStream_t st = c->stream;
 	const bool host = kind == MCS_MEM_HOST;
 	const size_t nn = std::max(n, 1);
-	size_t o = 0;
-	auto take = [&](size_t bytes) { const size_t r = o; o += (bytes + 255) & ~size_t(255); return r; };
-	const size_t oL = take(nn * 4), oDW = take(nn * 4), oDWt = take(nn * 8), oOW = take(nn * 4), oOV = take(nn * 8), oN = take(4), oErr = take(4);
-	uint8_t* X = nullptr;
-	HIPCHK(ctx_arena(c, o, &X));
-	HIPCHK(hipMemsetAsync(X + oErr, 0, 4, st));
-	if (host && n) HIPCHK(hipMemcpyAsync(X + oL, leaf_nodes, (size_t)n * 4, hipMemcpyHostToDevice, st));
-	int* outW = host ? (int*)(X + oOW) : word_ids_out;
-	double* outV = host ? (double*)(X + oOV) : values_out;
-	int* nOut = host ? (int*)(X + oN) : nwords_out;
-	hipLaunchKernelGGL(k_bow_vector, dim3(1), dim3(1024), 0, st, host ? (const int*)(X + oL) : leaf_nodes, n, nNodes, nWords, wordOf, weightOf, hist, (int*)(X + oDW),
-	                   (double*)(X + oDWt), outW, outV, nOut, (int*)(X + oErr));
-	HIPCHK(hipGetLastError());
+	// host kind: the outputs hold nwords_out entries, known only after the kernel, so they are fetched below from the block (intact until the next call)
+	const int* dLeaf = nullptr; int *dW = nullptr, *outW = nullptr, *nOut = nullptr, *dErr = nullptr; double *dWt = nullptr, *outV = nullptr;
 	int errv = 0, d = 0;
-	HIPCHK(hipMemcpyAsync(&errv, X + oErr, 4, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipMemcpyAsync(&d, host ? (const void*)(X + oN) : (const void*)nwords_out, 4, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipStreamSynchronize(st));
+	Staging stg(c, host);
+	stg.in(&dLeaf, leaf_nodes, (size_t)n * 4); stg.scratch(&dW, nn * 4); stg.scratch(&dWt, nn * 8); stg.download(&dErr, &errv, 4);
+	if (host) { stg.scratch(&outW, nn * 4); stg.scratch(&outV, nn * 8); stg.download(&nOut, &d, 4); }
+	else { outW = word_ids_out; outV = values_out; nOut = nwords_out; }
+	if (int r = stg.commit()) return r;
+	HIPCHK(hipMemsetAsync(dErr, 0, 4, st));
+	hipLaunchKernelGGL(k_bow_vector, dim3(1), dim3(1024), 0, st, dLeaf, n, nNodes, nWords, wordOf, weightOf, hist, dW, dWt, outW, outV, nOut, dErr);
+	HIPCHK(hipGetLastError());
+	if (int r = stg.finish(MCS_OK)) return r;
 	if (errv & 1) return fail(MCS_ERR_INVALID, "mcs_bow_vector: leaf node id out of range");
 	if (errv & 2) return fail(MCS_ERR_INVALID, "mcs_bow_vector: a node with a weight > 0 has no word id (not a leaf)");
 	if (host) {

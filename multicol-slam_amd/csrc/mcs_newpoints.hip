@@ -261,18 +261,6 @@ __global__ __launch_bounds__(1024) void k_np_compact(const int* __restrict__ mat
 using namespace mcs;
 
 // ------------------------------------------------------------------------------------------------ C ABI
-static inline size_t np_al(size_t v) { return (v + 255) / 256 * 256; }
-
-static int np_ensure(mcs_ctx* c, size_t need) {
-	if (c->npBuf && c->npBufCap >= need) return MCS_OK;
-	if (c->npBuf) (void)hipFree(c->npBuf);   // waits for the device: no earlier call still reads it
-	c->npBuf = nullptr; c->npBufCap = 0;
-	const size_t want = need + need / 2 + 256;
-	HIPCHK(hipMalloc((void**)&c->npBuf, want));
-	c->npBufCap = want;
-	return MCS_OK;
-}
-
 static int np_check_geom(const mcs_kf_geom& g, bool withMp) {
 	if (g.n < 0 || g.nr_cams < 1 || g.nr_cams > 32) return fail(MCS_ERR_INVALID, "keyframe: n >= 0 and 1 <= nr_cams <= 32");
 	if (!g.MtMc || !g.MtMc_inv || !g.M_t || !g.cams) return fail(MCS_ERR_INVALID, "keyframe: null matrices / camera models");
@@ -291,23 +279,6 @@ static NpKf np_view(const mcs_kf_geom& g) {
 	return k;
 }
 
-// host-kind calls: the caller's arrays copied into one device block
-struct NpBump {
-	uint8_t* base = nullptr; size_t used = 0, cap = 0; hipStream_t s = nullptr; hipError_t err = hipSuccess;
-	void* put(const void* src, size_t bytes) {
-		void* p = base + used;
-		if (used + np_al(bytes) > cap) { err = hipErrorOutOfMemory; return base; }   // the block is sized from the same counts: never taken
-		used += np_al(bytes);
-		if (src && bytes && err == hipSuccess) err = hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, s);
-		return p;
-	}
-	~NpBump() { if (base) (void)hipFree(base); }
-};
-static size_t np_geom_bytes(const mcs_kf_geom& g, bool withMp) {
-	const size_t nc = (size_t)g.nr_cams, n = (size_t)g.n;
-	return 2 * np_al(nc * 128) + np_al(128) + np_al(nc * sizeof(mcs_ocam)) + np_al(n * 24) + np_al(n * sizeof(mcs_keypoint)) + np_al(n * 4) +
-	       (withMp ? np_al((size_t)g.n_mp * 24) + np_al((size_t)g.n_mp * 4) : 0);
-}
 static int np_check_host_geom(const mcs_kf_geom& g, bool withMp) {
 	for (int c = 0; c < g.nr_cams; ++c)
 		if (g.cams[c].invP_deg < 1 || g.cams[c].invP_deg > MCS_MAX_POLY) return fail(MCS_ERR_INVALID, "bad polynomial degree");
@@ -318,15 +289,19 @@ static int np_check_host_geom(const mcs_kf_geom& g, bool withMp) {
 			if (g.mp_cam[i] < 0 || g.mp_cam[i] >= g.nr_cams) return fail(MCS_ERR_INVALID, "map point camera outside the rig");
 	return MCS_OK;
 }
-static mcs_kf_geom np_stage_geom(NpBump& b, const mcs_kf_geom& g, bool withMp) {
-	mcs_kf_geom d = g;
+// host-kind calls: a keyframe's arrays declared on the call's staging, *d the view of the staged copies
+static void np_stage_geom(Staging& st, const mcs_kf_geom& g, bool withMp, mcs_kf_geom* d) {
+	*d = g;
 	const size_t nc = (size_t)g.nr_cams, n = (size_t)g.n;
-	d.MtMc = (const double*)b.put(g.MtMc, nc * 128); d.MtMc_inv = (const double*)b.put(g.MtMc_inv, nc * 128); d.M_t = (const double*)b.put(g.M_t, 128);
-	d.cams = (const mcs_ocam*)b.put(g.cams, nc * sizeof(mcs_ocam));
-	d.rays = (const double*)b.put(g.rays, n * 24); d.keys = (const mcs_keypoint*)b.put(g.keys, n * sizeof(mcs_keypoint)); d.cam = (const int32_t*)b.put(g.cam, n * 4);
-	if (withMp) { d.mp_pos = (const double*)b.put(g.mp_pos, (size_t)g.n_mp * 24); d.mp_cam = (const int32_t*)b.put(g.mp_cam, (size_t)g.n_mp * 4); }
-	else { d.mp_pos = nullptr; d.mp_cam = nullptr; d.n_mp = 0; }
-	return d;
+	st.in(&d->MtMc, g.MtMc, nc * 128); st.in(&d->MtMc_inv, g.MtMc_inv, nc * 128); st.in(&d->M_t, g.M_t, 128); st.in(&d->cams, g.cams, nc * sizeof(mcs_ocam));
+	st.in(&d->rays, g.rays, n * 24); st.in(&d->keys, g.keys, n * sizeof(mcs_keypoint)); st.in(&d->cam, g.cam, n * 4);
+	if (withMp) { st.in(&d->mp_pos, g.mp_pos, (size_t)g.n_mp * 24); st.in(&d->mp_cam, g.mp_cam, (size_t)g.n_mp * 4); }
+	else { d->mp_pos = nullptr; d->mp_cam = nullptr; d->n_mp = 0; }
+}
+// ... and the per-pair outputs
+static void np_stage_out(Staging& st, const mcs_newpoints_out* o, size_t rows, int nsets, mcs_newpoints_out* d) {
+	st.out(&d->verdict, o->verdict, rows * 4); st.out(&d->x3D, o->x3D, rows * 24); st.out(&d->acc_count, o->acc_count, (size_t)nsets * 4);
+	st.out(&d->acc_idx1, o->acc_idx1, rows * 4); st.out(&d->acc_idx2, o->acc_idx2, rows * 4); st.out(&d->acc_x3D, o->acc_x3D, rows * 24);
 }
 
 static bool np_out_ok(const mcs_newpoints_out* o) { return o && o->verdict && o->x3D && o->acc_count && o->acc_idx1 && o->acc_idx2 && o->acc_x3D; }
@@ -340,7 +315,7 @@ static void np_launch_pair(const NpTriArgs& t, int n1, int* nmatches, int* accCo
 static int np_triangulate_device(mcs_ctx* c, int nsets, const mcs_kf_geom* kf1, const mcs_kf_geom* kf2, const int32_t* match12, const uint8_t* skipped,
                                  double cosThresh, double maxDIST, const mcs_newpoints_out* out) {
 	hipStream_t s = c->stream;
-	if (c->side && c->greedyPending) { HIPCHK(hipStreamWaitEvent(s, c->evGreedy, 0)); c->greedyPending = false; }   // match12 may come from a search whose greedy pass runs beside
+	if (int r = ctx_join_greedy(c, s)) return r;   // match12 may come from a search whose greedy pass runs beside
 	const int n1 = kf1[0].n;
 	for (int p = 0; p < nsets; ++p) {
 		NpTriArgs t{};
@@ -362,13 +337,14 @@ static int np_chain_device(mcs_ctx* c, int nsets, const mcs_kf_geom* kf1, const 
 	int maxMp = 0;
 	for (int p = 0; p < nsets; ++p) maxMp = std::max(maxMp, kf2[p].n_mp);
 	const size_t eBlock = (size_t)nr * nr * 9;
-	const size_t oE = 0, oZ = oE + (E ? 0 : np_al(eBlock * 8 * nsets)), oR = oZ + np_al((size_t)maxMp * 8), oF = oR + 256, total = oF + np_al((size_t)nsets * 4);
-	if (int r = np_ensure(c, total)) return r;
-	double* Ework = E ? nullptr : (double*)(c->npBuf + oE);
-	double* z = (double*)(c->npBuf + oZ);
-	int* removed = (int*)(c->npBuf + oR);
-	if (!fallbacks) fallbacks = (int32_t*)(c->npBuf + oF);
-	if (c->side && c->greedyPending) { HIPCHK(hipStreamWaitEvent(s, c->evGreedy, 0)); c->greedyPending = false; }   // an earlier search's greedy pass may still read valid1
+	Carve cv;
+	const size_t oE = cv.take(E ? 0 : eBlock * 8 * nsets), oZ = cv.take((size_t)maxMp * 8), oR = cv.take(4), oF = cv.take((size_t)nsets * 4);
+	HIPCHK(c->npBuf.reserve(cv.total));
+	double* Ework = E ? nullptr : (double*)(c->npBuf.p + oE);
+	double* z = (double*)(c->npBuf.p + oZ);
+	int* removed = (int*)(c->npBuf.p + oR);
+	if (!fallbacks) fallbacks = (int32_t*)(c->npBuf.p + oF);
+	if (int r = ctx_join_greedy(c, s)) return r;   // an earlier search's greedy pass may still read valid1
 	if (n1 > 0 && valid1 != d1->valid) {
 		if (d1->valid) HIPCHK(hipMemcpyAsync(valid1, d1->valid, (size_t)n1, hipMemcpyDeviceToDevice, s));
 		else HIPCHK(hipMemsetAsync(valid1, 1, (size_t)n1, s));
@@ -392,7 +368,7 @@ static int np_chain_device(mcs_ctx* c, int nsets, const mcs_kf_geom* kf1, const 
 		const double* Ep = E ? E + Epitch * p : Ework + eBlock * p;
 		// lists on the context's stream (behind the previous neighbour's k_np_triangulate), greedy pass on the side stream behind the lists
 		if (int r = mcs_search_triangulation(c, 1, &q, 0, &d2[p], 0, kf1->rays, kf2[p].rays, Ep, nr, dim, K, MCS_MEM_DEVICE, m12, nmatches + p, fallbacks + p)) return r;
-		if (c->side && c->greedyPending) { HIPCHK(hipStreamWaitEvent(s, c->evGreedy, 0)); c->greedyPending = false; }   // match12 is complete behind the greedy pass
+		if (int r = ctx_join_greedy(c, s)) return r;   // match12 is complete behind the greedy pass
 		if (checkOri && n1 > 0 && kf2[p].n > 0)
 			launch_rotation_consistency(3, (const float*)((const uint8_t*)kf1->keys + angleOff), (int)sizeof(mcs_keypoint),
 			                            (const float*)((const uint8_t*)kf2[p].keys + angleOff), (int)sizeof(mcs_keypoint), nullptr, m12, n1, 0, removed, s);
@@ -407,23 +383,6 @@ static int np_chain_device(mcs_ctx* c, int nsets, const mcs_kf_geom* kf1, const 
 	c->lastResultStream = s;   // every output of the chain is complete on the context's stream
 	return MCS_OK;
 }
-
-// device copies of the per-pair outputs of a host-kind call
-struct NpOutDev {
-	mcs_newpoints_out d{};
-	void carve(NpBump& b, size_t rows, int nsets) {
-		d.verdict = (int32_t*)b.put(nullptr, rows * 4); d.x3D = (double*)b.put(nullptr, rows * 24); d.acc_count = (int32_t*)b.put(nullptr, (size_t)nsets * 4);
-		d.acc_idx1 = (int32_t*)b.put(nullptr, rows * 4); d.acc_idx2 = (int32_t*)b.put(nullptr, rows * 4); d.acc_x3D = (double*)b.put(nullptr, rows * 24);
-	}
-	static size_t bytes(size_t rows, int nsets) { return 3 * np_al(rows * 4) + 2 * np_al(rows * 24) + np_al((size_t)nsets * 4); }
-	hipError_t download(const mcs_newpoints_out* o, size_t rows, int nsets, hipStream_t s) const {
-		hipError_t e = hipSuccess;
-		auto dl = [&](void* dst, const void* src, size_t bytes) { if (bytes && e == hipSuccess) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s); };
-		dl(o->verdict, d.verdict, rows * 4); dl(o->x3D, d.x3D, rows * 24); dl(o->acc_count, d.acc_count, (size_t)nsets * 4);
-		dl(o->acc_idx1, d.acc_idx1, rows * 4); dl(o->acc_idx2, d.acc_idx2, rows * 4); dl(o->acc_x3D, d.acc_x3D, rows * 24);
-		return e;
-	}
-};
 
 extern "C" {
 
@@ -441,36 +400,28 @@ int mcs_triangulate_matches(mcs_ctx* c, int nsets, const mcs_kf_geom* kf1, const
 	HIPCHK(hipSetDevice(c->device));
 	if (kind == MCS_MEM_DEVICE) return np_triangulate_device(c, nsets, kf1, kf2, match12, skipped, cosThresh, maxDIST, out);
 	const size_t rows = (size_t)nsets * n1;
-	size_t need = np_al(rows * 4) + np_al((size_t)nsets) + NpOutDev::bytes(rows, nsets);
 	for (int p = 0; p < nsets; ++p) {
 		if (int r = np_check_host_geom(kf1[p], false)) return r;
 		if (int r = np_check_host_geom(kf2[p], false)) return r;
 		for (int i = 0; i < n1; ++i)
 			if (match12[(size_t)p * n1 + i] >= kf2[p].n) return fail(MCS_ERR_INVALID, "match12 entry outside the second keyframe");
-		need += np_geom_bytes(kf1[p], false) + np_geom_bytes(kf2[p], false);
 	}
-	NpBump b;
-	b.s = c->stream;
-	HIPCHK(hipMalloc((void**)&b.base, need + 256));
-	b.cap = need + 256;
+	Staging st(c, true);
 	std::vector<mcs_kf_geom> g1(nsets), g2(nsets);
+	std::vector<int> same(nsets, -1);
 	for (int p = 0; p < nsets; ++p) {
 		// the same keyframe behind several pairs (the current keyframe of a neighbour loop) is staged once
-		int same = -1;
-		for (int q = 0; q < p && same < 0; ++q) if (memcmp(&kf1[q], &kf1[p], sizeof(mcs_kf_geom)) == 0) same = q;
-		g1[p] = same >= 0 ? g1[same] : np_stage_geom(b, kf1[p], false);
-		g2[p] = np_stage_geom(b, kf2[p], false);
+		for (int q = 0; q < p && same[p] < 0; ++q) if (memcmp(&kf1[q], &kf1[p], sizeof(mcs_kf_geom)) == 0) same[p] = q;
+		if (same[p] < 0) np_stage_geom(st, kf1[p], false, &g1[p]);
+		np_stage_geom(st, kf2[p], false, &g2[p]);
 	}
-	const int32_t* dm = (const int32_t*)b.put(match12, rows * 4);
-	const uint8_t* dskip = skipped ? (const uint8_t*)b.put(skipped, (size_t)nsets) : nullptr;
-	NpOutDev od;
-	od.carve(b, rows, nsets);
-	auto done = [&](int rc) { (void)hipStreamSynchronize(c->stream); return rc; };
-	if (b.err != hipSuccess) return done(fail(MCS_ERR_HIP, "H2D copy failed"));
-	if (int r = np_triangulate_device(c, nsets, g1.data(), g2.data(), dm, dskip, cosThresh, maxDIST, &od.d)) return done(r);
-	if (od.download(out, rows, nsets, c->stream) != hipSuccess) return done(fail(MCS_ERR_HIP, "D2H copy failed"));
-	HIPCHK(hipStreamSynchronize(c->stream));
-	return MCS_OK;
+	const int32_t* dm = nullptr; const uint8_t* dskip = nullptr;
+	st.in(&dm, match12, rows * 4); st.in(&dskip, skipped, (size_t)nsets);
+	mcs_newpoints_out od{};
+	np_stage_out(st, out, rows, nsets, &od);
+	if (int r = st.commit()) return r;
+	for (int p = 0; p < nsets; ++p) if (same[p] >= 0) g1[p] = g1[same[p]];
+	return st.finish(np_triangulate_device(c, nsets, g1.data(), g2.data(), dm, dskip, cosThresh, maxDIST, &od));
 }
 
 int mcs_create_new_map_points(mcs_ctx* c, int nsets, const mcs_kf_geom* kf1, const mcs_desc_set* kf1_desc, const mcs_kf_geom* kf2, const mcs_desc_set* kf2_desc,
@@ -498,51 +449,39 @@ int mcs_create_new_map_points(mcs_ctx* c, int nsets, const mcs_kf_geom* kf1, con
 		                       baseline, median_depth, skipped, valid1, out);
 	const size_t rows = (size_t)nsets * n1, eDoubles = E ? E_set_pitch * (size_t)(nsets - 1) + (size_t)nr * nr * 9 : 0;
 	if (int r = np_check_host_geom(*kf1, false)) return r;
-	auto set_bytes = [](const mcs_desc_set& d) { const size_t n = (size_t)d.n; return np_al(n * d.stride) * (d.mask ? 2 : 1) + np_al(n) + np_al(n * 4); };
-	size_t need = np_geom_bytes(*kf1, false) + set_bytes(*kf1_desc) + np_al(eDoubles * 8) + NpOutDev::bytes(rows, nsets) + np_al(rows * 4) + 2 * np_al((size_t)nsets * 4) +
-	              2 * np_al((size_t)nsets * 8) + np_al((size_t)nsets) + np_al((size_t)n1);
-	for (int p = 0; p < nsets; ++p) {
+	for (int p = 0; p < nsets; ++p)
 		if (int r = np_check_host_geom(kf2[p], true)) return r;
-		need += np_geom_bytes(kf2[p], true) + set_bytes(kf2_desc[p]);
-	}
-	NpBump b;
-	b.s = c->stream;
-	HIPCHK(hipMalloc((void**)&b.base, need + 256));
-	b.cap = need + 256;
-	auto stage_set = [&](const mcs_desc_set& d, const int32_t* group) {
-		mcs_desc_set o = d;
+	Staging st(c, true);
+	// a descriptor set whose group array is its keyframe's keypoint_to_cam shares the staged copy (bound after commit)
+	auto stage_set = [&](const mcs_desc_set& d, const mcs_kf_geom& g, mcs_desc_set* o) {
+		*o = d;
 		const size_t n = (size_t)d.n;
-		o.desc = (const uint8_t*)b.put(d.desc, n * d.stride);
-		o.mask = d.mask ? (const uint8_t*)b.put(d.mask, n * d.stride) : nullptr;
-		o.valid = d.valid ? (const uint8_t*)b.put(d.valid, n) : nullptr;
-		o.group = group;
-		return o;
+		st.in(&o->desc, d.desc, n * d.stride); st.in(&o->mask, d.mask, n * d.stride); st.in(&o->valid, d.valid, n);
+		if (d.group != g.cam) st.in(&o->group, d.group, n * 4);
 	};
-	const mcs_kf_geom g1 = np_stage_geom(b, *kf1, false);
-	const mcs_desc_set s1 = stage_set(*kf1_desc, kf1_desc->group == kf1->cam ? g1.cam : (const int32_t*)b.put(kf1_desc->group, (size_t)n1 * 4));
+	mcs_kf_geom g1;
+	mcs_desc_set s1;
 	std::vector<mcs_kf_geom> g2(nsets);
 	std::vector<mcs_desc_set> s2(nsets);
-	for (int p = 0; p < nsets; ++p) {
-		g2[p] = np_stage_geom(b, kf2[p], true);
-		s2[p] = stage_set(kf2_desc[p], kf2_desc[p].group == kf2[p].cam ? g2[p].cam : (const int32_t*)b.put(kf2_desc[p].group, (size_t)kf2[p].n * 4));
-	}
-	const double* dE = E ? (const double*)b.put(E, eDoubles * 8) : nullptr;
-	NpOutDev od;
-	od.carve(b, rows, nsets);
-	int32_t* dM = (int32_t*)b.put(nullptr, rows * 4); int32_t* dN = (int32_t*)b.put(nullptr, (size_t)nsets * 4); int32_t* dF = (int32_t*)b.put(nullptr, (size_t)nsets * 4);
-	double* dB = (double*)b.put(nullptr, (size_t)nsets * 8); double* dMed = (double*)b.put(nullptr, (size_t)nsets * 8);
-	uint8_t* dS = (uint8_t*)b.put(nullptr, (size_t)nsets); uint8_t* dV = (uint8_t*)b.put(nullptr, (size_t)n1);
-	hipStream_t s = c->stream;
-	auto done = [&](int rc) { (void)mcs_ctx_synchronize(c); return rc; };
-	if (b.err != hipSuccess) return done(fail(MCS_ERR_HIP, "H2D copy failed"));
-	if (int r = np_chain_device(c, nsets, &g1, &s1, g2.data(), s2.data(), dE, E_set_pitch, dim, K, check_orientation, cosThresh, maxDIST, dM, dN, dF, dB, dMed, dS, dV, &od.d))
-		return done(r);
-	hipError_t e = od.download(out, rows, nsets, s);
-	auto dl = [&](void* dst, const void* src, size_t bytes) { if (dst && bytes && e == hipSuccess) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s); };
-	dl(match12, dM, rows * 4); dl(nmatches, dN, (size_t)nsets * 4); dl(fallbacks, dF, (size_t)nsets * 4); dl(baseline, dB, (size_t)nsets * 8);
-	dl(median_depth, dMed, (size_t)nsets * 8); dl(skipped, dS, (size_t)nsets); dl(valid1, dV, (size_t)n1);
-	if (e != hipSuccess) return done(fail(MCS_ERR_HIP, "D2H copy failed"));
-	return done(MCS_OK);
+	np_stage_geom(st, *kf1, false, &g1);
+	stage_set(*kf1_desc, *kf1, &s1);
+	for (int p = 0; p < nsets; ++p) { np_stage_geom(st, kf2[p], true, &g2[p]); stage_set(kf2_desc[p], kf2[p], &s2[p]); }
+	const double* dE = nullptr;
+	st.in(&dE, E, eDoubles * 8);
+	mcs_newpoints_out od{};
+	np_stage_out(st, out, rows, nsets, &od);
+	int32_t *dM = nullptr, *dN = nullptr, *dF = nullptr; double *dB = nullptr, *dMed = nullptr; uint8_t *dS = nullptr, *dV = nullptr;
+	st.out(&dM, match12, rows * 4); st.out(&dN, nmatches, (size_t)nsets * 4); st.out(&dF, fallbacks, (size_t)nsets * 4); st.out(&dB, baseline, (size_t)nsets * 8);
+	st.out(&dMed, median_depth, (size_t)nsets * 8); st.out(&dS, skipped, (size_t)nsets); st.out(&dV, valid1, (size_t)n1);
+	if (int r = st.commit()) return r;
+	if (kf1_desc->group == kf1->cam) s1.group = g1.cam;
+	for (int p = 0; p < nsets; ++p) if (kf2_desc[p].group == kf2[p].cam) s2[p].group = g2[p].cam;
+	// the chain's searches are device-kind calls on the staged arrays: they declare nothing on the block this call holds (a second claim would be refused)
+	const int rc = np_chain_device(c, nsets, &g1, &s1, g2.data(), s2.data(), dE, E_set_pitch, dim, K, check_orientation, cosThresh, maxDIST, dM, dN, dF, dB, dMed, dS, dV, &od);
+	if (rc != MCS_OK) (void)mcs_ctx_synchronize(c);   // a failed chain may leave a greedy pass on the side stream that still reads the staged arrays
+	// success: every neighbour's greedy pass was joined onto the context's stream inside the chain (ctx_join_greedy after each search), so the one
+	// synchronisation of that stream in finish() leaves the outputs complete and the staged arrays idle, with greedyPending already false
+	return st.finish(rc);
 }
 
 }  // extern "C"

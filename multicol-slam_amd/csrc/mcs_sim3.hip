@@ -462,13 +462,10 @@ struct mcs_sim3 {
 	uint8_t* dev = nullptr;            // constants and state, one allocation
 	OcamDev* dCams = nullptr; double* dMcInv = nullptr; Sim3Solver* dSolvers = nullptr; Sim3Corr* dCorr = nullptr; int* dCorrSolver = nullptr;
 	int* dIndex1 = nullptr; int* dDraws = nullptr; Sim3State* dState = nullptr;
-	uint8_t* scratch = nullptr; size_t scratchCap = 0;
 	Sim3Out* hOut = nullptr; size_t hOutCap = 0;   // page-locked read-back
 };
 
 namespace {
-
-inline size_t al256(size_t v) { return (v + 255) / 256 * 256; }
 
 // SetRansacParameters (:139-165): the iteration count, with the double -> int conversion of x86-64 (cvttsd2si: INT_MIN when out of range or NaN)
 int ransac_max_its(double probability, int minInliers, int maxIterations, int N) {
@@ -482,15 +479,6 @@ int ransac_max_its(double probability, int minInliers, int maxIterations, int N)
 	return std::max(1, std::min(nIterations, maxIterations));
 }
 
-hipError_t grow_scratch(mcs_sim3* b, size_t bytes) {
-	if (bytes <= b->scratchCap) return hipSuccess;
-	if (b->scratch) (void)hipFree(b->scratch);
-	b->scratch = nullptr; b->scratchCap = 0;
-	const hipError_t e = hipMalloc((void**)&b->scratch, bytes + bytes / 2);
-	if (e == hipSuccess) b->scratchCap = bytes + bytes / 2;
-	return e;
-}
-
 // the slots of solver s's iterations [first, first + count), mask offsets continuing from `words`
 void add_slots(const mcs_sim3* b, int s, int first, int count, std::vector<Sim3Slot>& slots, long long& words) {
 	for (int k = 0; k < count; ++k) {
@@ -499,23 +487,19 @@ void add_slots(const mcs_sim3* b, int s, int first, int count, std::vector<Sim3S
 	}
 }
 
-// hypotheses and scores of `slots` in the scratch buffer (which holds `extra` more bytes after them for the caller)
-struct Eval { size_t oSlots, oHyp, oPicks, oMasks, oCounts, end; };
-int evaluate(mcs_sim3* b, const std::vector<Sim3Slot>& slots, long long words, size_t extra, Eval& ev) {
-	hipStream_t st = b->ctx->stream;
+// hypotheses and scores of `slots`: declared on the call's staging (the destinations are optional), launched after its commit
+struct Eval { const Sim3Slot* slots; double* hyp; int* picks; unsigned long long* masks; int* counts; };
+void eval_stage(Staging& st, const std::vector<Sim3Slot>& slots, long long words, Eval& ev, double* hypOut, int32_t* picksOut, unsigned long long* masksOut, int32_t* countsOut) {
 	const size_t H = slots.size();
-	size_t o = 0;
-	auto take = [&](size_t bytes) { const size_t r = o; o += al256(std::max<size_t>(bytes, 1)); return r; };
-	ev.oSlots = take(H * sizeof(Sim3Slot)); ev.oHyp = take(H * kHypDoubles * 8); ev.oPicks = take(H * 12); ev.oMasks = take((size_t)words * 8);
-	ev.oCounts = take(H * 4); ev.end = o;
-	HIPCHK(grow_scratch(b, o + extra));
-	uint8_t* X = b->scratch;
+	st.upload(&ev.slots, slots.data(), H * sizeof(Sim3Slot));
+	st.out(&ev.hyp, hypOut, H * kHypDoubles * 8); st.out(&ev.picks, picksOut, H * 12); st.out(&ev.masks, masksOut, (size_t)words * 8); st.out(&ev.counts, countsOut, H * 4);
+}
+int eval_launch(mcs_sim3* b, size_t H, const Eval& ev) {
 	if (!H) return MCS_OK;
-	HIPCHK(hipMemcpyAsync(X + ev.oSlots, slots.data(), H * sizeof(Sim3Slot), hipMemcpyHostToDevice, st));
-	Sim3HypArgs ha{(int)H, (const Sim3Slot*)(X + ev.oSlots), b->dSolvers, b->dCorr, b->dDraws, b->seed, (double*)(X + ev.oHyp), (int*)(X + ev.oPicks)};
+	hipStream_t st = b->ctx->stream;
+	Sim3HypArgs ha{(int)H, ev.slots, b->dSolvers, b->dCorr, b->dDraws, b->seed, ev.hyp, ev.picks};
 	hipLaunchKernelGGL(k_sim3_hyp, dim3((unsigned)((H + 63) / 64)), dim3(64), 0, st, ha);
-	Sim3ScoreArgs sa{(int)H, b->nrCams, (const Sim3Slot*)(X + ev.oSlots), b->dSolvers, b->dCorr, b->dMcInv, b->dCams, (const double*)(X + ev.oHyp),
-	                 (unsigned long long*)(X + ev.oMasks), (int*)(X + ev.oCounts)};
+	Sim3ScoreArgs sa{(int)H, b->nrCams, ev.slots, b->dSolvers, b->dCorr, b->dMcInv, b->dCams, (const double*)ev.hyp, ev.masks, ev.counts};
 	hipLaunchKernelGGL(k_sim3_score, dim3((unsigned)((H + 3) / 4)), dim3(256), 0, st, sa);
 	HIPCHK(hipGetLastError());
 	return MCS_OK;
@@ -527,7 +511,6 @@ int mcs_sim3_destroy(mcs_sim3* b) {
 	if (!b) return MCS_OK;
 	(void)hipSetDevice(b->ctx->device);
 	(void)hipFree(b->dev);
-	(void)hipFree(b->scratch);
 	if (b->hOut) (void)hipHostFree(b->hOut);
 	delete b;
 	return MCS_OK;
@@ -548,16 +531,8 @@ int mcs_sim3_create(mcs_ctx* c, int nr_cams, const double* M_c, const mcs_ocam* 
 	const int nc = ns ? corr_offsets[ns] : 0;
 	if (nc && (!Xw || !cam || !sigma2 || !index1)) return fail(MCS_ERR_INVALID, "null correspondence array");
 	std::vector<OcamDev> hc(nr_cams);
-	for (int i = 0; i < nr_cams; ++i) {
-		const mcs_ocam& m = cams[i];
-		if (m.p_deg < 1 || m.p_deg > MCS_MAX_POLY || m.invP_deg < 1 || m.invP_deg > MCS_MAX_POLY) return fail(MCS_ERR_INVALID, "bad polynomial degree");
-		OcamDev& o = hc[i];
-		memset(&o, 0, sizeof(o));
-		o.c = m.c; o.d = m.d; o.e = m.e; o.u0 = m.u0; o.v0 = m.v0; o.invAffine = m.c - m.d * m.e;
-		for (int k = 0; k < m.p_deg; ++k) o.p[k] = m.p[k];
-		for (int k = 0; k < m.invP_deg; ++k) o.invP[k] = m.invP[k];
-		o.p_deg = m.p_deg; o.invP_deg = m.invP_deg;
-	}
+	for (int i = 0; i < nr_cams; ++i)
+		if (int r = ocam_to_dev(cams[i], &hc[i])) return r;
 	std::vector<Sim3Solver> sv(ns);
 	std::vector<int> corrSolver(nc);
 	int vb = 0, drawOff = 0;
@@ -597,31 +572,24 @@ int mcs_sim3_create(mcs_ctx* c, int nr_cams, const double* M_c, const mcs_ocam* 
 	mcs_sim3* b = new mcs_sim3();
 	b->ctx = c; b->ns = ns; b->nc = nc; b->nrCams = nr_cams; b->seed = seed; b->sumN1 = vb;
 	b->solvers = sv; b->mnIt.assign(ns, 0);
-	size_t o = 0;
-	auto take = [&](size_t bytes) { const size_t r = o; o += al256(std::max<size_t>(bytes, 1)); return r; };
-	const size_t oCams = take(sizeof(OcamDev) * nr_cams), oMc = take((size_t)nr_cams * 128), oMcInv = take((size_t)nr_cams * 128),
-	             oSol = take(sizeof(Sim3Solver) * ns), oCorr = take(sizeof(Sim3Corr) * nc), oCS = take(4 * (size_t)nc), oIdx = take(4 * (size_t)nc),
-	             oDraws = take(4 * (size_t)drawOff), oState = take(sizeof(Sim3State) * ns), oMt = take((size_t)ns * 256),
-	             oMtMc = take((size_t)ns * 2 * nr_cams * 128), oX = take((size_t)nc * 48), oCam = take((size_t)nc * 8), oSig = take((size_t)nc * 16);
+	// the object's constants and state are one allocation of its own, laid out by the staging that uploads them: the eleven arrays go up in one copy
+	Staging stg(c, true);
+	const double *dMc = nullptr, *dMt = nullptr, *dMtMc = nullptr, *dX = nullptr, *dSig = nullptr; const int* dCam = nullptr;
+	stg.upload(&b->dCams, hc.data(), sizeof(OcamDev) * nr_cams); stg.in(&dMc, M_c, (size_t)nr_cams * 128); stg.upload(&b->dSolvers, sv.data(), sizeof(Sim3Solver) * ns);
+	stg.upload(&b->dCorrSolver, corrSolver.data(), 4 * (size_t)nc); stg.in(&b->dIndex1, index1, 4 * (size_t)nc); stg.in(&b->dDraws, draws, 4 * (size_t)drawOff);
+	stg.in(&dMt, M_t_inv, (size_t)ns * 256); stg.in(&dMtMc, MtMc_inv, (size_t)ns * 2 * nr_cams * 128); stg.in(&dX, Xw, (size_t)nc * 48); stg.in(&dCam, cam, (size_t)nc * 8);
+	stg.in(&dSig, sigma2, (size_t)nc * 16);   // (nc == 0: the correspondence arrays may be null and stay null on the device; every kernel that reads them is bounded by nc)
+	stg.scratch(&b->dMcInv, (size_t)nr_cams * 128); stg.scratch(&b->dCorr, sizeof(Sim3Corr) * nc); stg.scratch(&b->dState, sizeof(Sim3State) * ns);
 	auto bail = [&](hipError_t e, const char* what) { mcs_sim3_destroy(b); return fail(MCS_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); };
-	hipError_t e = hipMalloc((void**)&b->dev, o);
+	hipError_t e = hipMalloc((void**)&b->dev, stg.bytes());
 	if (e != hipSuccess) return bail(e, "mcs_sim3_create: allocation");
-	uint8_t* D = b->dev;
-	b->dCams = (OcamDev*)(D + oCams); b->dMcInv = (double*)(D + oMcInv); b->dSolvers = (Sim3Solver*)(D + oSol); b->dCorr = (Sim3Corr*)(D + oCorr);
-	b->dCorrSolver = (int*)(D + oCS); b->dIndex1 = (int*)(D + oIdx); b->dDraws = draws ? (int*)(D + oDraws) : nullptr; b->dState = (Sim3State*)(D + oState);
 	hipStream_t st = c->stream;
-	struct Up { size_t off; const void* src; size_t bytes; };
-	const Up ups[] = {{oCams, hc.data(), sizeof(OcamDev) * nr_cams}, {oMc, M_c, (size_t)nr_cams * 128}, {oSol, sv.data(), sizeof(Sim3Solver) * ns},
-	                  {oCS, corrSolver.data(), 4 * (size_t)nc}, {oIdx, index1, 4 * (size_t)nc}, {oDraws, draws, 4 * (size_t)drawOff},
-	                  {oMt, M_t_inv, (size_t)ns * 256}, {oMtMc, MtMc_inv, (size_t)ns * 2 * nr_cams * 128}, {oX, Xw, (size_t)nc * 48}, {oCam, cam, (size_t)nc * 8},
-	                  {oSig, sigma2, (size_t)nc * 16}};
-	for (const Up& u : ups)
-		if (u.bytes && u.src && (e = hipMemcpyAsync(D + u.off, u.src, u.bytes, hipMemcpyHostToDevice, st)) != hipSuccess) return bail(e, "mcs_sim3_create: upload");
-	if (ns && (e = hipMemsetAsync(D + oState, 0, sizeof(Sim3State) * ns, st)) != hipSuccess) return bail(e, "mcs_sim3_create: state");
-	Sim3SetupArgs sa{nc, nr_cams, (const double*)(D + oMc), b->dMcInv, b->dCorrSolver, (const double*)(D + oMt), (const double*)(D + oMtMc), b->dCams,
-	                 (const double*)(D + oX), (const int*)(D + oCam), (const double*)(D + oSig), b->dCorr};
+	if (int r = stg.commit(b->dev)) { mcs_sim3_destroy(b); return r; }
+	if (ns && (e = hipMemsetAsync(b->dState, 0, sizeof(Sim3State) * ns, st)) != hipSuccess) return bail(e, "mcs_sim3_create: state");
+	Sim3SetupArgs sa{nc, nr_cams, dMc, b->dMcInv, b->dCorrSolver, dMt, dMtMc, b->dCams, dX, dCam, dSig, b->dCorr};
 	hipLaunchKernelGGL(k_sim3_setup, dim3((unsigned)((std::max(nc, nr_cams) + 63) / 64)), dim3(64), 0, st, sa);
-	if ((e = hipGetLastError()) != hipSuccess || (e = hipStreamSynchronize(st)) != hipSuccess) return bail(e, "mcs_sim3_create: setup");
+	if ((e = hipGetLastError()) != hipSuccess) return bail(e, "mcs_sim3_create: setup");
+	if (int r = stg.finish(MCS_OK)) { mcs_sim3_destroy(b); return r; }
 	*out = b;
 	return MCS_OK;
 }
@@ -681,34 +649,31 @@ int mcs_sim3_iterate(mcs_sim3* b, const int32_t* n_iterations, uint8_t* success,
 		}
 	}
 	slotOff[ns] = (int)slots.size();
-	const size_t oNIt = 0, oOff = al256(4 * (size_t)ns), oOut = oOff + al256(4 * ((size_t)ns + 1)), oVb = oOut + al256(sizeof(Sim3Out) * ns),
-	             extra = oVb + al256(std::max(b->sumN1, 1));
-	Eval ev;
-	const int rc = evaluate(b, slots, words, extra, ev);
-	if (rc != MCS_OK) return rc;
-	uint8_t* X = b->scratch;
-	uint8_t* Y = X + ev.end;
-	HIPCHK(hipMemcpyAsync(Y + oNIt, nIt.data(), 4 * (size_t)ns, hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemcpyAsync(Y + oOff, slotOff.data(), 4 * ((size_t)ns + 1), hipMemcpyHostToDevice, st));
-	Sim3ScanArgs sa{ns, (const int*)(Y + oNIt), (const int*)(Y + oOff), (const Sim3Slot*)(X + ev.oSlots), b->dSolvers, (const double*)(X + ev.oHyp),
-	                (const int*)(X + ev.oCounts), b->dState, (Sim3Out*)(Y + oOut)};
-	hipLaunchKernelGGL(k_sim3_scan, dim3((ns + 63) / 64), dim3(64), 0, st, sa);
-	if (inliers && b->sumN1) {
-		HIPCHK(hipMemsetAsync(Y + oVb, 0, b->sumN1, st));
-		if (b->nc)
-			hipLaunchKernelGGL(k_sim3_inliers, dim3((b->nc + 255) / 256), dim3(256), 0, st, b->nc, (const int*)b->dCorrSolver, (const int*)b->dIndex1,
-			                   (const Sim3Solver*)b->dSolvers, (const Sim3Out*)(Y + oOut), (const unsigned long long*)(X + ev.oMasks), Y + oVb);
-	}
-	HIPCHK(hipGetLastError());
 	if (b->hOutCap < (size_t)ns) {
 		if (b->hOut) (void)hipHostFree(b->hOut);
 		b->hOut = nullptr; b->hOutCap = 0;
 		HIPCHK(hipHostMalloc((void**)&b->hOut, sizeof(Sim3Out) * ns, hipHostMallocDefault));
 		b->hOutCap = ns;
 	}
-	HIPCHK(hipMemcpyAsync(b->hOut, Y + oOut, sizeof(Sim3Out) * ns, hipMemcpyDeviceToHost, st));
-	if (inliers && b->sumN1) HIPCHK(hipMemcpyAsync(inliers, Y + oVb, b->sumN1, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipStreamSynchronize(st));
+	const bool wantInliers = inliers && b->sumN1;
+	Staging stg(b->ctx, true);
+	Eval ev{};
+	eval_stage(stg, slots, words, ev, nullptr, nullptr, nullptr, nullptr);
+	const int *dNIt = nullptr, *dOff = nullptr; Sim3Out* dOut = nullptr; uint8_t* dVb = nullptr;
+	stg.upload(&dNIt, nIt.data(), 4 * (size_t)ns); stg.upload(&dOff, slotOff.data(), 4 * ((size_t)ns + 1));
+	stg.out(&dOut, b->hOut, sizeof(Sim3Out) * ns); stg.out(&dVb, wantInliers ? inliers : nullptr, (size_t)b->sumN1);
+	if (int r = stg.commit()) return r;
+	if (int r = eval_launch(b, slots.size(), ev)) return r;
+	Sim3ScanArgs sa{ns, dNIt, dOff, ev.slots, b->dSolvers, (const double*)ev.hyp, (const int*)ev.counts, b->dState, dOut};
+	hipLaunchKernelGGL(k_sim3_scan, dim3((ns + 63) / 64), dim3(64), 0, st, sa);
+	if (wantInliers) {
+		HIPCHK(hipMemsetAsync(dVb, 0, b->sumN1, st));
+		if (b->nc)
+			hipLaunchKernelGGL(k_sim3_inliers, dim3((b->nc + 255) / 256), dim3(256), 0, st, b->nc, (const int*)b->dCorrSolver, (const int*)b->dIndex1,
+			                   (const Sim3Solver*)b->dSolvers, (const Sim3Out*)dOut, (const unsigned long long*)ev.masks, dVb);
+	}
+	HIPCHK(hipGetLastError());
+	if (int r = stg.finish(MCS_OK)) return r;
 	for (int s = 0; s < ns; ++s) {
 		const Sim3Out& o = b->hOut[s];
 		b->mnIt[s] = o.mnIterations;
@@ -745,20 +710,15 @@ int mcs_sim3_hypotheses(mcs_sim3* b, int solver, int first, int count, int32_t* 
 	if (S.drawOff >= 0 && (long long)first + count > S.nDraws) return fail(MCS_ERR_INVALID, "mcs_sim3_hypotheses: beyond the caller's draws");
 	if (!count) return MCS_OK;
 	HIPCHK(hipSetDevice(b->ctx->device));
-	hipStream_t st = b->ctx->stream;
 	std::vector<Sim3Slot> slots;
 	long long words = 0;
 	add_slots(b, solver, first, count, slots, words);
-	Eval ev;
-	const int rc = evaluate(b, slots, words, 0, ev);
-	if (rc != MCS_OK) return rc;
-	uint8_t* X = b->scratch;
 	std::vector<unsigned long long> m(inliers ? (size_t)words : 0);
-	HIPCHK(hipMemcpyAsync(n_inliers, X + ev.oCounts, 4 * (size_t)count, hipMemcpyDeviceToHost, st));
-	if (picks) HIPCHK(hipMemcpyAsync(picks, X + ev.oPicks, 12 * (size_t)count, hipMemcpyDeviceToHost, st));
-	if (hyp) HIPCHK(hipMemcpyAsync(hyp, X + ev.oHyp, (size_t)count * kHypDoubles * 8, hipMemcpyDeviceToHost, st));
-	if (inliers && words) HIPCHK(hipMemcpyAsync(m.data(), X + ev.oMasks, (size_t)words * 8, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipStreamSynchronize(st));
+	Staging stg(b->ctx, true);
+	Eval ev{};
+	eval_stage(stg, slots, words, ev, hyp, picks, inliers ? m.data() : nullptr, n_inliers);
+	if (int r = stg.commit()) return r;
+	if (int r = stg.finish(eval_launch(b, slots.size(), ev))) return r;
 	if (inliers)
 		for (int h = 0; h < count; ++h)
 			for (int i = 0; i < S.N; ++i) inliers[(size_t)h * S.N + i] = (uint8_t)((m[(size_t)h * S.maskWords + (i >> 6)] >> (i & 63)) & 1ull);
