@@ -888,4 +888,93 @@ NewMapPoints CreateNewMapPoints(Context& ctx, KF* pKF, const std::vector<KF*>& v
 	return out;
 }
 
+// cTracking::SearchReferencePointsInFrustum (src/cTracking.cpp:953-1012) over mcs_search_local_points: the first loop (:957-976) runs here as written, then
+// cMultiFrame::isInFrustum for every local point in every camera, the nToMatch gate and cORBmatcher::SearchByProjection(F, mvpLocalMapPoints, th) are ONE
+// device call.  Afterwards the tracking fields and visible counts are written back onto the map points, F.mvpMapPoints is filled and the reference's value
+// (matches of the first loop + the search's) is returned.  FR: the caller's frame type with camSystem (a cMultiCamSys_ of this header), mnId, mvpMapPoints
+// (vector of MP*), mvKeys (28-byte cv::KeyPoint-layout records), keypoint_to_cam and cont_idx_to_local_cam_idx (find(i)->second), mvScaleFactors,
+// GetDescriptorRowPtr(cam, row) and, with havingMasks, GetDescriptorMaskRowPtr(cam, row).  MP: GetWorldPos(), GetNormal(), GetMinDistanceInvariance(),
+// GetMaxDistanceInvariance(), isBad(), IncreaseVisible(), mnLastFrameSeen, GetDescriptorPtr() / GetDescriptorMaskPtr() and the per-camera fields
+// mbTrackInView, mTrackProjX, mTrackProjY, mnTrackScaleLevel, mTrackViewCos (indexable by camera, at least GetNrCams() entries: include/cMapPoint.h:101-105).
+// UpdateReference, PoseOptimization and the IncreaseFound bookkeeping of TrackLocalMap stay with the caller.
+template <class FR, class MP>
+int SearchReferencePointsInFrustum(Context& ctx, FR& F, std::vector<MP*>& vpLocalMapPoints, double th = 3.0, double nnratio = 0.8, int descDim = 32,
+                                   bool havingMasks = false) {
+	cMultiCamSys_& cs = F.camSystem;
+	const int nr = cs.GetNrCams();
+	int nrMatches = 0;
+	for (size_t i = 0; i < F.mvpMapPoints.size(); ++i) {   // :957-976
+		MP* pMP = F.mvpMapPoints[i];
+		if (!pMP) continue;
+		if (pMP->isBad()) { F.mvpMapPoints[i] = nullptr; continue; }
+		pMP->IncreaseVisible();
+		pMP->mnLastFrameSeen = F.mnId;
+		pMP->mbTrackInView[(int)F.keypoint_to_cam.find(i)->second] = false;
+		++nrMatches;
+	}
+	const size_t np = vpLocalMapPoints.size(), ns = np * (size_t)nr, nf = F.mvKeys.size();
+	if (np == 0) return nrMatches;
+	std::vector<double> pos(3 * np), nrm(3 * np), minD(np), maxD(np), px(ns), py(ns), vc(ns), MtMc((size_t)nr * 16), MtMcInv((size_t)nr * 16);
+	std::vector<uint8_t> flags(np), inView(ns), desc(np * (size_t)descDim), mask(havingMasks ? np * (size_t)descDim : 0);
+	std::vector<int32_t> lvl(ns), vis(np), match(ns, -1);
+	for (size_t i = 0; i < np; ++i) {
+		MP* pMP = vpLocalMapPoints[i];
+		const auto X = pMP->GetWorldPos();
+		const auto N = pMP->GetNormal();
+		for (int k = 0; k < 3; ++k) { pos[3 * i + k] = Sim3At(X, k); nrm[3 * i + k] = Sim3At(N, k); }
+		minD[i] = pMP->GetMinDistanceInvariance(); maxD[i] = pMP->GetMaxDistanceInvariance();
+		flags[i] = (uint8_t)((pMP->isBad() ? MCS_LP_BAD : 0) | (pMP->mnLastFrameSeen == F.mnId ? MCS_LP_SEEN : 0));
+		for (int c = 0; c < nr; ++c) {
+			const size_t p = i * (size_t)nr + c;
+			inView[p] = pMP->mbTrackInView[c] ? 1 : 0; px[p] = pMP->mTrackProjX[c]; py[p] = pMP->mTrackProjY[c];
+			lvl[p] = pMP->mnTrackScaleLevel[c]; vc[p] = pMP->mTrackViewCos[c];
+		}
+		std::memcpy(&desc[i * (size_t)descDim], pMP->GetDescriptorPtr(), (size_t)descDim);
+		if (havingMasks) std::memcpy(&mask[i * (size_t)descDim], pMP->GetDescriptorMaskPtr(), (size_t)descDim);
+	}
+	std::vector<mcs_ocam> oc;
+	std::vector<const uint8_t*> mm;
+	std::vector<int32_t> w, h;
+	bool any = false;
+	for (int c = 0; c < nr; ++c) {
+		cCamModelGeneral_& m = cs.camModels[c];
+		oc.push_back(m.ocam); w.push_back(m.ocam.width); h.push_back(m.ocam.height);
+		mm.push_back(m.mirrorMask0.empty() ? nullptr : m.mirrorMask0.data); any = any || !m.mirrorMask0.empty();
+		std::memcpy(&MtMc[16 * (size_t)c], cs.MtMc[c].data(), 128); std::memcpy(&MtMcInv[16 * (size_t)c], cs.MtMc_inv[c].data(), 128);
+	}
+	std::vector<mcs_keypoint> keys(nf);
+	std::vector<int32_t> fcam(nf);
+	std::vector<uint8_t> fdesc(nf * (size_t)descDim), fmask(havingMasks ? nf * (size_t)descDim : 0), assigned(std::max<size_t>(nf, 1));
+	for (size_t i = 0; i < nf; ++i) {
+		static_assert(sizeof(F.mvKeys[0]) == sizeof(mcs_keypoint), "mvKeys must hold cv::KeyPoint-layout records");
+		std::memcpy(&keys[i], &F.mvKeys[i], sizeof(mcs_keypoint));
+		const int c = (int)F.keypoint_to_cam.find(i)->second, row = (int)F.cont_idx_to_local_cam_idx.find(i)->second;
+		fcam[i] = c;
+		std::memcpy(&fdesc[i * (size_t)descDim], F.GetDescriptorRowPtr(c, row), (size_t)descDim);
+		if (havingMasks) std::memcpy(&fmask[i * (size_t)descDim], F.GetDescriptorMaskRowPtr(c, row), (size_t)descDim);
+		assigned[i] = F.mvpMapPoints[i] ? 1 : 0;
+	}
+	mcs_local_points lp{pos.data(), nrm.data(), minD.data(), maxD.data(), flags.data(), (int32_t)np};
+	mcs_rig_view rig{MtMcInv.data(), MtMc.data(), oc.data(), any ? mm.data() : nullptr, nr};
+	mcs_track_state st{inView.data(), px.data(), py.data(), lvl.data(), vc.data()};
+	mcs_frame_view fv{keys.data(), fdesc.data(), havingMasks ? fmask.data() : nullptr, fcam.data(), assigned.data(), (int32_t)nf, descDim, nr, w.data(), h.data(),
+	                  F.mvScaleFactors.data(), (int32_t)F.mvScaleFactors.size()};
+	int32_t nmatches = 0, nToMatch = 0;
+	mcs_throw(mcs_search_local_points(ctx.h, &lp, &rig, &st, desc.data(), havingMasks ? mask.data() : nullptr, descDim, &fv, th, nnratio, descDim, MCS_MEM_HOST,
+	                                  match.data(), &nmatches, &nToMatch, vis.data()));
+	for (size_t i = 0; i < np; ++i) {
+		MP* pMP = vpLocalMapPoints[i];
+		for (int k = 0; k < vis[i]; ++k) pMP->IncreaseVisible();   // :995
+		if (flags[i]) continue;                                    // the loop :981-999 never touched this point
+		for (int c = 0; c < nr; ++c) {
+			const size_t p = i * (size_t)nr + c;
+			pMP->mbTrackInView[c] = inView[p] != 0; pMP->mTrackProjX[c] = px[p]; pMP->mTrackProjY[c] = py[p];
+			pMP->mnTrackScaleLevel[c] = lvl[p]; pMP->mTrackViewCos[c] = vc[p];
+		}
+	}
+	for (size_t p = 0; p < ns; ++p)
+		if (match[p] >= 0) F.mvpMapPoints[(size_t)match[p]] = vpLocalMapPoints[p / (size_t)nr];   // F.mvpMapPoints[bestIdx] = pMP, src/cORBmatcher.cpp:159
+	return nrMatches + nmatches;
+}
+
 }  // namespace MultiColSLAM

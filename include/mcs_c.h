@@ -34,8 +34,9 @@ extern "C" {
 /* ABI revision of this header: bumped whenever a struct layout or an entry point's signature changes (3: mcs_desc_set carries block_rows / block_pitch_rows
  * since round 2 — callers built against an older header must be recompiled; mcs_describe_fast_table, FAST types 0 / 1 in round 3; 4: mcs_extractor_tie_stats; 5: mcs_copy_narrow,
  * mcs_ctx_result_stream, mcs_ctx_stream_conflicts, mcs_ctx_transfer_stream in round 4; 8: mcs_extractor_set_tie_capture / _patch_ties in round 6;
- * 9: the keyframe database mcs_kfdb_*, mcs_vocabulary_set_words, mcs_bow_vector; 10: the Sim3 RANSAC mcs_sim3_*).  mcs_abi_version() returns
- * the value the LIBRARY was built with: compare it with MCS_ABI_VERSION after dlopen. */
+ * 9: the keyframe database mcs_kfdb_*, mcs_vocabulary_set_words, mcs_bow_vector; 10: the Sim3 RANSAC mcs_sim3_*).  Purely additive
+ * entry points leave it alone: mcs_triangulate_matches / mcs_create_new_map_points and mcs_frustum / mcs_search_local_points arrived within revision 10 (look
+ * them up with dlsym).  mcs_abi_version() returns the value the LIBRARY was built with: compare it with MCS_ABI_VERSION after dlopen. */
 #define MCS_ABI_VERSION 10
 
 #define MCS_MAX_POLY 16
@@ -522,6 +523,48 @@ int mcs_create_new_map_points(mcs_ctx*, int nsets, const mcs_kf_geom* kf1, const
                               const mcs_desc_set* kf2_desc /* [nsets] */, const double* E /* optional */, size_t E_set_pitch, int dim, int K,
                               int check_orientation, double cosThresh, double maxDIST, mcs_mem_kind kind, int32_t* match12, int32_t* nmatches,
                               int32_t* fallbacks, double* baseline, double* median_depth, uint8_t* skipped, uint8_t* valid1, const mcs_newpoints_out* out);
+
+/* ------------------------------------------------------------------ cTracking::SearchReferencePointsInFrustum (src/cTracking.cpp:953-1012): the search step of TrackLocalMap
+ * The local map points as the function reads them, n points:
+ *   pos / normal          GetWorldPos() / GetNormal(), 3 doubles each
+ *   min_dist / max_dist   GetMinDistanceInvariance() / GetMaxDistanceInvariance()
+ *   flags                 bit0 = isBad(), bit1 = (mnLastFrameSeen == mCurrentFrame.mnId) AFTER the function's first loop (:957-976), which stays with the caller
+ * The rig: Get_MtMc_inv(c) / Get_MtMc(c) (4x4 row-major per camera), the camera models (the backward polynomial, width and height are read) and the nr_cams
+ * level-0 mirror masks (rows of cams[c].width bytes; the pointer array, or NULL for the bounds test only).
+ * The tracking fields the reference keeps on every map point, [n][nr_cams] each, slot p = i * nr_cams + c:
+ *   in_view = mbTrackInView[c], proj_x / proj_y = mTrackProjX / Y[c], level = mnTrackScaleLevel[c], view_cos = mTrackViewCos[c]
+ * They are IN/OUT state: the slots of a point whose flags are non-zero are not written (:985-988), a slot that isInFrustum rejects gets in_view = 0 and keeps its
+ * other four fields, a slot it accepts gets all five.  Every POINTER lives where the call's `kind` says (matrices, camera models, the mask pointer array and the
+ * masks too); the structs and their counts are host values. */
+typedef struct {
+	const double* pos; const double* normal; const double* min_dist; const double* max_dist; const uint8_t* flags; int32_t n;
+} mcs_local_points;
+typedef struct {
+	const double* MtMc_inv; const double* MtMc; const mcs_ocam* cams; const uint8_t* const* mirror_masks; int32_t nr_cams;
+} mcs_rig_view;
+typedef struct {
+	uint8_t* in_view; double* proj_x; double* proj_y; int32_t* level; double* view_cos;
+} mcs_track_state;
+#define MCS_LP_BAD 1    /* mcs_local_points.flags */
+#define MCS_LP_SEEN 2
+/* mcs_frustum              bool cMultiFrame::isInFrustum(int cam, cMapPoint*, double viewingCosLimit) (src/cMultiFrame.cpp:218-270) for every camera of every point
+ *     whose flags are 0, i.e. the loop :981-999.  visible_inc[i] = cameras point i came into view in (one IncreaseVisible() each, :995), n_to_match = their sum
+ *     (nToMatch).  scale_factors / nlevels: mvScaleFactors, mnScaleLevels (1 .. MCS_MAX_LEVELS).  As in the reference viewingCosLimit is not applied (:249-250), a
+ *     point behind a camera is in view if it projects inside the mask, and NaN distances pass the range test.
+ * mcs_search_local_points  the function from :978 on: that loop, then, only if n_to_match > 0 (:1001), cORBmatcher::SearchByProjection(F, mvpLocalMapPoints, th)
+ *     (:67-166, as mcs_search_by_projection) over every slot whose in_view is set and whose point is not bad — the slots of MCS_LP_SEEN points included, with
+ *     whatever earlier frames left there.  desc / mask: one descriptor (+ mask, or NULL) row of `stride` bytes per POINT; frame: as for mcs_search_by_projection
+ *     (assigned updated in place; frame->nr_cams must equal rig->nr_cams, its scale_factors / nlevels are the frustum's).
+ *     match[n * nr_cams] = frame feature matched to slot p or -1, nmatches = the search's return value (the caller adds the count of its first loop),
+ *     n_to_match and visible_inc as above.  An in-view slot whose level lies outside [0, nlevels) (stale state only) is not searched; host-kind: MCS_ERR_INVALID.
+ * n = 0 is a successful no-op (n_to_match = 0, nmatches = 0).  DEVICE: both only enqueue work on the context's stream — no host wait, no count read back — and
+ * all outputs are complete in the order of that stream when they return; scratch comes from a grow-only buffer of the context (growing it waits for the device).
+ * mcs_search_local_points is refused with MCS_ERR_UNSUPPORTED while deferred searches are on (mcs_ctx_set_async_search). */
+int mcs_frustum(mcs_ctx*, const mcs_local_points* pts, const mcs_rig_view* rig, const double* scale_factors, int nlevels, const mcs_track_state* state,
+                mcs_mem_kind kind, int32_t* visible_inc, int32_t* n_to_match);
+int mcs_search_local_points(mcs_ctx*, const mcs_local_points* pts, const mcs_rig_view* rig, const mcs_track_state* state, const uint8_t* desc,
+                            const uint8_t* mask, int stride, const mcs_frame_view* frame, double th, double nnratio, int dim, mcs_mem_kind kind,
+                            int32_t* match, int32_t* nmatches, int32_t* n_to_match, int32_t* visible_inc);
 
 /* self-test of an arithmetic shortcut of the descriptor kernel: the omni model's three divisions by the same norm (src/cam_model_omni.cpp:
  * 146-161) share one refined reciprocal; this runs n pseudo-random (numerator, denominator) pairs of the magnitudes the kernel sees through

@@ -77,6 +77,7 @@ EXPORTS = [
     "mcs_sim3_create", "mcs_sim3_destroy", "mcs_sim3_set_ransac_parameters", "mcs_sim3_iterate", "mcs_sim3_best", "mcs_sim3_info",
     "mcs_sim3_hypotheses", "mcs_sim3_draw",
     "mcs_triangulate_matches", "mcs_create_new_map_points",
+    "mcs_frustum", "mcs_search_local_points",
 ]
 
 WINDOW_RATIO, WINDOW_BEST, WINDOW_INITIALIZE = 1, 2, 3
@@ -116,6 +117,21 @@ class NewPointsOut(C.Structure):   # mcs_newpoints_out
 
 # verdict codes of mcs_triangulate_matches / mcs_create_new_map_points (MCS_NP_* of include/mcs_c.h)
 NP_NO_MATCH, NP_ACCEPTED, NP_PARALLAX, NP_BEHIND_1, NP_REPROJ_1, NP_BEHIND_2, NP_REPROJ_2, NP_DISTANCE, NP_SKIPPED = range(9)
+
+
+class LocalPoints(C.Structure):   # mcs_local_points: the local map points as cTracking::SearchReferencePointsInFrustum reads them (src/cTracking.cpp:978-999)
+    _fields_ = [("pos", C.c_void_p), ("normal", C.c_void_p), ("min_dist", C.c_void_p), ("max_dist", C.c_void_p), ("flags", C.c_void_p), ("n", C.c_int32)]
+
+
+class RigView(C.Structure):   # mcs_rig_view
+    _fields_ = [("MtMc_inv", C.c_void_p), ("MtMc", C.c_void_p), ("cams", C.c_void_p), ("mirror_masks", C.c_void_p), ("nr_cams", C.c_int32)]
+
+
+class TrackState(C.Structure):   # mcs_track_state: mbTrackInView / mTrackProjX / mTrackProjY / mnTrackScaleLevel / mTrackViewCos, [npoints][nr_cams]
+    _fields_ = [("in_view", C.c_void_p), ("proj_x", C.c_void_p), ("proj_y", C.c_void_p), ("level", C.c_void_p), ("view_cos", C.c_void_p)]
+
+
+LP_BAD, LP_SEEN = 1, 2   # MCS_LP_* of include/mcs_c.h
 
 
 _lib = None
@@ -216,6 +232,9 @@ def lib():
     L.mcs_triangulate_matches.argtypes = [vp, C.c_int, C.POINTER(KfGeom), C.POINTER(KfGeom), vp, vp, C.c_double, C.c_double, C.c_int, C.POINTER(NewPointsOut)]
     L.mcs_create_new_map_points.argtypes = [vp, C.c_int, C.POINTER(KfGeom), C.POINTER(DescSet), C.POINTER(KfGeom), C.POINTER(DescSet), vp, C.c_size_t, C.c_int,
                                             C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.POINTER(NewPointsOut)]
+    L.mcs_frustum.argtypes = [vp, C.POINTER(LocalPoints), C.POINTER(RigView), vp, C.c_int, C.POINTER(TrackState), C.c_int, vp, vp]
+    L.mcs_search_local_points.argtypes = [vp, C.POINTER(LocalPoints), C.POINTER(RigView), C.POINTER(TrackState), vp, vp, C.c_int, C.POINTER(FrameView),
+                                          C.c_double, C.c_double, C.c_int, C.c_int, vp, vp, vp, vp]
     L.mcs_copy_narrow.argtypes = [vp, vp, vp, C.c_size_t, C.c_int, vp]
     L.mcs_ctx_result_stream.argtypes = [vp, C.POINTER(vp)]
     L.mcs_ctx_stream_conflicts.argtypes = [vp, vp, C.POINTER(C.c_uint)]

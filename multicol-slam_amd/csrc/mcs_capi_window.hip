@@ -1,5 +1,6 @@
 // mcs_capi_window.hip — C ABI of the grid-window matchers (SearchByProjection(F, mapPoints) and the explicit-window rules) and of the projection they
-// consume (include/mcs_c.h: mcs_search_by_projection, mcs_window_match, mcs_world_to_cam).  Kernels: mcs_project.hip.
+// consume (include/mcs_c.h: mcs_search_by_projection, mcs_window_match, mcs_world_to_cam), and of the search step of TrackLocalMap that chains the two
+// (mcs_frustum, mcs_search_local_points).  Kernels: mcs_project.hip, mcs_frustum.hip.
 #include "mcs_host.h"
 #include <algorithm>
 #include <cstring>
@@ -136,6 +137,117 @@ int mcs_world_to_cam(mcs_ctx* c, const double* MtMc_inv, const mcs_ocam* cams, i
 	launch_world_to_cam(a, c->stream);
 	HIPCHK(hipGetLastError());
 	return st.finish(MCS_OK);
+}
+
+// ---------------------------------------------------------------------------------------------- cTracking::SearchReferencePointsInFrustum
+// frame == nullptr: mcs_frustum (src/cMultiFrame.cpp:218-270 over the loop src/cTracking.cpp:981-999); else the function from :978 on.
+static int local_points_common(mcs_ctx* c, const mcs_local_points* pts, const mcs_rig_view* rig, const double* scales, int nlevels, const mcs_track_state* stt,
+                               const uint8_t* desc, const uint8_t* mask, int stride, const mcs_frame_view* f, double th, double nnratio, int dim, mcs_mem_kind kind,
+                               int32_t* match, int32_t* nmatches, int32_t* nToMatch, int32_t* visibleInc) {
+	const bool search = f != nullptr;
+	if (!c || !pts || !rig || !stt || !nToMatch) return fail(MCS_ERR_INVALID, "null argument");
+	if (search && (!match || !nmatches)) return fail(MCS_ERR_INVALID, "null argument");
+	if (pts->n < 0 || rig->nr_cams < 1 || rig->nr_cams > 32 || (long long)pts->n * rig->nr_cams > 0x7FFFFFFFll / kProjListK) return fail(MCS_ERR_INVALID, "bad sizes");
+	if (nlevels < 1 || nlevels > MCS_MAX_LEVELS) return fail(MCS_ERR_INVALID, "bad sizes");
+	if (search) {
+		if (dim != 16 && dim != 32 && dim != 64) return fail(MCS_ERR_INVALID, "dim must be 16, 32 or 64");
+		if (f->n < 0 || f->n > 65536 || f->nr_cams != rig->nr_cams) return fail(MCS_ERR_INVALID, "bad sizes (frame features must be <= 65536)");
+		if ((mask == nullptr) != (f->mask == nullptr)) return fail(MCS_ERR_INVALID, "masks must be given for both sides or neither");
+		if (stride < dim || f->stride < dim || (stride & 3) || (f->stride & 3)) return fail(MCS_ERR_INVALID, "descriptor stride must be >= dim and a multiple of 4");
+		if (c->asyncSearch) return fail(MCS_ERR_UNSUPPORTED, "the frustum test and the search run in order: switch deferred searches off (mcs_ctx_set_async_search)");
+	}
+	const int np = pts->n, nr = rig->nr_cams;
+	const size_t ns = (size_t)np * nr;
+	if (np > 0) {
+		if (!pts->pos || !pts->normal || !pts->min_dist || !pts->max_dist || !pts->flags || !rig->MtMc_inv || !rig->MtMc || !rig->cams || !scales || !visibleInc ||
+		    !stt->in_view || !stt->proj_x || !stt->proj_y || !stt->level || !stt->view_cos)
+			return fail(MCS_ERR_INVALID, "null argument");
+		if (search && (!desc || !f->width || !f->height || (f->n > 0 && (!f->keys || !f->desc || !f->cam || !f->assigned)))) return fail(MCS_ERR_INVALID, "null argument");
+	}
+	HIPCHK(hipSetDevice(c->device));
+	hipStream_t s = c->stream;
+	if (np == 0) {   // nothing to project: nToMatch = 0, so nothing is searched either (:1001)
+		if (kind == MCS_MEM_HOST) { *nToMatch = 0; if (search) *nmatches = 0; return MCS_OK; }
+		HIPCHK(hipMemsetAsync(nToMatch, 0, 4, s));
+		if (search) HIPCHK(hipMemsetAsync(nmatches, 0, 4, s));
+		return MCS_OK;
+	}
+	if (kind == MCS_MEM_HOST) {   // what the kernels index with (device kind: the caller's contract)
+		for (int k = 0; k < nr; ++k) {
+			if (rig->cams[k].invP_deg < 1 || rig->cams[k].invP_deg > MCS_MAX_POLY) return fail(MCS_ERR_INVALID, "bad polynomial degree");
+			if (rig->cams[k].width < 1 || rig->cams[k].height < 1) return fail(MCS_ERR_INVALID, "bad image size");
+			if (rig->mirror_masks && !rig->mirror_masks[k]) return fail(MCS_ERR_INVALID, "null mirror mask");
+		}
+		if (search)
+			for (int i = 0; i < np; ++i) {
+				if (pts->flags[i] != MCS_LP_SEEN) continue;   // the stale slots SearchByProjection reads
+				for (int k = 0; k < nr; ++k)
+					if (stt->in_view[(size_t)i * nr + k] && (stt->level[(size_t)i * nr + k] < 0 || stt->level[(size_t)i * nr + k] >= nlevels))
+						return fail(MCS_ERR_INVALID, "projection level outside [0, nlevels)");
+			}
+	}
+	if (int r = ctx_join_greedy(c, s)) return r;   // the frame's arrays may come from a search whose greedy pass runs on the side stream
+	// per-slot scratch, in the context's own buffer for either kind (struct mcs_ctx)
+	Carve cv;
+	const size_t oFresh = cv.take(ns), oActive = cv.take(search ? ns : 0), oCam = cv.take(search ? ns * 4 : 0), oCnt = cv.take(search ? ns * 4 : 0),
+	             oLists = cv.take(search ? ns * kProjListK * 8 : 0);
+	HIPCHK(c->lmBuf.reserve(cv.total));
+	uint8_t* base = c->lmBuf.p;
+	FrustumArgs fa{};
+	fa.npoints = np; fa.nrCams = nr; fa.nlevels = nlevels;
+	fa.fresh = base + oFresh;
+	if (search) { fa.active = base + oActive; fa.pcam = (int*)(base + oCam); }
+	ProjArgs a{};
+	Staging st(c, kind == MCS_MEM_HOST);
+	st.in(&fa.pos, pts->pos, (size_t)np * 24); st.in(&fa.normal, pts->normal, (size_t)np * 24); st.in(&fa.minDist, pts->min_dist, (size_t)np * 8);
+	st.in(&fa.maxDist, pts->max_dist, (size_t)np * 8); st.in(&fa.flags, pts->flags, (size_t)np);
+	st.in(&fa.MtMcInv, rig->MtMc_inv, (size_t)nr * 128); st.in(&fa.MtMc, rig->MtMc, (size_t)nr * 128); st.in(&fa.cams, rig->cams, (size_t)nr * sizeof(mcs_ocam));
+	std::vector<const uint8_t*> mp(nr, nullptr);
+	if (kind == MCS_MEM_HOST && rig->mirror_masks) {
+		for (int k = 0; k < nr; ++k) st.in(&mp[k], rig->mirror_masks[k], (size_t)rig->cams[k].width * rig->cams[k].height);
+		st.upload(&fa.masks, mp.data(), sizeof(void*) * nr);   // commit() binds mp[] before it reads the sources
+	} else fa.masks = rig->mirror_masks;
+	st.inout(&fa.inView, stt->in_view, ns); st.inout(&fa.projX, stt->proj_x, ns * 8); st.inout(&fa.projY, stt->proj_y, ns * 8);
+	st.inout(&fa.level, stt->level, ns * 4); st.inout(&fa.viewCos, stt->view_cos, ns * 8);
+	st.out(&fa.visibleInc, visibleInc, (size_t)np * 4); st.out(&fa.nToMatch, nToMatch, 4);
+	if (search) {
+		const size_t nf = f->n, nc = f->nr_cams;
+		a.nproj = (int)ns; a.pstride = stride; a.nfeat = f->n; a.fstride = f->stride; a.nrCams = f->nr_cams;
+		a.th = th; a.ratio = nnratio; a.dim = dim; a.rule = 0; a.cap = kProjListK;
+		a.thHigh = mask ? (int)floor(1.5 * dim) : 3 * dim;   // TH_HIGH_ (src/cORBmatcher.cpp:46-65)
+		a.lists = (unsigned long long*)(base + oLists); a.counts = (int*)(base + oCnt);
+		a.pcam = fa.pcam; a.active = fa.active; a.rowDiv = nr;
+		st.in(&a.pdesc, desc, (size_t)np * stride); st.in(&a.pmask, mask, (size_t)np * stride);
+		st.in(&a.keys, f->keys, nf * sizeof(mcs_keypoint)); st.in(&a.fdesc, f->desc, nf * f->stride); st.in(&a.fmask, f->mask, nf * f->stride); st.in(&a.fcam, f->cam, nf * 4);
+		st.in(&a.width, f->width, nc * 4); st.in(&a.height, f->height, nc * 4);
+		st.inout(&a.assigned, f->assigned, nf);
+		st.out(&a.match, match, ns * 4); st.out(&a.nmatches, nmatches, 4);
+	}
+	st.in(&fa.scales, scales, (size_t)nlevels * 8);
+	if (int r = st.commit()) return r;
+	c->tic("frustum"); launch_frustum(fa, s); c->toc("frustum");
+	if (search) {
+		a.px = fa.projX; a.py = fa.projY; a.vcos = fa.viewCos; a.level = fa.level; a.scales = fa.scales;
+		// grids sized by the host-known slot count; an idle slot leaves at once (k_proj_candidates) and the greedy pass resolves it to -1
+		c->tic("lm_candidates"); launch_proj_candidates(a, s); c->toc("lm_candidates");
+		c->tic("lm_greedy"); launch_proj_greedy(a, s); c->toc("lm_greedy");
+		c->lastResultStream = s;   // every output is complete on the context's stream
+	}
+	HIPCHK(hipGetLastError());
+	return st.finish(MCS_OK);
+}
+
+int mcs_frustum(mcs_ctx* c, const mcs_local_points* pts, const mcs_rig_view* rig, const double* scale_factors, int nlevels, const mcs_track_state* state,
+                mcs_mem_kind kind, int32_t* visible_inc, int32_t* n_to_match) {
+	return local_points_common(c, pts, rig, scale_factors, nlevels, state, nullptr, nullptr, 0, nullptr, 0.0, 0.0, 0, kind, nullptr, nullptr, n_to_match, visible_inc);
+}
+
+int mcs_search_local_points(mcs_ctx* c, const mcs_local_points* pts, const mcs_rig_view* rig, const mcs_track_state* state, const uint8_t* desc, const uint8_t* mask,
+                            int stride, const mcs_frame_view* frame, double th, double nnratio, int dim, mcs_mem_kind kind, int32_t* match, int32_t* nmatches,
+                            int32_t* n_to_match, int32_t* visible_inc) {
+	if (!frame) return fail(MCS_ERR_INVALID, "null argument");
+	return local_points_common(c, pts, rig, frame->scale_factors, frame->nlevels, state, desc, mask, stride, frame, th, nnratio, dim, kind, match, nmatches,
+	                           n_to_match, visible_inc);
 }
 
 int mcs_distinctive_descriptors(mcs_ctx* c, const uint8_t* desc, const uint8_t* mask, int stride, int dim, const int32_t* offsets, int npoints,

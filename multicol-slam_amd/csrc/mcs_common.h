@@ -255,6 +255,9 @@ struct ProjArgs {
 	const double* rad; const int* minLvl; const int* maxLvl;   // explicit window per probe
 	int* owner; int* mdist;                                    // rule 3: vnMatches21 / vMatchedDistance, [nfeat]
 	int* accepted;                                             // rule 3, optional: partner at acceptance time per probe (rotation histogram)
+	// slot form (mcs_search_local_points): the probes are the [map point][camera] slots themselves, most of them idle
+	const uint8_t* active;                                     // optional, [nproj]: a probe with 0 leaves at once with match = -1 (nullptr: every probe is active)
+	int rowDiv;                                                // probe p reads descriptor / mask row p / rowDiv (0: row p)
 };
 
 void launch_projection(const ProjArgs& a, hipStream_t s);
@@ -291,6 +294,38 @@ __device__ __forceinline__ void omni_world_to_img(const OcamDev& cam, double x, 
 	u = uu * cam.c + vv * cam.d + cam.u0;
 	v = uu * cam.e + vv + cam.v0;
 }
+
+// cCamModelGeneral_::isPointInMirrorMask(u, v, 0) (src/cam_model_omni.cpp:163-178): cvRound, the open bounds test, then the level-0 mask (nullptr: bounds only).
+// The one statement for k_world_to_cam (mcs_project.hip) and k_frustum (mcs_frustum.hip).
+__device__ __forceinline__ bool in_mirror_mask(double u, double v, int W, int H, const uint8_t* m) {
+	const int ur = __double2int_rn(u), vr = __double2int_rn(v);
+	if (ur >= W || ur <= 0 || vr >= H || vr <= 0) return false;
+	return !m || m[(size_t)vr * W + ur] > 0;
+}
+
+// ptRot = M * (P, 1) as cv::Matx multiplies: s = 0; s += a(i,k) * b(k) in increasing k (WorldToCamHom_fast, src/cam_system_omni.cpp:114-133)
+__device__ __forceinline__ void matx44_point(const double* M, double x, double y, double z, double r[4]) {
+	const double pt4[4] = {x, y, z, 1.0};
+#pragma unroll
+	for (int row = 0; row < 4; ++row) {
+		double s = 0;
+#pragma unroll
+		for (int k = 0; k < 4; ++k) s += M[4 * row + k] * pt4[k];
+		r[row] = s;
+	}
+}
+
+// cMultiFrame::isInFrustum for every (local map point, camera) slot + the bookkeeping of cTracking::SearchReferencePointsInFrustum (mcs_frustum.hip)
+struct FrustumArgs {
+	const double* pos; const double* normal; const double* minDist; const double* maxDist; const uint8_t* flags; int npoints;   // flags bit0 isBad(), bit1 seen in this frame
+	const double* MtMcInv; const double* MtMc; const mcs_ocam* cams; const uint8_t* const* masks; int nrCams;
+	const double* scales; int nlevels;
+	uint8_t* inView; double* projX; double* projY; int* level; double* viewCos;   // [npoints][nrCams], in/out
+	uint8_t* fresh;               // scratch [npoints][nrCams]: the slot came into view in THIS call
+	int* pcam; uint8_t* active;   // optional (the search follows): camera of slot p; in view && point not bad && nToMatch > 0
+	int* visibleInc; int* nToMatch;
+};
+void launch_frustum(const FrustumArgs& a, hipStream_t s);
 
 struct DistinctArgs {   // cMapPoint::ComputeDistinctiveDescriptors for a batch of map points (mcs_distinct.hip)
 	const uint8_t* desc; const uint8_t* mask; int stride; int dim;

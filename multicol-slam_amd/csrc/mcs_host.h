@@ -79,6 +79,9 @@ struct mcs_ctx {
 	// returns without a host wait while its kernels (and the greedy pass on the side stream) still use it, so it cannot live in a block that the next
 	// call lays out afresh.
 	DevBuf npBuf;
+	// mcs_frustum / mcs_search_local_points: per-slot scratch (fresh / active flags, slot cameras, candidate lists and counts; mcs_capi_window.hip).  Its own
+	// buffer for the same reason: the device-kind call returns while its kernels run, and successive calls reuse it in the order of the context's stream.
+	DevBuf lmBuf;
 	// Second HIP stream for the latency-bound / independent kernels (blur next to FAST+oct-tree, the greedy resolution next to the
 	// following batch's extraction): they leave most CUs idle, so overlapping them with the VALU-bound kernels is free throughput.
 	hipStream_t side = nullptr;    // extraction fork: resize chain + blur beside FAST + oct-tree

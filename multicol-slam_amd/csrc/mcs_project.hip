@@ -59,11 +59,12 @@ __device__ __forceinline__ unsigned long long member_key(const ProjArgs& a, cons
 }
 
 __device__ __forceinline__ int proj_distance(const ProjArgs& a, int p, int i) {
-	const uint32_t* q = reinterpret_cast<const uint32_t*>(a.pdesc + (size_t)p * a.pstride);
+	const size_t prow = a.rowDiv ? (size_t)(p / a.rowDiv) : (size_t)p;   // slot form: every camera's slot of a map point reads the point's one row
+	const uint32_t* q = reinterpret_cast<const uint32_t*>(a.pdesc + prow * a.pstride);
 	const uint32_t* t = reinterpret_cast<const uint32_t*>(a.fdesc + (size_t)i * a.fstride);
 	int acc = 0;
 	if (a.pmask) {
-		const uint32_t* qm = reinterpret_cast<const uint32_t*>(a.pmask + (size_t)p * a.pstride);
+		const uint32_t* qm = reinterpret_cast<const uint32_t*>(a.pmask + prow * a.pstride);
 		const uint32_t* tm = reinterpret_cast<const uint32_t*>(a.fmask + (size_t)i * a.fstride);
 		for (int w = 0; w < a.dim / 4; ++w) { const uint32_t x = q[w] ^ t[w]; acc += __popc(x & qm[w]); acc += __popc(x & tm[w]); }
 		return acc >> 1;
@@ -91,6 +92,10 @@ constexpr int kListK = kProjListK;
 __global__ __launch_bounds__(64) void k_proj_candidates(ProjArgs a) {
 	const int p = blockIdx.x, lane = threadIdx.x;
 	const unsigned long long NONE = ~0ull;
+	if (a.active && !a.active[p]) {   // an idle slot: no member, so the greedy pass resolves it to -1 without reading its list (its level / projection may be unset)
+		if (lane == 0) a.counts[p] = 0;
+		return;
+	}
 	const Window w = make_window(a, p);
 	const int cam = a.pcam[p];
 	unsigned long long loc[kListK];   // this lane's smallest keys, ascending
@@ -267,26 +272,13 @@ __global__ __launch_bounds__(64) void k_world_to_cam(WorldToCamArgs a) {
 	const int i = blockIdx.x * 64 + threadIdx.x;
 	if (i >= a.n) return;
 	const int c = a.pcam[i];
-	const double* M = a.M + 16 * (size_t)c;
-	const double pt4[4] = {a.pts[3 * (size_t)i], a.pts[3 * (size_t)i + 1], a.pts[3 * (size_t)i + 2], 1.0};
 	double r[4];
-#pragma unroll
-	for (int row = 0; row < 4; ++row) {   // cv::Matx product: s = 0; s += a(i,k) * b(k)
-		double s = 0;
-#pragma unroll
-		for (int k = 0; k < 4; ++k) s += M[4 * row + k] * pt4[k];
-		r[row] = s;
-	}
+	matx44_point(a.M + 16 * (size_t)c, a.pts[3 * (size_t)i], a.pts[3 * (size_t)i + 1], a.pts[3 * (size_t)i + 2], r);
 	double u, v;
 	omni_world_to_img(a.cams[c], r[0], r[1], r[2], u, v);
 	a.uv[2 * (size_t)i] = u; a.uv[2 * (size_t)i + 1] = v;
-	const int ur = __double2int_rn(u), vr = __double2int_rn(v);
 	unsigned fl = 0;
-	const int W = a.width[c], H = a.height[c];
-	if (!(ur >= W || ur <= 0 || vr >= H || vr <= 0)) {
-		const uint8_t* m = a.masks ? a.masks[c] : nullptr;
-		if (!m || m[(size_t)vr * W + ur] > 0) fl |= 1u;
-	}
+	if (in_mirror_mask(u, v, a.width[c], a.height[c], a.masks ? a.masks[c] : nullptr)) fl |= 1u;
 	if (r[2] <= 0.0) fl |= 2u;
 	a.flags[i] = (uint8_t)fl;
 }

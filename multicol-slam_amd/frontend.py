@@ -9,6 +9,7 @@
   cMultiKeyFrameDatabase               src/cMultiKeyFrameDatabase.cpp:43-329 (inverted file, relocalisation / loop candidates)
   cSim3Solver (+ cSim3SolverBatch)     src/cSim3Solver.cpp (the RANSAC of cLoopClosing::ComputeSim3, one round over many candidates per call)
   CreateNewMapPoints                   src/cLocalMapping.cpp:223-381 (the mapping thread's neighbour loop: search, triangulation and checks in one call)
+  cMultiFrame.isInFrustum, SearchReferencePointsInFrustum   src/cMultiFrame.cpp:218-270, src/cTracking.cpp:953-1012 (the search step of TrackLocalMap in one call)
 
 Everything numeric runs in libmcs_hip.so on the GPU; this file only shapes inputs/outputs (numpy stands in for cv::Mat).
 """
@@ -246,6 +247,26 @@ class cMultiFrame:
     def ComputeBoW(self):   # src/cMultiFrame.cpp:356-363 (voc = the cORBVocabulary given to the constructor)
         if not getattr(self, "mBowVec", None):
             self.mBowVec, self.mFeatVec = self.mpORBvocabulary.transform(self.all_descriptors(), 4)
+
+    def isInFrustum(self, cam, pMP, viewingCosLimit=0.3, ctx=None):
+        """bool cMultiFrame::isInFrustum(int cam, cMapPoint *pMP, double viewingCosLimit) (src/cMultiFrame.cpp:218-270): one slot through mcs_frustum.
+        Writes mbTrackInView[cam] and, if in view, mTrackProjX/Y[cam], mnTrackScaleLevel[cam], mTrackViewCos[cam] onto pMP.  viewingCosLimit is not applied,
+        as in the reference (:249-250)."""
+        pts = _local_points([pMP], None)
+        pts["flags"][:] = 0                       # the function itself does not look at isBad() / mnLastFrameSeen
+        rig = _rig_arrays(self.camSystem, [cam])
+        st = dict(in_view=np.zeros(1, np.uint8), proj_x=np.zeros(1), proj_y=np.zeros(1), level=np.zeros(1, np.int32), view_cos=np.zeros(1))
+        vis, ntm = np.zeros(1, np.int32), np.zeros(1, np.int32)
+        sc = np.ascontiguousarray(self.mvScaleFactors, np.float64)
+        from ._capi import TrackState
+        ts = TrackState(*[np_ptr(st[k]) for k in ("in_view", "proj_x", "proj_y", "level", "view_cos")])
+        check(lib().mcs_frustum((ctx or default_context()).h, C.byref(pts["struct"]), C.byref(rig["struct"]), np_ptr(sc), len(sc), C.byref(ts), MEM_HOST,
+                                np_ptr(vis), np_ptr(ntm)))
+        pMP.mbTrackInView[cam] = bool(st["in_view"][0])
+        if st["in_view"][0]:
+            pMP.mTrackProjX[cam], pMP.mTrackProjY[cam] = float(st["proj_x"][0]), float(st["proj_y"][0])
+            pMP.mnTrackScaleLevel[cam], pMP.mTrackViewCos[cam] = int(st["level"][0]), float(st["view_cos"][0])
+        return bool(st["in_view"][0])
 
     # flat (all cameras concatenated) descriptor views, the row order of mvKeys
     def all_descriptors(self):
@@ -679,6 +700,95 @@ def CreateNewMapPoints(pKF, vpNeighKFs, checkOrientation=False, featDim=32, havi
                         x3D_all=x3D[lo:lo + n1].copy(), match12=m12[lo:lo + n1].copy(), nmatches=int(nm[s]), fallbacks=int(fb[s]), baseline=float(bl[s]),
                         medianDepth=float(md[s]), skipped=bool(sk[s])))
     return res, v1[:n1].astype(bool)
+
+
+def _local_points(vpMapPoints, frame_id):
+    """mcs_local_points of a list of map points (GetWorldPos, GetNormal, Get{Min,Max}DistanceInvariance, isBad, mnLastFrameSeen) + the arrays behind it"""
+    from ._capi import LP_BAD, LP_SEEN, LocalPoints
+    n = len(vpMapPoints)
+    a = dict(pos=np.ascontiguousarray([np.asarray(m.GetWorldPos(), np.float64)[:3] for m in vpMapPoints], np.float64).reshape(n, 3),
+             normal=np.ascontiguousarray([np.asarray(m.GetNormal(), np.float64)[:3] for m in vpMapPoints], np.float64).reshape(n, 3),
+             min_dist=np.array([m.GetMinDistanceInvariance() for m in vpMapPoints], np.float64),
+             max_dist=np.array([m.GetMaxDistanceInvariance() for m in vpMapPoints], np.float64),
+             flags=np.array([(LP_BAD if m.isBad() else 0) | (LP_SEEN if frame_id is not None and getattr(m, "mnLastFrameSeen", None) == frame_id else 0)
+                             for m in vpMapPoints], np.uint8))
+    a["struct"] = LocalPoints(np_ptr(a["pos"]), np_ptr(a["normal"]), np_ptr(a["min_dist"]), np_ptr(a["max_dist"]), np_ptr(a["flags"]), n)
+    return a
+
+
+def _rig_arrays(camSystem, cams=None):
+    """mcs_rig_view of a cMultiCamSys_ (all cameras, or the listed ones) + the arrays behind it"""
+    from ._capi import RigView
+    cams = list(range(camSystem.GetNrCams())) if cams is None else list(cams)
+    nr = len(cams)
+    a = dict(MtMc_inv=np.ascontiguousarray(np.stack([camSystem.MtMc_inv[c] for c in cams]).reshape(nr, 16)),
+             MtMc=np.ascontiguousarray(np.stack([camSystem.MtMc[c] for c in cams]).reshape(nr, 16)))
+    a["ocs"] = (type(camSystem.cams[0].ocam) * nr)(*[camSystem.cams[c].ocam for c in cams])
+    masks = [camSystem.cams[c].GetMirrorMask(0) for c in cams]
+    a["masks"] = [None if m is None else np.ascontiguousarray(m, np.uint8) for m in masks]
+    a["mp"] = (C.c_void_p * nr)(*[None if m is None else m.ctypes.data for m in a["masks"]])
+    has = all(m is not None for m in a["masks"])
+    a["struct"] = RigView(np_ptr(a["MtMc_inv"]), np_ptr(a["MtMc"]), C.cast(a["ocs"], C.c_void_p), C.cast(a["mp"], C.c_void_p) if has else None, nr)
+    return a
+
+
+def SearchReferencePointsInFrustum(F, vpLocalMapPoints, th=3, nnratio=0.8, featDim=32, havingMasks=False, ctx=None):
+    """int cTracking::SearchReferencePointsInFrustum() (src/cTracking.cpp:953-1012) for frame F (mCurrentFrame) and vpLocalMapPoints (mvpLocalMapPoints).
+    The first loop (:957-976) runs here as written; isInFrustum for every local point in every camera, the nToMatch gate and
+    cORBmatcher(nnratio).SearchByProjection(F, vpLocalMapPoints, th) are ONE device call (mcs_search_local_points).  The tracking fields and
+    IncreaseVisible() counts are written back onto the map points, F.mvpMapPoints is filled, the reference's value is returned.  Map points:
+    GetWorldPos(), GetNormal(), GetMinDistanceInvariance(), GetMaxDistanceInvariance(), isBad(), IncreaseVisible(), mnLastFrameSeen, GetDescriptor() /
+    GetDescriptorMask() (numpy rows) and the per-camera lists mbTrackInView, mTrackProjX, mTrackProjY, mnTrackScaleLevel, mTrackViewCos."""
+    from ._capi import FrameView, TrackState
+    ctx = ctx or default_context()
+    nr = F.camSystem.GetNrCams()
+    nrMatches = 0
+    for i, pMP in enumerate(F.mvpMapPoints):     # :957-976
+        if pMP is None:
+            continue
+        if pMP.isBad():
+            F.mvpMapPoints[i] = None
+            continue
+        pMP.IncreaseVisible()
+        pMP.mnLastFrameSeen = F.mnId
+        pMP.mbTrackInView[int(F.keypoint_to_cam[i])] = False
+        nrMatches += 1
+    n = len(vpLocalMapPoints)
+    if n == 0:
+        return nrMatches
+    pts = _local_points(vpLocalMapPoints, F.mnId)
+    rig = _rig_arrays(F.camSystem)
+    st = dict(in_view=np.array([[bool(v) for v in m.mbTrackInView[:nr]] for m in vpLocalMapPoints], np.uint8),
+              proj_x=np.array([m.mTrackProjX[:nr] for m in vpLocalMapPoints], np.float64), proj_y=np.array([m.mTrackProjY[:nr] for m in vpLocalMapPoints], np.float64),
+              level=np.array([m.mnTrackScaleLevel[:nr] for m in vpLocalMapPoints], np.int32), view_cos=np.array([m.mTrackViewCos[:nr] for m in vpLocalMapPoints], np.float64))
+    ts = TrackState(*[np_ptr(st[k]) for k in ("in_view", "proj_x", "proj_y", "level", "view_cos")])
+    dd = np.ascontiguousarray(np.stack([m.GetDescriptor() for m in vpLocalMapPoints]), np.uint8)
+    mm = np.ascontiguousarray(np.stack([m.GetDescriptorMask() for m in vpLocalMapPoints]), np.uint8) if havingMasks else None
+    keys = np.ascontiguousarray(F.mvKeys)
+    fd = np.ascontiguousarray(F.all_descriptors(), np.uint8)
+    fm = np.ascontiguousarray(F.all_masks(), np.uint8) if havingMasks else None
+    fc = np.ascontiguousarray(F.keypoint_to_cam, np.int32)
+    assigned = np.array([m is not None for m in F.mvpMapPoints] or [0], np.uint8)
+    w, h = np.ascontiguousarray(F.mnMaxX, np.int32), np.ascontiguousarray(F.mnMaxY, np.int32)
+    sc = np.ascontiguousarray(F.mvScaleFactors, np.float64)
+    fv = FrameView(np_ptr(keys), np_ptr(fd), np_ptr(fm), np_ptr(fc), np_ptr(assigned), F.totalN, featDim, nr, np_ptr(w), np_ptr(h), np_ptr(sc), len(sc))
+    match, vis = np.full(n * nr, -1, np.int32), np.zeros(n, np.int32)
+    nm, ntm = np.zeros(1, np.int32), np.zeros(1, np.int32)
+    check(lib().mcs_search_local_points(ctx.h, C.byref(pts["struct"]), C.byref(rig["struct"]), C.byref(ts), np_ptr(dd), np_ptr(mm), featDim, C.byref(fv), float(th),
+                                        float(nnratio), featDim, MEM_HOST, np_ptr(match), np_ptr(nm), np_ptr(ntm), np_ptr(vis)))
+    for i, pMP in enumerate(vpLocalMapPoints):
+        for _ in range(int(vis[i])):             # :995
+            pMP.IncreaseVisible()
+        if pts["flags"][i]:                      # the loop :981-999 never touched this point
+            continue
+        for c in range(nr):
+            pMP.mbTrackInView[c] = bool(st["in_view"][i, c])
+            pMP.mTrackProjX[c], pMP.mTrackProjY[c] = float(st["proj_x"][i, c]), float(st["proj_y"][i, c])
+            pMP.mnTrackScaleLevel[c], pMP.mTrackViewCos[c] = int(st["level"][i, c]), float(st["view_cos"][i, c])
+    for p in np.flatnonzero(match >= 0):
+        F.mvpMapPoints[int(match[p])] = vpLocalMapPoints[int(p) // nr]     # F.mvpMapPoints[bestIdx] = pMP, src/cORBmatcher.cpp:159
+    SearchReferencePointsInFrustum.last = dict(nToMatch=int(ntm[0]), nmatches=int(nm[0]), match=match.reshape(n, nr))
+    return nrMatches + int(nm[0])
 
 
 def DescriptorDistance64(descr_i, descr_j, dim=32, ctx=None):
