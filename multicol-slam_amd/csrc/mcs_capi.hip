@@ -62,7 +62,6 @@ struct GTabInfo {
 
 // The packed device form of a table (mcs_common.h kGDev*): per row [g0 g1 g2 g3] as doubles, [g4 g5 g6 0] as floats (round to nearest).
 static void pack_g_table(const double* tab, uint8_t* out) {
-	if (!MCS_G_PACKED) { memcpy(out, tab, (size_t)kGTabDoubles * sizeof(double)); return; }   // (the device reads the host's rows as they are)
 	for (int r = 0; r < kGRows; ++r) {
 		double* d = reinterpret_cast<double*>(out + (size_t)r * kGDevRowBytes);
 		const double* g = tab + (size_t)r * kGRow;
@@ -234,7 +233,7 @@ static double describe_fast_bound(const mcs_ocam& m, int npoints, const GTabInfo
 	const double aff = 1.0 + std::fabs(m.c) + std::fabs(m.d) + std::fabs(m.e), pp = 8 * u * (std::fabs(m.u0) + std::fabs(m.v0));
 	const int nb = npoints / 128;
 	const double inputs = aff * g.inB * (2 * (2 + 3) * u * 1.01);
-	const double fast = aff * (g.tailU + 16 * u * g.rhoB + 2.01 * u * g.dB + (MCS_G_PACKED ? g.f32U : 0.0));
+	const double fast = aff * (g.tailU + 16 * u * g.rhoB + 2.01 * u * g.dB + g.f32U);
 	const double ref = aff * (12 * u * Sp + 96 * u * S) + pp;
 	const double point = inputs + fast + ref;
 	const double total = 2 * point + (npoints + 2 * nb + 7) * u * 20480.0 + 2 * u * 8192.0 + 2.3283064365386963e-10 * 1.001;
@@ -338,7 +337,6 @@ int mcs_ctx_create(int device, void* hip_stream, mcs_ctx** out) {
 		for (int i = 0; i < 2; ++i) HIPCHK(hipEventCreateWithFlags(&c->evGreedyBuf[i], hipEventDisableTiming));
 
 		HIPCHK(hipEventCreateWithFlags(&c->evFork, hipEventDisableTiming));
-		HIPCHK(hipEventCreateWithFlags(&c->evPyr1, hipEventDisableTiming));
 		HIPCHK(hipEventCreateWithFlags(&c->evPyr, hipEventDisableTiming));
 		HIPCHK(hipEventCreateWithFlags(&c->evBlur, hipEventDisableTiming));
 		HIPCHK(hipEventCreateWithFlags(&c->evMatch, hipEventDisableTiming));
@@ -390,7 +388,7 @@ int mcs_ctx_destroy(mcs_ctx* c) {
 		(void)hipStreamSynchronize(c->side3); (void)hipStreamDestroy(c->side3);
 		(void)hipEventDestroy(c->evLists); (void)hipEventDestroy(c->evGreedyBuf[0]); (void)hipEventDestroy(c->evGreedyBuf[1]);
 		for (int i = 0; i < 4; ++i) if (c->evSearch[i]) (void)hipEventDestroy(c->evSearch[i]);
-		(void)hipEventDestroy(c->evFork); (void)hipEventDestroy(c->evPyr1); (void)hipEventDestroy(c->evPyr); (void)hipEventDestroy(c->evBlur); (void)hipEventDestroy(c->evMatch); (void)hipEventDestroy(c->evGreedy);
+		(void)hipEventDestroy(c->evFork); (void)hipEventDestroy(c->evPyr); (void)hipEventDestroy(c->evBlur); (void)hipEventDestroy(c->evMatch); (void)hipEventDestroy(c->evGreedy);
 		(void)hipEventDestroy(c->evDescFork); (void)hipEventDestroy(c->evDescJoin);
 		(void)hipStreamDestroy(c->side);
 	}
@@ -520,9 +518,9 @@ int mcs_extractor_create(mcs_ctx* ctx, const mcs_extractor_params* p, int width,
 				c.cw = skip ? 0 : (short)std::max(0, (int)maxX - (int)iniX - 2 * detB);
 				c.ch = skip ? 0 : (short)std::max(0, (int)maxY - (int)iniY - 2 * detB);
 				c.slot = slotBase + (i * L.nCols + j) * L.capc;
-				{   // k_fast_cells: tile row = cw + 4 + 3 bytes in dwords, 4-pixel groups per row
-					const int ndw = (c.cw + 4 + 3 + 3) >> 2, gpr = std::max((c.cw + 3) >> 2, 1);
-					c.rowM = (65536 + ndw - 1) / ndw; c.grpM = (65536 + gpr - 1) / gpr;
+				{   // k_fast_cells: tile row = cw + 4 + 3 bytes in dwords
+					const int ndw = (c.cw + 4 + 3 + 3) >> 2;
+					c.rowM = (65536 + ndw - 1) / ndw;
 				}
 				e->cells.push_back(c);
 			}
@@ -975,50 +973,13 @@ static int extract_impl(mcs_extractor* e, int nimg, const uint8_t* images, size_
 			HIPCHK(hipStreamWaitEvent(s, c->evPyr, 0));
 			launch_fast(b, hd, nimg, s, 1, hd.nlevels);
 		} else {
-		static const int sched = getenv("MCS_SCHED") ? atoi(getenv("MCS_SCHED")) : 3;   // launch order; 3 (default) since round 4, the others for A/B
-		if (sched == 5) {   // as 3, with the chain on the MAIN stream: no cross-stream event in front of the first resize and none between the chain and FAST; the blur forks
-			launch_pyramid(b, hd, nimg, s, 1, hd.nlevels);
-			HIPCHK(hipEventRecord(c->evPyr, s));
-			HIPCHK(hipStreamWaitEvent(c->side, c->evPyr, 0));
-			launch_blur(b, hd, nimg, c->side);
-			HIPCHK(hipEventRecord(c->evBlur, c->side));
-			launch_fast(b, hd, nimg, s, 0, hd.nlevels);
-		} else if (sched == 6) {   // FAST alone, the blur beside the oct-trees (latency-bound: one workgroup per image and level, the level-0 ones set its time)
+			// the whole resize chain first, then FAST on all levels in one launch (the blur beside it): the launch orders that start FAST on the first levels earlier lost
 			launch_pyramid(b, hd, nimg, c->side, 1, hd.nlevels);
 			HIPCHK(hipEventRecord(c->evPyr, c->side));
-			HIPCHK(hipStreamWaitEvent(s, c->evPyr, 0));
-			launch_fast(b, hd, nimg, s, 0, hd.nlevels);
-			HIPCHK(hipEventRecord(c->evPyr1, s));
-			HIPCHK(hipStreamWaitEvent(c->side, c->evPyr1, 0));
 			launch_blur(b, hd, nimg, c->side);
 			HIPCHK(hipEventRecord(c->evBlur, c->side));
-		} else {
-		launch_pyramid(b, hd, nimg, c->side, 1, 2);
-		HIPCHK(hipEventRecord(c->evPyr1, c->side));
-		launch_pyramid(b, hd, nimg, c->side, 2, hd.nlevels);
-		HIPCHK(hipEventRecord(c->evPyr, c->side));
-		launch_blur(b, hd, nimg, c->side);
-		HIPCHK(hipEventRecord(c->evBlur, c->side));
-		if (sched == 1) {          // FAST level 0, then every other level in one launch behind the whole chain
-			launch_fast(b, hd, nimg, s, 0, 1);
-			HIPCHK(hipStreamWaitEvent(s, c->evPyr, 0));
-			launch_fast(b, hd, nimg, s, 1, hd.nlevels);
-		} else if (sched == 2) {   // head start for the chain: levels 0 + 1 in one launch once level 1 exists, the rest behind the chain
-			HIPCHK(hipStreamWaitEvent(s, c->evPyr1, 0));
-			launch_fast(b, hd, nimg, s, 0, 2);
-			HIPCHK(hipStreamWaitEvent(s, c->evPyr, 0));
-			launch_fast(b, hd, nimg, s, 2, hd.nlevels);
-		} else if (sched == 3) {   // the whole chain first, then FAST on all levels in one launch (the blur beside it)
 			HIPCHK(hipStreamWaitEvent(s, c->evPyr, 0));
 			launch_fast(b, hd, nimg, s, 0, hd.nlevels);
-		} else {
-		launch_fast(b, hd, nimg, s, 0, 1);           // levels 0 and 1 carry more than half of the FAST work: the rest of the resize chain finishes behind them
-		HIPCHK(hipStreamWaitEvent(s, c->evPyr1, 0));
-		launch_fast(b, hd, nimg, s, 1, 2);
-		HIPCHK(hipStreamWaitEvent(s, c->evPyr, 0));
-		launch_fast(b, hd, nimg, s, 2, hd.nlevels);
-		}
-		}
 		}
 		// (holding the previous step's deferred matcher back until here, so that it runs beside the oct-tree / orientation / descriptor kernels instead of
 		// beside FAST and the resize chain: measured, 2.22 -> 2.55 ms per step — the descriptor kernel on the critical path suffers more from the company)
@@ -1315,7 +1276,7 @@ int mcs_describe_fast_table_packed(const mcs_ocam* cam, void* packed, int* row_b
 	const GTabInfo g = build_g_table(*cam, tab.data());
 	if (packed) pack_g_table(tab.data(), reinterpret_cast<uint8_t*>(packed));
 	if (row_bytes) *row_bytes = kGDevRowBytes;
-	if (f32_term) *f32_term = MCS_G_PACKED ? g.f32U : 0.0;   // (0: this build's device rows are the doubles themselves)
+	if (f32_term) *f32_term = g.f32U;
 	return MCS_OK;
 }
 

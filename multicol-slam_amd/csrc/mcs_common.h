@@ -58,7 +58,7 @@ struct PyrDesc {
 };
 
 struct CellInfo { short level; short x0, y0; short cw, ch; short pad; int slot; int rowM, grpM; };  // processed region [x0,x0+cw) x [y0,y0+ch) in level ROI coords;
-// rowM = ceil(2^16 / dwords per staged tile row), grpM = ceil(2^16 / 4-pixel groups per row): the FAST kernel's divisions by multiplication
+// rowM = ceil(2^16 / dwords per staged tile row): the FAST kernel's division by multiplication; grpM is unused padding now (it keeps sizeof(CellInfo))
 
 // bilinear resize tables (Appendix A.1), one entry per destination column / row of a level
 struct ResizeTap { short ofs; short a0; short a1; short pad; };
@@ -89,11 +89,9 @@ struct OcamDev {
 constexpr int kGM = MCS_G_M, kGDeg = MCS_G_DEG, kGE0 = MCS_G_E0, kGE1 = MCS_G_E1, kGRows = (kGE1 - kGE0) << kGM, kGRow = kGDeg + 1, kGTabDoubles = kGRows * kGRow;
 // ... as the HOST builds it (kGRow doubles per row).  The DEVICE reads a packed form (round 6): 48-byte rows in three 16-byte slots, [g0 g1] [g2 g3] doubles and
 // [g4 g5 g6 0] floats — three ds_read_b128 per row from LDS instead of seven 8-byte loads; the float tail's roundings are bounded by GTabInfo.f32U (mcs_capi.hip).
-#ifndef MCS_G_PACKED
-#define MCS_G_PACKED 1   // 1: the packed rows (three ds_read_b128 per gather: 27 % fewer LDS-array cycles per keypoint).  0 (A/B): rows of kGRow doubles, which the compiler reads as
-#endif                   // three ds_read2_b64 + one ds_read_b64 (half rate).  Round 6: 0.456 against 0.493 ms once the kernel no longer spills (profiles/NOTES.md).
-static_assert(!MCS_G_PACKED || kGDeg == 6, "the packed device rows hold degree 6");
-constexpr int kGDevRowBytes = MCS_G_PACKED ? 48 : kGRow * 8, kGDevDoubles = kGRows * kGDevRowBytes / 8;
+// (Against rows of kGRow doubles, which the compiler reads as three ds_read2_b64 + one ds_read_b64 at half rate: 27 % fewer LDS-array cycles per keypoint, 0.456 against 0.493 ms.)
+static_assert(kGDeg == 6, "the packed device rows hold degree 6");
+constexpr int kGDevRowBytes = 48, kGDevDoubles = kGRows * kGDevRowBytes / 8;
 // The table starts at s = 2^kGE0, i.e. 1/32 pixel from the optical axis: G has a sqrt-type branch point at s = 0 (rho(theta) of a fitted backward polynomial
 // does not vanish exactly on the axis), so only log-spaced bins reach down there.  One keypoint in 200 has the axis inside its pattern's footprint, and of
 // those one in 300 a point within 1/32 px of it: that keypoint takes the exact pass.  (Starting the table at s = 16 sent 1 % of all keypoints there, at

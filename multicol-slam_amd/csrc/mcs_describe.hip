@@ -207,10 +207,9 @@ struct Sampler {
 	const uint8_t* raw; int rstride;
 	int w, h;
 	const uint8_t* patch; int prow, pcol;   // LDS patch and the level coordinates of its origin
-	template <int PITCH = kPatchPitch>
 	__device__ __forceinline__ int at(int r, int c) const {
 		const unsigned pr = (unsigned)(r - prow), pc = (unsigned)(c - pcol);
-		if (pr < (unsigned)kPatchRows && pc < (unsigned)kPatchRows) return patch[pr * PITCH + pc];
+		if (pr < (unsigned)kPatchRows && pc < (unsigned)kPatchRows) return patch[pr * kPatchPitch + pc];
 		if ((unsigned)r < (unsigned)h && (unsigned)c < (unsigned)w) return blur[(size_t)r * bstride + c];
 		r = r < -kEdge ? -kEdge : (r > h + kEdge - 1 ? h + kEdge - 1 : r);   // clamp to the bordered buffer
 		c = c < -kEdge ? -kEdge : (c > w + kEdge - 1 ? w + kEdge - 1 : c);
@@ -237,16 +236,11 @@ struct Sampler {
 #ifndef MCS_ABLATE
 #define MCS_ABLATE 0   // A/B experiments only: 1 skip the sequential mean, 2 skip the omni model, 4 skip sampling
 #endif
-#ifndef MCS_MERGE_CHAINS
-#define MCS_MERGE_CHAINS 0   // A/B only.  1 = mdBRIEF keeps all three distorted patterns in LDS and runs their six coordinate sums as ONE
-                             // chain (lanes 0..5): 1024 fewer dependent adds per keypoint, but 26.5 KB LDS per wave (6 waves/CU instead
-                             // of 12) and 186 VGPRs; measured 3.00 ms vs 2.93 ms per 192 images, so the separate chains stay.
-#endif
 // coordinate buffers per wave: [pattern][x | y][npoints] doubles
 // The y array starts 2 doubles after the end of the x array: x[p] and y[p] are read in the same ds_read (even / odd lanes) and must not
 // share LDS banks (an offset of exactly npoints doubles = a multiple of 256 B made every read of the sum chain a 2-way bank conflict).
 __host__ __device__ constexpr int pat_doubles(int npoints) { return 2 * npoints + 2; }
-__host__ __device__ constexpr int coord_bytes(int mode, int npoints) { return mode == 0 ? 0 : (mode == 2 && MCS_MERGE_CHAINS ? 3 : 1) * pat_doubles(npoints) * 8; }
+__host__ __device__ constexpr int coord_bytes(int mode, int npoints) { return mode == 0 ? 0 : pat_doubles(npoints) * 8; }
 
 // Everything a keypoint needs before its descriptor: slot -> (level, position), the output row, the blurred patch in LDS, orientation (E5), the
 // keypoint record and ray (E8/E9).  Shared by the exact pass (describe_wave) and the fast pass (k_describe_fast); false = this wave has no keypoint.
@@ -421,7 +415,6 @@ __device__ __forceinline__ void describe_wave(const ExtractBuffers& b, int waves
 	constexpr int NP = 128 * NB;              // pattern points = 2*8*descSize
 	constexpr int CH = NP / (2 * NB);         // chain elements folded into one point iteration (= 64)
 	constexpr int YO = NP + 2;                // offset of the y array inside a pattern buffer (bank shift, see pat_doubles)
-	constexpr int PD = pat_doubles(NP);
 	double* buf = reinterpret_cast<double*>(reinterpret_cast<uint8_t*>(lds) + (size_t)wave * (coord_bytes(MODE, NP) + kPatchBytes));   // [pattern][x | y][NP] distorted coordinates
 	const OcamDev& cam = b.cams[img];
 	// The camera is the same for the whole wave: pull the backward polynomial and the affine terms into SGPRs ONCE.  (The
@@ -515,30 +508,16 @@ __device__ __forceinline__ void describe_wave(const ExtractBuffers& b, int waves
 #pragma unroll
 	for (int j = 0; j < NB; ++j) { bitsMain[j] = 0ull; agree[j] = ~0ull; }
 	constexpr int npat = MODE == 2 ? 3 : 1;
-	constexpr bool merged = MODE == 2 && MCS_MERGE_CHAINS;
-	double sumAll = 0.0, tie = 0.0;
-	if (merged) {
-		// all three patterns first, then ONE dependent add chain: lane 2*pat + c accumulates coordinate c of pattern pat (each of the
-		// six sums still runs p = 0..NP-1 in the reference's order; the other lanes repeat lane 0's work)
-#pragma unroll
-		for (int pat = 0; pat < npat; ++pat) pass(true, pat == 0 ? ang0 : (pat == 1 ? ang1 : ang2), buf + pat * PD, false, buf, sumAll);
-		if (!(MCS_ABLATE & 1)) {
-			const int cl = lane < 2 * npat ? lane : 0;
-			const double* arr = buf + (cl >> 1) * PD + (cl & 1) * YO;
-#pragma unroll 16
-			for (int p = 0; p < NP; ++p) sumAll += arr[p];
-		}
-	}
+	double tie = 0.0;
+	// (mdBRIEF's three patterns in LDS together and their six sums as ONE chain: 1024 fewer dependent adds, but 26.5 KB of LDS per wave and 186 registers — 3.00 against 2.93 ms per 192 images)
 #pragma unroll
 	for (int pat = 0; pat < npat; ++pat) {
-		double* cur = merged ? buf + pat * PD : buf;
-		double sum = sumAll;
-		if (!merged) {
-			pass(true, pat == 0 ? ang0 : (pat == 1 ? ang1 : ang2), cur, false, cur, sum);
-			pass(false, 0.0, cur, true, cur, sum);
-		}
+		double* cur = buf;
+		double sum = 0.0;
+		pass(true, pat == 0 ? ang0 : (pat == 1 ? ang1 : ang2), cur, false, cur, sum);
+		pass(false, 0.0, cur, true, cur, sum);
 		const double mean = sum / (double)NP;
-		const double meanX = __shfl(mean, merged ? 2 * pat : 0), meanY = __shfl(mean, merged ? 2 * pat + 1 : 1);
+		const double meanX = __shfl(mean, 0), meanY = __shfl(mean, 1);
 #pragma unroll
 		for (int j = 0; j < NB; ++j) {
 			const int k = j * 64 + lane;
@@ -761,12 +740,9 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
 // sum, like the shuffle form (describe_fast_bound counts its roundings, not its order).
 template <int CTRL>
 __device__ __forceinline__ double dpp_f64(double v) {
-#ifndef MCS_DPP_OLD_SELF
-#define MCS_DPP_OLD_SELF 0   // 1 (round 5, A/B): old = the source itself — the compiler then copies the source in front of every v_mov_b32_dpp (two extra moves per step)
-#endif
 	const int vl = __double2loint(v), vh = __double2hiint(v);   // a rotation inside the rows of 16: every lane has a source, so with bound_ctrl the old value is dead and no copy is made
-	const int lo = MCS_DPP_OLD_SELF ? __builtin_amdgcn_update_dpp(vl, vl, CTRL, 0xF, 0xF, false) : __builtin_amdgcn_update_dpp(0, vl, CTRL, 0xF, 0xF, true);
-	const int hi = MCS_DPP_OLD_SELF ? __builtin_amdgcn_update_dpp(vh, vh, CTRL, 0xF, 0xF, false) : __builtin_amdgcn_update_dpp(0, vh, CTRL, 0xF, 0xF, true);
+	const int lo = __builtin_amdgcn_update_dpp(0, vl, CTRL, 0xF, 0xF, true);   // (old = the source itself: the compiler copies the source in front of every v_mov_b32_dpp, two extra moves per step)
+	const int hi = __builtin_amdgcn_update_dpp(0, vh, CTRL, 0xF, 0xF, true);
 	return __hiloint2double(hi, lo);
 }
 __device__ __forceinline__ void wave_sum2_f64(double sx, double sy, double& totx, double& toty) {
@@ -789,22 +765,18 @@ __device__ __forceinline__ void wave_sum2_f64(double sx, double sy, double& totx
 // one pattern point through the fast arithmetic; `bad` collects points the table does not cover.  (Requesting the row of point t + 1 before the Horner
 // chain of point t — a hand-made software pipeline — was built and measured: 0.712 against 0.705 ms, not kept.)
 struct FastCam { double c, d, e; };
-#ifndef MCS_FAST_CLAMP
-#define MCS_FAST_CLAMP 1   // clamp the row index before the LDS gather (0, A/B: an unclamped gather measured the same, 0.594 against 0.602 ms)
-#endif
 // `top` collects the largest row index seen (unsigned: below the table, negative, NaN and Inf all come out huge): one compare per pattern instead of one per
 // point; the gather itself reads the clamped row, its value is never used for such a point (the keypoint goes to the exact pass).
-template <bool CLAMP, class Tab>
+template <class Tab>
 __device__ __forceinline__ void fast_w2i(const FastCam& C, Tab tab, double xr, double yr, double& u, double& v, unsigned& top) {
 	const double s = __builtin_fma(xr, xr, yr * yr);
 	const unsigned hi = (unsigned)__double2hiint(s), lo = (unsigned)__double2loint(s);
 	const unsigned idx = (hi >> (20 - kGM)) - (unsigned)((1023 + kGE0) << kGM);            // (exponent - kGE0) * 2^kGM + top kGM mantissa bits
 	top = max(top, idx);
-	unsigned row = CLAMP || MCS_FAST_CLAMP ? (idx < (unsigned)kGRows ? idx : (unsigned)(kGRows - 1)) : (idx & 0xFFFFFFu);   // 24 bits: v_mad_u32_u24 forms the byte offset
+	unsigned row = idx < (unsigned)kGRows ? idx : (unsigned)(kGRows - 1);   // (an unclamped gather measured the same: 0.594 against 0.602 ms)
 	if (MCS_FAST_ABLATE & 16) row = 0;   // A/B: every lane reads the same row (LDS broadcast: no bank conflicts, no gather)
 	const double frac = __hiloint2double((int)((hi & ((1u << (20 - kGM)) - 1u)) | 0x3FF00000u), (int)lo);   // 1 + the mantissa bits below the bin index
 	const double tau = frac - (1.0 + 1.0 / (double)(2 << kGM));                           // exact
-#if MCS_G_PACKED
 	// The row (mcs_common.h kGDev*): 48 bytes in three 16-byte slots — [g0 g1] [g2 g3] as doubles, [g4 g5 g6 0] as floats.  From LDS that is three ds_read_b128
 	// (12 array cycles per wave; the 56-byte rows of doubles went as three ds_read2_b64 + one ds_read_b64: 26, and collided in rows r, r + 16), and rows 16 bytes
 	// aligned at a stride of three slots collide only for r = r' mod 16 within a 16-lane group.  The tail g4 + g5 tau + g6 tau^2 is evaluated in float (its share
@@ -820,15 +792,6 @@ __device__ __forceinline__ void fast_w2i(const FastCam& C, Tab tab, double xr, d
 	G = __builtin_fma(G, tau, g23.x);
 	G = __builtin_fma(G, tau, g01.y);
 	G = __builtin_fma(G, tau, g01.x);
-#else
-	const auto g = tab + row * kGRow;
-	double gc[kGRow];
-#pragma unroll
-	for (int i = 0; i < kGRow; ++i) gc[i] = g[i];
-	double G = gc[kGDeg];
-#pragma unroll
-	for (int i = kGDeg - 1; i >= 0; --i) G = __builtin_fma(G, tau, gc[i]);
-#endif
 	const double uu = xr * G, vv = yr * G;
 	u = __builtin_fma(uu, C.c, vv * C.d);
 	v = __builtin_fma(uu, C.e, vv);
@@ -939,146 +902,6 @@ __global__ __launch_bounds__(256) void k_orient_b(ExtractBuffers b, int wavesPer
 constexpr int kFastBlocks = MCS_FAST_BLOCKS;
 static_assert(kSlotAlign % kFastWaves == 0, "a group's keypoint slots must belong to one image");
 
-// The fast pass's sampler: the LDS patch serves practically every sample; the general path (blurred level / bordered raw level) looks its level up only
-// when it is taken, so that none of it occupies registers in the hot loop.
-struct LazySampler {
-	const ExtractBuffers* b; int img, level;
-	const uint8_t* patch;
-	// `reach` collects offset + 4096 of every sample that takes the general path: the caller sends the keypoint to the exact pass unless all stay below 8192.
-	// (A sample inside the patch is within +-21: nothing to collect on the fast path — and an offset outside [-4096, 4096), NaN included, can never pass for inside.)
-	// one sample at offset (dy, dx) from the keypoint through the general path (blurred level / bordered raw level; the patch too, for a lane whose own point is inside)
-	__device__ __forceinline__ int sample(int dy, int dx, int row, int col) const {
-		const PyrDesc& d = *b->desc;
-		const LevelInfo& L = d.lv[level];
-		Sampler sm;
-		int rstride;
-		sm.raw = level_ptr(*b, d, img, level, &rstride);
-		sm.rstride = rstride;
-		sm.blur = b->blur + (size_t)img * d.pyrBytes + L.off; sm.bstride = L.stride;
-		sm.w = L.w; sm.h = L.h;
-		sm.patch = patch; sm.prow = row - kPatchR; sm.pcol = col - kPatchR;
-		return sm.at<kFPitch>(row + dy, col + dx);
-	}
-	__device__ __forceinline__ void pair(int row, int col, int dy0, int dx0, int dy1, int dx1, int& t0, int& t1, unsigned& reach) const {
-		const unsigned r0 = (unsigned)(dy0 + kPatchR), c0 = (unsigned)(dx0 + kPatchR), r1 = (unsigned)(dy1 + kPatchR), c1 = (unsigned)(dx1 + kPatchR);
-		const bool inside = max(max(r0, c0), max(r1, c1)) < (unsigned)kPatchRows;
-		if (!__any(!inside)) {
-			// explicitly LDS: left as loads through the generic `patch` pointer, the compiler merges this load with the general path's (below) into ONE flat load
-			// behind the branch — slower than ds_read_u8, and every flat load waits on vmcnt(0), i.e. for the patch requested for the NEXT keypoint
-			typedef const __attribute__((address_space(3))) uint8_t lds_byte;
-			lds_byte* const pl = (lds_byte*)patch;
-			t0 = pl[r0 * kFPitch + c0];
-			t1 = pl[r1 * kFPitch + c1];
-		} else {
-			reach |= (unsigned)(dy0 + 4096) | (unsigned)(dx0 + 4096) | (unsigned)(dy1 + 4096) | (unsigned)(dx1 + 4096);
-			const PyrDesc& d = *b->desc;
-			const LevelInfo& L = d.lv[level];
-			Sampler sm;
-			int rstride;
-			sm.raw = level_ptr(*b, d, img, level, &rstride);
-			sm.rstride = rstride;
-			sm.blur = b->blur + (size_t)img * d.pyrBytes + L.off; sm.bstride = L.stride;
-			sm.w = L.w; sm.h = L.h;
-			sm.patch = patch; sm.prow = row - kPatchR; sm.pcol = col - kPatchR;
-			t0 = sm.at<kFPitch>(row + dy0, col + dx0);
-			t1 = sm.at<kFPitch>(row + dy1, col + dx1);
-			asm volatile("" : "+v"(t0), "+v"(t1));   // (keeps the two paths' loads apart, see above)
-		}
-	}
-};
-
-// One keypoint of the fast pass by one wave: the patch is in LDS, (ukx, uky) and the pattern angles' cos / sin come from k_orient_b.  Returns false if the
-// keypoint has to take the exact pass (a coordinate in the guard band, a point outside the table, out of range).
-// patD: this lane's pattern points as doubles in LDS — point t at patD[64 t] = (x, y): one ds_read_b128 where unpacking the packed bytes took four VALU instructions
-// per point and pattern (hoisted out of the loops the 4 NB doubles would cost 8 NB registers)
-// ahead(): the walk's requests for the keypoints to come, issued right behind this keypoint's first LDS read (k_describe_fast says why there).
-template <int MODE, int NB, class Ahead>
-__device__ __forceinline__ bool fast_keypoint(const ExtractBuffers& b, const FastCam& C, const double* tabLds, const LazySampler& sm, int row, int col,
-                                              double ukx, double uky, const double (&axc)[3], const double (&ays)[3], const double2* patD,
-                                              unsigned long long (&bitsMain)[NB], unsigned long long (&agree)[NB], Ahead&& ahead) {
-	constexpr int NP = 128 * NB;
-	// The rounding and its guard in fixed point: y = coordinate - mean + 1.5 * 2^20 + 0.5 lies in [2^20, 2^21) where one unit of the high word is one pixel and
-	// the low word is the fraction in units of 2^-32.  floor(y) is the rounded offset (ties are excluded by the guard), the fraction within guardUnits of 0 /
-	// 2^32 means the coordinate is within the band of a tie, and high word - hiword(1.5 * 2^20 - 4096) is offset + 4096, in [0, 8192) iff |offset| <= 4096
-	// (NaN, Inf and anything outside the binade give a huge value).  Costs two roundings of 2^-33 (describe_fast_bound adds them).
-	const double kFix = 1572864.5;                 // 1.5 * 2^20 + 0.5
-	const unsigned kHiBase = 0x4137F000u;          // high word of 1.5 * 2^20 - 4096
-	const unsigned guardUnits = (unsigned)__builtin_ceil(b.guardEps * 4294967296.0);
-#pragma unroll
-	for (int j = 0; j < NB; ++j) { bitsMain[j] = 0ull; agree[j] = ~0ull; }
-	constexpr int npat = MODE == 2 ? 3 : 1;
-#pragma unroll
-	for (int pat = 0; pat < npat; ++pat) {
-		const double ax = axc[pat], ay = ays[pat];
-		double u[2 * NB], v[2 * NB];
-		double sumx = 0.0, sumy = 0.0;
-		bool bad = false;
-		unsigned top = 0;
-		// opaque per pattern — the points are read again for every pattern, not held across them — as an LDS byte offset: an opaque generic pointer would make
-		// these flat loads, which count on vmcnt too and would wait for the patch just requested
-		typedef double f64x2 __attribute__((ext_vector_type(2)));
-		typedef const __attribute__((address_space(3))) f64x2 lds_f64x2;
-		unsigned pdo = (unsigned)(uintptr_t)(lds_f64x2*)patD;
-		asm volatile("" : "+v"(pdo));
-		lds_f64x2* const pd = (lds_f64x2*)(uintptr_t)pdo;
-		auto rotate = [&](int t, double& xr, double& yr) {
-			const f64x2 p = pd[64 * t];
-			if (pat == 0 && t == 0) ahead();
-			xr = __builtin_fma(p.x, ax, __builtin_fma(-p.y, ay, ukx));
-			yr = __builtin_fma(p.x, ay, __builtin_fma(p.y, ax, uky));
-		};
-		if (MCS_FAST_ABLATE & 2) {
-#pragma unroll
-			for (int t = 0; t < 2 * NB; ++t) { rotate(t, u[t], v[t]); sumx += u[t]; sumy += v[t]; }
-		} else {
-#pragma unroll
-			for (int t = 0; t < 2 * NB; ++t) {
-				double xr, yr;
-				rotate(t, xr, yr);
-				fast_w2i<false>(C, tabLds, xr, yr, u[t], v[t], top);
-				sumx += u[t]; sumy += v[t];
-				if ((t & (MCS_FAST_FENCE - 1)) == MCS_FAST_FENCE - 1) __builtin_amdgcn_sched_barrier(0);   // at most MCS_FAST_FENCE point evaluations in flight (registers)
-			}
-		}
-		double totx, toty;
-		wave_sum2_f64(sumx, sumy, totx, toty);
-		const double meanX = totx * (1.0 / (double)NP), meanY = toty * (1.0 / (double)NP);
-		bad |= top >= (unsigned)kGRows;   // a point below / above the table, NaN, Inf
-		bad |= !(fabs(meanX) < 16384.0) || !(fabs(meanY) < 16384.0);
-		// the guard's half-width is folded into the addend: the low word of y then reads (fraction + g) mod 2^32, and "within the band of a tie" is low word < 2g —
-		// no integer add per coordinate.  (Where the fraction + g wraps, the carry lands in the high word: such a coordinate is in the band, its keypoint leaves
-		// for the exact pass and the offset is never used.)  The smallest low word of the pattern is kept (v_min3_u32) and compared once.
-		const double gAdd = (double)guardUnits * (1.0 / 4294967296.0);
-		const double cmx = (kFix - meanX) + gAdd, cmy = (kFix - meanY) + gAdd;   // exact: one unit of the last place of kFix - mean is 2^-32 (or more)
-		unsigned reach = 0, minlo = 0xFFFFFFFFu;
-		// rounding, guard and the pair's test in one sweep (the samples of a keypoint that turns out to need the exact pass are wasted, nothing else: its
-		// bits are not written)
-#pragma unroll
-		for (int j = 0; j < NB; ++j) {
-			int ix[2], iy[2];
-#pragma unroll
-			for (int e = 0; e < 2; ++e) {
-				const double yx = u[2 * j + e] + cmx, yy = v[2 * j + e] + cmy;
-				const unsigned hx = (unsigned)__double2hiint(yx) - kHiBase, hy = (unsigned)__double2hiint(yy) - kHiBase;
-				if (!(MCS_FAST_ABLATE & 4)) minlo = min(minlo, min((unsigned)__double2loint(yx), (unsigned)__double2loint(yy)));
-				ix[e] = (int)hx - 4096; iy[e] = (int)hy - 4096;
-			}
-			int t0 = ix[0], t1 = iy[1];
-			if (!(MCS_FAST_ABLATE & 1)) sm.pair(row, col, iy[0], ix[0], iy[1], ix[1], t0, t1, reach);
-			const unsigned long long bits = __ballot(t0 < t1);
-			if (pat == 0) bitsMain[j] = bits;
-			else agree[j] &= ~(bits ^ bitsMain[j]);
-		}
-		if (!(MCS_FAST_ABLATE & 4)) bad |= minlo < 2u * guardUnits;
-		if (!(MCS_FAST_ABLATE & 4)) bad |= reach >= 8192u;
-		if (__any(bad)) return false;
-	}
-	return true;
-}
-
-#ifndef MCS_FAST_UNIQ
-#define MCS_FAST_UNIQ 1   // 1: the pattern's distinct points (round 5, UPat above); 0: every point of the pattern (round 4's fast_keypoint), kept for A/B
-#endif
 // The LDS tables of the distinct-point form as one workgroup sees them, and this wave's byte array
 struct UTabs {
 	const double2* upat; const double* uw; const uint32_t* gidx;   // already offset by the lane (upat + lane, uw + lane, gidx + lane * NB)
@@ -1090,7 +913,7 @@ __host__ __device__ constexpr size_t gidx_bytes(int nb) { return (size_t)64 * 2 
 __host__ __device__ constexpr size_t uvals_bytes(int nb) { return (size_t)(nb == 2 ? 4 : nb == 4 ? 6 : 9) * 64; }
 
 // One keypoint of the fast pass by one wave, distinct-point form.  Per pattern: R rounds of the omni model (lane l, round t: distinct point t * 64 + l), the
-// weighted wave sum for the mean, rounding + guard per DISTINCT point in the fixed-point form of fast_keypoint, ONE patch byte per distinct point written to
+// weighted wave sum for the mean, rounding + guard per DISTINCT point in fixed point (below), ONE patch byte per distinct point written to
 // vals[], then every lane gathers the 2 NB bytes of its own pairs.  LDS operations of one wave execute in order, so the gather sees the bytes written just
 // before it by the other lanes (and the next pattern's bytes land behind this pattern's gather); nothing here needs a barrier.
 // The whole keypoint is ONE basic block: the measured bound of this kernel is not instruction issue but the dependent chains of a pattern (the wave sum's 22
@@ -1104,10 +927,17 @@ __device__ __forceinline__ bool fast_keypoint_u(const ExtractBuffers& b, const F
                                                 double ukx, double uky, const double (&axc)[3], const double (&ays)[3], const UTabs& T,
                                                 unsigned long long (&bitsMain)[NB], unsigned long long (&agree)[NB], Ahead&& ahead) {
 	constexpr int NP = 128 * NB, R = UPat<NB>::R, RW = UPat<NB>::RW;
-	const double kFix = 1572864.5;                                       // 1.5 * 2^20 + 0.5 (fast_keypoint)
+	// The rounding and its guard in fixed point: y = coordinate - mean + 1.5 * 2^20 + 0.5 lies in [2^20, 2^21) where one unit of the high word is one pixel and
+	// the low word is the fraction in units of 2^-32.  floor(y) is the rounded offset (ties are excluded by the guard), the fraction within guardUnits of 0 /
+	// 2^32 means the coordinate is within the band of a tie (NaN, Inf and anything outside the binade give a huge high word).  Costs two roundings of 2^-33
+	// (describe_fast_bound adds them).
+	const double kFix = 1572864.5;                                       // 1.5 * 2^20 + 0.5
 	const unsigned kHiPatch = 0x4137F000u + 4096u - (unsigned)kPatchR;   // high word of y minus this = offset + kPatchR: the patch row / column
 	const unsigned guardUnits = (unsigned)__builtin_ceil(b.guardEps * 4294967296.0);
-	const double gAdd = (double)guardUnits * (1.0 / 4294967296.0);       // the guard's half-width folded into the addend (fast_keypoint)
+	// the guard's half-width is folded into the addend: the low word of y then reads (fraction + g) mod 2^32, and "within the band of a tie" is low word < 2g —
+	// no integer add per coordinate.  (Where the fraction + g wraps, the carry lands in the high word: such a coordinate is in the band, its keypoint leaves
+	// for the exact pass and the offset is never used.)  The smallest low word of the keypoint is kept and compared once.
+	const double gAdd = (double)guardUnits * (1.0 / 4294967296.0);
 #pragma unroll
 	for (int j = 0; j < NB; ++j) { bitsMain[j] = 0ull; agree[j] = ~0ull; }
 	constexpr int npat = MODE == 2 ? 3 : 1;
@@ -1117,7 +947,8 @@ __device__ __forceinline__ bool fast_keypoint_u(const ExtractBuffers& b, const F
 	typedef const __attribute__((address_space(3))) uint32_t lds_u32;
 	typedef __attribute__((address_space(3))) uint8_t lds_u8;
 	typedef const __attribute__((address_space(3))) uint8_t lds_cu8;
-	// opaque (as LDS byte offsets: see fast_keypoint): the tables are read again for every keypoint, nothing derived from them is held across the walk
+	// opaque, as LDS byte offsets (an opaque generic pointer would make these flat loads, which count on vmcnt too and would wait for the patch just requested):
+	// the tables are read again for every keypoint, nothing derived from them is held across the walk
 	unsigned pdo = (unsigned)(uintptr_t)(lds_f64x2*)T.upat, pwo = (unsigned)(uintptr_t)(lds_f64*)T.uw, pgo = (unsigned)(uintptr_t)(lds_u32*)T.gidx;
 	unsigned pvo = (unsigned)(uintptr_t)(lds_u8*)T.vals, plo = (unsigned)(uintptr_t)(lds_cu8*)patch;
 	int lane = threadIdx.x & 63;
@@ -1141,7 +972,7 @@ __device__ __forceinline__ bool fast_keypoint_u(const ExtractBuffers& b, const F
 			if (pat == 0 && t == 0) ahead();
 			const double xr = __builtin_fma(p.x, ax, __builtin_fma(-p.y, ay, ukx));
 			const double yr = __builtin_fma(p.x, ay, __builtin_fma(p.y, ax, uky));
-			if (MCS_FAST_ABLATE & 2) { u[t] = xr; v[t] = yr; } else fast_w2i<false>(C, tabLds, xr, yr, u[t], v[t], top);
+			if (MCS_FAST_ABLATE & 2) { u[t] = xr; v[t] = yr; } else fast_w2i(C, tabLds, xr, yr, u[t], v[t], top);
 			if (t < RW) { const double w = pw[64 * t]; sumx = __builtin_fma(w, u[t], sumx); sumy = __builtin_fma(w, v[t], sumy); }
 			else { sumx += u[t]; sumy += v[t]; }
 			constexpr int kFence = R > 6 ? 2 : MCS_FAST_FENCE;   // at most kFence point evaluations in flight (registers; nine rounds hold 36 for u, v alone)
@@ -1160,14 +991,11 @@ __device__ __forceinline__ bool fast_keypoint_u(const ExtractBuffers& b, const F
 			const unsigned pc = (unsigned)__double2hiint(yx) - kHiPatch, pr = (unsigned)__double2hiint(yy) - kHiPatch;   // unsigned: left of / above the patch, NaN: huge
 			if (!(MCS_FAST_ABLATE & 4)) minlo = min(minlo, min((unsigned)__double2loint(yx), (unsigned)__double2loint(yy)));
 			maxrc = max(maxrc, max(pr, pc));
-#ifndef MCS_PATCH_OFF_MAD
-#define MCS_PATCH_OFF_MAD 0   // 1 (round 5, A/B): pr * kFPitch + pc as written — pr is an arbitrary 32-bit value, so the compiler takes v_mad_u64_u32 for it: full rate (tools/valu_rate2), but its 64-bit results cost register pairs, and the block sat at the edge of the register file (1 spill; with the packed rows 28)
-#endif
 			// row * 48 + column by two shift-adds on 32-bit registers (a wrapped product of a row far outside the patch is clamped like any other: any byte will do, the keypoint leaves below)
-			static_assert(kFPitch == 48 || MCS_PATCH_OFF_MAD, "the shift-add form is for a pitch of 48");
+			static_assert(kFPitch == 48, "the shift-add form is for a pitch of 48");
 			unsigned off16 = (pr << 4) + pc;
-			if (!MCS_PATCH_OFF_MAD) asm volatile("" : "+v"(off16));   // (opaque: the compiler otherwise folds the two shift-adds back into the multiply-add)
-			const unsigned offRaw = MCS_PATCH_OFF_MAD ? pr * (unsigned)kFPitch + pc : (pr << 5) + off16;
+			asm volatile("" : "+v"(off16));   // (opaque: the compiler otherwise folds the two shift-adds back into the multiply-add)
+			const unsigned offRaw = (pr << 5) + off16;
 			const unsigned off = min(offRaw, (unsigned)(kFPatchBytes - 1));   // (a sample outside the patch: any byte of it, the keypoint leaves below)
 			val[t] = (MCS_FAST_ABLATE & 1) ? (int)off : (int)pl[off];
 		}
@@ -1193,19 +1021,11 @@ __device__ __forceinline__ bool fast_keypoint_u(const ExtractBuffers& b, const F
 	return !__any(bad);
 }
 
-#ifndef MCS_FAST_DMA
-#define MCS_FAST_DMA 1   // 0: the round-3 walk (slot record by loads, patch through registers), for A/B
-#endif
-constexpr int kFastPatchBufs = MCS_FAST_DMA ? 2 : 1;
-constexpr int kMailDwords = 32, kMailBytes = MCS_FAST_DMA ? 2 * kMailDwords * 4 : 0;   // per wave
+constexpr int kFastPatchBufs = 2;
+constexpr int kMailDwords = 32, kMailBytes = 2 * kMailDwords * 4;   // per wave
 constexpr int kMailCam = 19, kMailUsed = 26;   // dwords 0..2 lvl, rc, poff; 3..18 the eight doubles of KpAuxSoA::d8; 19 tabIdx; 20..25 cam.c, cam.d, cam.e
-#if MCS_FAST_UNIQ
 __host__ __device__ constexpr size_t fast_wave_lds(int nb) { return (size_t)kFastPatchBufs * kFPatchBytes + kMailBytes + uvals_bytes(nb); }   // patch buffer(s), mailboxes, the sampled bytes
 __host__ __device__ constexpr size_t fast_pat_bytes(int nb) { return upat_bytes(nb) + uw_bytes(nb) + gidx_bytes(nb); }   // distinct points, weights, gather indices
-#else
-__host__ __device__ constexpr size_t fast_wave_lds(int) { return (size_t)kFastPatchBufs * kFPatchBytes + kMailBytes; }
-__host__ __device__ constexpr size_t fast_pat_bytes(int nb) { return (size_t)2 * nb * 64 * sizeof(double2); }   // the pattern points as doubles, [point][lane]
-#endif
 
 // The requests are written as inline assembly, not __builtin_amdgcn_global_load_lds: knowing an LDS-DMA write is in flight, the compiler puts an
 // s_waitcnt vmcnt(0) in front of the first LDS read it cannot prove disjoint from the destination — here every table, pattern and patch read of the keypoint
@@ -1275,7 +1095,6 @@ __global__ __launch_bounds__(64 * kFastWaves) void k_describe_fast(ExtractBuffer
 	double2* const patLds = reinterpret_cast<double2*>(reinterpret_cast<uint8_t*>(lds) + kGDevDoubles * sizeof(double));
 	uint8_t* const waveLds = reinterpret_cast<uint8_t*>(patLds) + fast_pat_bytes(NB) + (size_t)wave * kFastWaveLds;
 	uint32_t* const mailBase = reinterpret_cast<uint32_t*>(waveLds + kFastPatchBufs * kFPatchBytes);
-#if MCS_FAST_UNIQ
 	// the pattern's distinct points, their weights and the lanes' gather indices (host-built, upload_describe_tables; visible after the barrier behind the first table load)
 	constexpr int kSlot = NB == 2 ? 0 : NB == 4 ? 1 : 2;
 	double* const uwLds = reinterpret_cast<double*>(reinterpret_cast<uint8_t*>(patLds) + upat_bytes(NB));
@@ -1283,14 +1102,6 @@ __global__ __launch_bounds__(64 * kFastWaves) void k_describe_fast(ExtractBuffer
 	for (int i = threadIdx.x; i < UPat<NB>::R * 64; i += 64 * kFastWaves) patLds[i] = g_upat[kSlot][i];
 	for (int i = threadIdx.x; i < UPat<NB>::RW * 64; i += 64 * kFastWaves) uwLds[i] = g_uw[kSlot][i];
 	for (int i = threadIdx.x; i < 64 * NB; i += 64 * kFastWaves) gidxLds[i] = reinterpret_cast<const uint32_t*>(g_gidx[kSlot])[i];
-#else
-	// the pattern points as doubles (visible after the barrier behind the first table load)
-	for (int i = threadIdx.x; i < 2 * NB * 64; i += 64 * kFastWaves) {
-		const int t = i >> 6, ln = i & 63;
-		const signed char* pp = c_pattern + ((t >> 1) * 64 + ln) * 4 + 2 * (t & 1);
-		patLds[i] = double2{(double)pp[0], (double)pp[1]};
-	}
-#endif
 	double* const tabLds = lds;
 	const PyrDesc& d = *b.desc;
 	KpAuxSoA A; A.carve(b.aux, nslots);
@@ -1300,10 +1111,8 @@ __global__ __launch_bounds__(64 * kFastWaves) void k_describe_fast(ExtractBuffer
 	// image: 711 instead of 365 MB fetched from HBM per launch).  Within a trip an XCD (blockIdx.x % 8: its own L2) takes a contiguous eighth.
 	const int nb = (int)gridDim.x, perXcd = (nb + kNumXCD - 1) / kNumXCD;
 	const int logical = nb % kNumXCD == 0 ? ((int)blockIdx.x % kNumXCD) * perXcd + (int)blockIdx.x / kNumXCD : (int)blockIdx.x;   // a bijection on [0, nb) either way
-	const size_t S = (size_t)nslots;
 	const size_t pyrBytes = d.pyrBytes;
 	int curTab = -1;
-#if MCS_FAST_DMA
 	auto slot_of = [&](int kk) { const int g = kk * nb + logical; return kk < groupsPerBlock && g < ngroups ? g * kFastWaves + wave : -1; };
 	auto ask_record = [&](int kk) { const int gw = slot_of(kk); if (gw >= 0) record_request(A, b.cams, gw, gw / wavesPerImage, mailBase + (kk & 1) * kMailDwords); };
 	auto ask_patch = [&](const FastKp& r, int kk) {
@@ -1318,25 +1127,15 @@ __global__ __launch_bounds__(64 * kFastWaves) void k_describe_fast(ExtractBuffer
 	if (slot_of(0) < 0) nxt.lvl = -1;
 	ask_patch(nxt, 0);
 	ask_record(1);
-	// The walk's ONE wait for vector memory sits at the END of a trip, in front of the trip's output stores (round 6): what it waits for — the next keypoint's patch
-	// and the record after it — was requested a whole keypoint earlier and has long landed, and the stores then have the next trip to complete.  (At the top of the
-	// trip, where it stood, it also waited for the stores just issued: on this chip stores count in vmcnt like loads, a store's round trip per keypoint.)
-#ifndef MCS_FAST_WAIT_TOP
-#define MCS_FAST_WAIT_TOP 1   // 1 (default): the wait at the top of the trip; 0: at its end, in front of the output stores — measured 0.506 against 0.498 ms, not kept
-#endif
+	// The walk's ONE wait for vector memory sits at the TOP of a trip: what it waits for — this keypoint's patch and the record after it — was requested a whole
+	// keypoint earlier.  (At the end of the trip, in front of the trip's output stores: 0.506 against 0.498 ms, not kept.)
 	FastKp cur = nxt;
-	if (!MCS_FAST_WAIT_TOP) {
-		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-		nxt = mail_read(mailBase + kMailDwords);
-		if (slot_of(1) < 0) nxt.lvl = -1;
-	}
-	auto advance = [&](int k) {   // end of trip k: patch k + 1 and record k + 2 have landed
+	auto advance = [&](int k) {   // trip k is over (top of trip k + 1): patch k + 1 and record k + 2 have landed
 		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 		cur = nxt;
 		nxt = mail_read(mailBase + (k & 1) * kMailDwords);   // record k + 2 went into the mailbox record k was read from
 		if (slot_of(k + 2) < 0) nxt.lvl = -1;
 	};
-#endif
 #pragma unroll 1
 	for (int k = 0; k < groupsPerBlock; ++k) {
 		const int g = k * nb + logical;
@@ -1346,12 +1145,9 @@ __global__ __launch_bounds__(64 * kFastWaves) void k_describe_fast(ExtractBuffer
 		const int gwu = base + wave;
 		int lane = threadIdx.x & 63;
 		asm volatile("" : "+v"(lane));   // opaque per trip: nothing derived from the lane id is worth holding in registers across the walk
-#if MCS_FAST_DMA
-#if MCS_FAST_WAIT_TOP
-		advance(k - 1);   // A/B: the wait at the top of the trip (round 5)
-#endif
-		const FastKp me = cur;   // (its patch landed before the previous trip's stores went out: advance())
-		// The requests go out behind this keypoint's first LDS read (inside fast_keypoint), not here: the compiler keeps an s_waitcnt vmcnt(0) in front of that
+		advance(k - 1);
+		const FastKp me = cur;   // (its patch has landed: advance())
+		// The requests go out behind this keypoint's first LDS read (inside fast_keypoint_u), not here: the compiler keeps an s_waitcnt vmcnt(0) in front of that
 		// read (pending flat accesses of the sampler's general path, as its bookkeeping sees the loop) — issued before it, they would be waited for at once.
 		auto ahead = [&]() {
 			ask_patch(nxt, k + 1);   // the other patch buffer: its keypoint (k - 1) is finished
@@ -1359,11 +1155,6 @@ __global__ __launch_bounds__(64 * kFastWaves) void k_describe_fast(ExtractBuffer
 		};
 		const int tabIdx = me.tabIdx;
 		uint8_t* const patchLds = waveLds + (k & 1) * kFPatchBytes;
-#else
-		const OcamDev& cam = b.cams[bimg];
-		const int tabIdx = cam.tabIdx;
-		uint8_t* const patchLds = waveLds;
-#endif
 		if (tabIdx != curTab) {   // uniform over the workgroup: every wave walks the same groups
 			if (curTab >= 0) __syncthreads();   // nobody reads the old table any more
 			if (!(MCS_FAST_ABLATE & 8)) {
@@ -1378,61 +1169,16 @@ __global__ __launch_bounds__(64 * kFastWaves) void k_describe_fast(ExtractBuffer
 			__syncthreads();
 			curTab = tabIdx;
 		}
-#if MCS_FAST_DMA
-		if (!me.usable()) { ahead(); if (!MCS_FAST_WAIT_TOP) advance(k); continue; }   // nothing here, or already on the exact pass's pre-list
-		const int level = me.lvl & 0xFF;
-		const int row = me.rc & 0xFFFF, col = (int)((unsigned)me.rc >> 16);
+		if (!me.usable()) { ahead(); continue; }   // nothing here, or already on the exact pass's pre-list
 		const FastCam C = me.C;
 		const double ukx = me.d8[0], uky = me.d8[1];
 		double axc[3], ays[3];
 #pragma unroll
 		for (int q = 0; q < 3; ++q) { axc[q] = me.d8[2 + 2 * q]; ays[q] = me.d8[3 + 2 * q]; }
-#else
-		// this wave's keypoint as the orientation kernels left it (wave-uniform: scalar loads)
-		const int gws = __builtin_amdgcn_readfirstlane(gwu);
-		const int lvlRaw = A.lvl[gws];
-		if (lvlRaw < 0 || (lvlRaw & kAuxExact)) continue;   // nothing here, or already on the exact pass's pre-list
-		const int level = lvlRaw & 0xFF;
-		const int rc = A.rc[gws];
-		const int row = rc & 0xFFFF, col = (int)((unsigned)rc >> 16);
-		{
-			const LevelInfo& L = d.lv[level];
-			int ln = threadIdx.x & 63;
-			const uint8_t* bp = b.blur + (size_t)bimg * pyrBytes + L.off + (size_t)(row - kPatchR) * L.stride + (col - kPatchR);
-			uint32_t pv[kPatchTrips];
-#pragma unroll
-			for (int t = 0; t < kPatchTrips; ++t) { const int i = min(ln + 64 * t, kPatchRows * kPatchDw - 1); const int r = i / kPatchDw; __builtin_memcpy(&pv[t], bp + (size_t)r * L.stride + 4 * (i - r * kPatchDw), 4); }
-#pragma unroll
-			for (int t = 0; t < kPatchTrips; ++t) { const int i = min(ln + 64 * t, kPatchRows * kPatchDw - 1); const int r = i / kPatchDw; *reinterpret_cast<uint32_t*>(&patchLds[r * kFPitch + 4 * (i - r * kPatchDw)]) = pv[t]; }
-		}
-		FastCam C;
-		C.c = cam.c; C.d = cam.d; C.e = cam.e;
-		const double* D8 = A.d8 + gws;
-		const double ukx = D8[0], uky = D8[S];
-		double axc[3], ays[3];
-#pragma unroll
-		for (int q = 0; q < 3; ++q) { axc[q] = D8[(2 + 2 * q) * S]; ays[q] = D8[(3 + 2 * q) * S]; }
-#endif
-		LazySampler sm;
-		sm.b = &b; sm.img = bimg; sm.level = level; sm.patch = patchLds;
-		(void)sm; (void)row; (void)col;
 		unsigned long long bitsMain[NB], agree[NB];
-#if MCS_FAST_UNIQ
 		UTabs T;
 		T.upat = patLds + lane; T.uw = uwLds + lane; T.gidx = gidxLds + lane * NB; T.vals = waveLds + kFastPatchBufs * kFPatchBytes + kMailBytes;
-#if MCS_FAST_DMA
 		const bool ok = fast_keypoint_u<MODE, NB>(b, C, tabLds, patchLds, ukx, uky, axc, ays, T, bitsMain, agree, ahead);
-#else
-		const bool ok = fast_keypoint_u<MODE, NB>(b, C, tabLds, patchLds, ukx, uky, axc, ays, T, bitsMain, agree, [] {});
-#endif
-#elif MCS_FAST_DMA
-		const bool ok = fast_keypoint<MODE, NB>(b, C, tabLds, sm, row, col, ukx, uky, axc, ays, patLds + lane, bitsMain, agree, ahead);
-#else
-		const bool ok = fast_keypoint<MODE, NB>(b, C, tabLds, sm, row, col, ukx, uky, axc, ays, patLds + lane, bitsMain, agree, [] {});
-#endif
-#if MCS_FAST_DMA
-		if (!MCS_FAST_WAIT_TOP) advance(k);
-#endif
 		if (lane == 0) {
 			if (!ok) { const int at = atomicAdd(b.fbCount, 1); b.fbList[at] = (uint32_t)gwu; }
 			else {
@@ -1447,7 +1193,6 @@ __global__ __launch_bounds__(64 * kFastWaves) void k_describe_fast(ExtractBuffer
 			}
 		}
 	}
-	(void)S; (void)d;
 }
 
 // self-test of the fast arithmetic: n pseudo-random pattern points around random keypoints of camera `cam` through fast_w2i and through the exact
@@ -1472,7 +1217,7 @@ __global__ void k_selftest_fast_model(const OcamDev* camp, const double* tab, un
 	C.c = cam.c; C.d = cam.d; C.e = cam.e;
 	double uf, vf;
 	unsigned top = 0;
-	fast_w2i<true>(C, tab, xr, yr, uf, vf, top);
+	fast_w2i(C, tab, xr, yr, uf, vf, top);
 	if (top >= (unsigned)kGRows) return;
 	double diff = fmax(fabs(uf + cam.u0 - ue), fabs(vf + cam.v0 - ve));   // one extra rounding here (the kernel never adds the principal point)
 	if (!(diff == diff)) diff = 1e300;   // NaN on either side counts as a failure

@@ -33,9 +33,6 @@ namespace mcs {
 #ifndef MCS_FAST_BS
 #define MCS_FAST_BS 128
 #endif
-#ifndef MCS_FAST_SEG16
-#define MCS_FAST_SEG16 1   // pass 1 of the 16-pixel ring on sixteen pixels per thread (round 5); 0: four pixels per thread (round 4), for A/B
-#endif
 template <int CW> struct FastGeom {
 	static constexpr int kTileX = 4;   // tile column of the cell's first processed pixel: a 4-byte left margin (3 ring pixels + 1), so that groups of 4 pixels are aligned dwords
 	static constexpr int kTilePitch = (CW + kTileX + 3 + 4 + 3) / 4 * 4, kTileRows = CW + 6;   // + 4: the packed compass test reads one dword past the right ring
@@ -290,12 +287,9 @@ __global__ __launch_bounds__(kFastBS) void k_fast_cells(ExtractBuffers b, int ni
 	__shared__ int nSurv;
 	__shared__ unsigned short surv[CW * CW];   // codes of the pixels that pass the compass test
 	constexpr int QR = AG >= 0 ? AgastGeom<AG < 0 ? 3 : AG>::R : 3;   // radius of the compass test
-#ifndef MCS_FAST_ORDERED
-#define MCS_FAST_ORDERED 1   // 0 (A/B): the round-5 form — survivors appended by atomics in any order, verdict bitmap + row prefix + a second loop for the emission
-#endif
 	// FAST on the 16-pixel ring: the survivor list is kept in ROW-MAJOR order (round 6), so that a kept survivor's place in the output is the number of kept survivors in
 	// front of it in the list — non-max suppression, mask and emission are then ONE loop with a ballot, where a verdict bitmap, a row prefix and a second loop stood
-	constexpr bool kOrdered = MCS_FAST_ORDERED && P == 16 && MCS_FAST_SEG16 && AG < 0;
+	constexpr bool kOrdered = P == 16 && AG < 0;
 	__shared__ int waveTot[kFastBS / 64];
 	int listRun = 0;   // survivors listed by the trips so far (uniform)
 
@@ -317,48 +311,13 @@ __global__ __launch_bounds__(kFastBS) void k_fast_cells(ExtractBuffers b, int ni
 	const uint8_t* src = level_ptr(b, d, img, cell.level, &stride);
 	src += (size_t)(cell.y0 - 3) * stride + (cell.x0 - Geo::kTileX);
 	const int th = ch + 6;
-#ifndef MCS_FAST_STAGE_DMA
-#define MCS_FAST_STAGE_DMA 0   // 1 (A/B, round 6): the tile by LDS-DMA (below) — a quarter fewer VALU instructions in this phase, bit-exact, and SLOWER: 0.345 against 0.337 ms (481 dword requests per cell, each wave's M0 set-up and the wait in front of the barrier)
-#endif
-#if MCS_FAST_STAGE_DMA
-	// Staging by LDS-DMA (round 6): global_load_lds_dword moves a dword per lane from global memory straight into LDS at (uniform base + 4 * lane) — lane c of
-	// the workgroup owns dword c of the tile in row-major order (a tile row = kTilePitch / 4 dwords of the image row starting at x0 - kTileX), so the only VALU
-	// work left is c -> (row, dword) and the global offset: ~6 instructions per thread and trip, no LDS stores, no registers in between.  The kernel is bound by
-	// VALU issue (0.92 busy) and a fifth of its VALU instructions were this copy.  A row's dwords past the image row's end are not requested (the rightmost
-	// cell of a narrow level; they lie beyond the ring and the one dword the compass test reads past it).
-	{
-		constexpr int kRowDw = kTilePitch / 4;
-		constexpr unsigned kRowM = (65536u + kRowDw - 1) / kRowDw;   // c / kRowDw = (c * kRowM) >> 16, exact for c < kTileRows * kRowDw <= 72 * 18
-		static_assert((unsigned)(kTileRows * kRowDw) * (kRowM * kRowDw - 65536u) < 65536u, "row of a tile dword by multiplication");
-		const int availDw = min(kRowDw, (L.w - (cell.x0 - Geo::kTileX) + 3) >> 2);   // dwords of a tile row that start inside the image row (level-ROI coordinates: x0 >= 22 > kTileX)
-		const int ndwTile = kRowDw * th;
-		for (int base = 0; base < ndwTile; base += kFastBS) {   // (uniform trip count: the LDS base of a wave's request is wave-uniform)
-			const int c = base + tid;
-			const unsigned ty = ((unsigned)c * kRowM) >> 16, kx = (unsigned)c - ty * (unsigned)kRowDw;
-			if (c < ndwTile && (int)kx < availDw)
-				__builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (ty * (unsigned)stride + 4u * kx)),
-				                                 (__attribute__((address_space(3))) void*)(tile + 4 * (base + (tid & ~63))), 4, 0, 0);
-		}
-	}
-	// the score tile cleared as 16-byte words by one trip, the verdict bitmap as dwords
-	{
-		constexpr int kSc16 = (kScRows * kScPitch + 15) / 16;
-		for (int i = tid; i < kSc16; i += kFastBS) reinterpret_cast<uint4*>(sc)[i] = uint4{0u, 0u, 0u, 0u};
-	}
-	if (!kOrdered) for (int i = tid; i < 2 * ch; i += kFastBS) keepBits[i] = 0;
-	if (tid == 0) { runBase = 0; nSurv = 0; }
-	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's requests have landed (hipcc does not count LDS-DMA loads in front of a barrier)
-	__syncthreads();
-#else
-#ifndef MCS_FAST_STAGE16
-#define MCS_FAST_STAGE16 1   // 0 (A/B): the round-5 staging for every cell (two dwords per thread and trip)
-#endif
 	// Staging in 16-byte chunks (round 6): a tile row (kTilePitch bytes of the image row from x0 - kTileX) is ceil(kTilePitch / 16) chunks, the last one pulled back to end
 	// with the row (its leading bytes then duplicate the chunk before it: same bytes to the same LDS addresses); a thread loads one chunk (one unaligned 16-byte load)
 	// and stores it as four dwords.  The index arithmetic is paid per 16 bytes instead of per 4: this phase was a fifth of the kernel's VALU instructions, and the kernel is
 	// bound by VALU issue.  Only for cells whose tile rows end inside the image row (cw >= kTilePitch - 26 for FAST: every cell of the usual 30-px grid with the 40-px
 	// instance); the rest — a wide instance serving a level of narrow cells — take the dword loop below.
-	const bool stage16 = MCS_FAST_STAGE16 && (cell.x0 - Geo::kTileX + kTilePitch <= L.w);
+	// (LDS-DMA staging, a dword per lane straight into the tile, was bit-exact with a quarter fewer VALU instructions in this phase and slower: 0.345 against 0.337 ms.)
+	const bool stage16 = cell.x0 - Geo::kTileX + kTilePitch <= L.w;
 	if (stage16) {
 		constexpr int kChunks = (kTilePitch + 15) / 16, kLast = kTilePitch - 16;   // kTilePitch is a multiple of 4, >= 16
 		static_assert((kChunks & (kChunks - 1)) == 0 || kChunks == 3 || kChunks == 5 || kChunks == 6, "chunks per row");
@@ -377,37 +336,36 @@ __global__ __launch_bounds__(kFastBS) void k_fast_cells(ExtractBuffers b, int ni
 		if (tid == 0) { runBase = 0; nSurv = 0; }
 		__syncthreads();
 	} else {
-	const int tw = cw + Geo::kTileX + 3;
-	const int ndw = (tw + 3) >> 2;   // unaligned dword loads; the <= 3 bytes of over-read per row stay inside the image row
-	// i / ndw by multiplication (CellInfo.rowM = ceil(2^16 / ndw)): ndw <= 17 and i < 17 * 66, so the error term i * (M*ndw - 2^16) < 2^16 and
-	// (i * M) >> 16 is exact; 32-bit offsets keep the address arithmetic out of 64-bit multiplies.
-	const unsigned rowM = (unsigned)cell.rowM;
-	// two dwords per thread and trip (a ~30x30 cell is 370 dwords: one trip): both loads are in flight before the first LDS store waits
-	const int ndwTile = ndw * th;
-	for (int i = tid; i < ndwTile; i += 2 * kFastBS) {
-		const int i2 = i + kFastBS;
-		const bool has2 = i2 < ndwTile;
-		const unsigned ty = ((unsigned)i * rowM) >> 16, kx = (unsigned)i - ty * (unsigned)ndw;
-		const unsigned ty2 = ((unsigned)i2 * rowM) >> 16, kx2 = (unsigned)i2 - ty2 * (unsigned)ndw;
-		uint32_t v, v2 = 0;
-		__builtin_memcpy(&v, src + (ty * (unsigned)stride + 4u * kx), 4);
-		if (has2) __builtin_memcpy(&v2, src + (ty2 * (unsigned)stride + 4u * kx2), 4);
-		*reinterpret_cast<uint32_t*>(&tile[ty * kTilePitch + 4 * kx]) = v;
-		if (has2) *reinterpret_cast<uint32_t*>(&tile[ty2 * kTilePitch + 4 * kx2]) = v2;
+		const int tw = cw + Geo::kTileX + 3;
+		const int ndw = (tw + 3) >> 2;   // unaligned dword loads; the <= 3 bytes of over-read per row stay inside the image row
+		// i / ndw by multiplication (CellInfo.rowM = ceil(2^16 / ndw)): ndw <= 17 and i < 17 * 66, so the error term i * (M*ndw - 2^16) < 2^16 and
+		// (i * M) >> 16 is exact; 32-bit offsets keep the address arithmetic out of 64-bit multiplies.
+		const unsigned rowM = (unsigned)cell.rowM;
+		// two dwords per thread and trip (a ~30x30 cell is 370 dwords: one trip): both loads are in flight before the first LDS store waits
+		const int ndwTile = ndw * th;
+		for (int i = tid; i < ndwTile; i += 2 * kFastBS) {
+			const int i2 = i + kFastBS;
+			const bool has2 = i2 < ndwTile;
+			const unsigned ty = ((unsigned)i * rowM) >> 16, kx = (unsigned)i - ty * (unsigned)ndw;
+			const unsigned ty2 = ((unsigned)i2 * rowM) >> 16, kx2 = (unsigned)i2 - ty2 * (unsigned)ndw;
+			uint32_t v, v2 = 0;
+			__builtin_memcpy(&v, src + (ty * (unsigned)stride + 4u * kx), 4);
+			if (has2) __builtin_memcpy(&v2, src + (ty2 * (unsigned)stride + 4u * kx2), 4);
+			*reinterpret_cast<uint32_t*>(&tile[ty * kTilePitch + 4 * kx]) = v;
+			if (has2) *reinterpret_cast<uint32_t*>(&tile[ty2 * kTilePitch + 4 * kx2]) = v2;
+		}
+		const int sh = ch + 2;
+		for (int i = tid; i < sh * (kScPitch / 4); i += kFastBS) reinterpret_cast<uint32_t*>(sc)[i] = 0;   // score tile cleared as dwords
+		if (!kOrdered) for (int i = tid; i < 2 * ch; i += kFastBS) keepBits[i] = 0;
+		if (tid == 0) { runBase = 0; nSurv = 0; }
+		__syncthreads();
 	}
-	const int sh = ch + 2;
-	for (int i = tid; i < sh * (kScPitch / 4); i += kFastBS) reinterpret_cast<uint32_t*>(sc)[i] = 0;   // score tile cleared as dwords
-	if (!kOrdered) for (int i = tid; i < 2 * ch; i += kFastBS) keepBits[i] = 0;
-	if (tid == 0) { runBase = 0; nSurv = 0; }
-	__syncthreads();
-	}
-#endif
 
 	const int t = d.fastThreshold;
 	const int lane = tid & 63, wave = tid >> 6;
 	// pass 1: cheap compass test on every pixel; survivors are compacted into an LDS list (order is irrelevant here) so that
 	// pass 2 — the full 16-pixel arc score, ~10x the work — runs with all lanes busy instead of diverging inside each wave
-	if constexpr ((P == 16 && MCS_FAST_SEG16) || AG >= 0) {
+	if constexpr (P == 16 || AG >= 0) {
 		// pass 1, 16-pixel ring, round 5: SIXTEEN adjacent pixels per thread (four fast_quick4 groups whose row dwords overlap: 14 LDS dwords instead of 20), so a
 		// 31 x 31 cell is 62 lanes — ONE trip of ONE wave where four-pixel lanes took two trips of both waves —, and the per-trip overhead (index arithmetic, prefix sum
 		// over the lanes' survivor counts, the atomic, the list writes) is paid once per 16 pixels: ~236 instead of ~470 wave-instructions per cell for this pass.
@@ -456,34 +414,6 @@ __global__ __launch_bounds__(kFastBS) void k_fast_cells(ExtractBuffers b, int ni
 				bits &= bits - 1u;
 			}
 		}
-	} else if constexpr (P == 16) {
-		// pass 1, 16-pixel ring: four adjacent pixels per thread (fast_quick4); the wave reserves list space for all of them with one prefix sum over the lanes'
-		// survivor counts (DPP) and one atomic
-		const int gpr = (cw + 3) >> 2, ngrp = gpr * ch;   // groups per row: gpr <= 15, g < 15 * 60: CellInfo.grpM = ceil(2^16 / gpr) is exact
-		const unsigned gM = (unsigned)cell.grpM;
-		const v2s tt = {(short)t, (short)t};
-		for (int base = 0; base < ngrp; base += kFastBS) {
-			const int g = base + tid;
-			uint32_t bits = 0;
-			int code = 0;
-			if (g < ngrp) {
-				const int py = (int)(((unsigned)g * gM) >> 16), gx = g - py * gpr;
-				bits = fast_quick4<kTilePitch>(&tile[(py + 3) * kTilePitch + 4 * gx + Geo::kTileX], tt);
-				const int left = cw - 4 * gx;   // pixels of the group inside the cell (the last group of a row may be partial): pixels 0, 1, 2, 3 are bits 0, 1, 16, 17
-				if (left < 4) bits &= left == 3 ? 0x00010003u : left == 2 ? 0x00000003u : 0x00000001u;
-				code = (py << 6) | (4 * gx);
-			}
-			const int cnt = __popc(bits);
-			const int incl = wave_incl_scan(cnt);
-			const int total = __builtin_amdgcn_readlane(incl, 63);
-			int wbase = 0;
-			if (lane == 0 && total) wbase = atomicAdd(&nSurv, total);
-			wbase = __builtin_amdgcn_readfirstlane(wbase) + incl - cnt;
-			if (bits & 0x00000001u) surv[wbase] = (unsigned short)code;
-			if (bits & 0x00000002u) surv[wbase + (int)(bits & 1u)] = (unsigned short)(code + 1);
-			if (bits & 0x00010000u) surv[wbase + __popc(bits & 0x3u)] = (unsigned short)(code + 2);
-			if (bits & 0x00020000u) surv[wbase + __popc(bits & 0x10003u)] = (unsigned short)(code + 3);
-		}
 	} else {
 		// p / cw by multiplication: cw <= 60 and p < 3600, so with M = ceil(2^18 / cw) the error term p * (M*cw - 2^18) < 3600 * 60 < 2^18 and (p * M) >> 18 is exact
 		const int npx = cw * ch;
@@ -515,13 +445,13 @@ __global__ __launch_bounds__(kFastBS) void k_fast_cells(ExtractBuffers b, int ni
 			if (i + 1 < ns) sc[(yb + 1) * kScPitch + xb + 1] = (uint8_t)(s2 >> 8);
 		}
 	} else
-	for (int i = tid; i < ns; i += kFastBS) {
-		const int p = surv[i];
-		const int py = p >> 6, px = p & 63;
-		const uint8_t* c = &tile[(py + 3) * kTilePitch + px + Geo::kTileX];
-		if constexpr (AG >= 0) sc[(py + 1) * kScPitch + px + 1] = (uint8_t)agast_score<(AG < 0 ? 0 : AG), kTilePitch>(c, t);
-		else sc[(py + 1) * kScPitch + px + 1] = (uint8_t)small_ring_score<P, kTilePitch>(c, t);
-	}
+		for (int i = tid; i < ns; i += kFastBS) {
+			const int p = surv[i];
+			const int py = p >> 6, px = p & 63;
+			const uint8_t* c = &tile[(py + 3) * kTilePitch + px + Geo::kTileX];
+			if constexpr (AG >= 0) sc[(py + 1) * kScPitch + px + 1] = (uint8_t)agast_score<(AG < 0 ? 0 : AG), kTilePitch>(c, t);
+			else sc[(py + 1) * kScPitch + px + 1] = (uint8_t)small_ring_score<P, kTilePitch>(c, t);
+		}
 	__syncthreads();
 
 	uint32_t* slots = b.slots + (size_t)img * d.slotsPerImage + cell.slot;

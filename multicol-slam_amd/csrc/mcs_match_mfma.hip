@@ -36,9 +36,6 @@
 #ifndef MCS_MM_TPS
 #define MCS_MM_TPS 2
 #endif
-#ifndef MCS_MM_NBUF
-#define MCS_MM_NBUF 2
-#endif
 namespace mcs {
 
 typedef int v8i_t __attribute__((ext_vector_type(8)));
@@ -167,8 +164,8 @@ __global__ __launch_bounds__(XQ) void k_match_mfma(MatchArgs a) {
 	constexpr int CB = MCS_MM_CB;                    // candidate column depth per lane, a power of two (A/B, round 4: 32 with one-tile stages — the same LDS — 10.6 against 7.07 ms on configs[2]: 30 spilled registers, sort network of 32)
 	constexpr int SLABS = TPS * NS;                  // 1-KB operand slabs (tile, K step) per stage
 	// A operands of two stages: stage g + 1 arrives (global_load_lds: global -> LDS without passing registers) while stage g is multiplied
-	__shared__ __attribute__((aligned(16))) uint4 ex[MCS_MM_NBUF][TPS][NS][64];
-	__shared__ __attribute__((aligned(16))) float wrow[MCS_MM_NBUF][64];
+	__shared__ __attribute__((aligned(16))) uint4 ex[2][TPS][NS][64];
+	__shared__ __attribute__((aligned(16))) float wrow[2][64];
 	__shared__ uint32_t lut[256];
 	__shared__ uint32_t cand[(CB + 1) * XQ];
 
@@ -206,7 +203,7 @@ __global__ __launch_bounds__(XQ) void k_match_mfma(MatchArgs a) {
 			__builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(srcW + (size_t)g * (32 * TPS) + ln),
 			                                 (__attribute__((address_space(3))) void*)(&wrow[buf][0]), 4, 0, 0);
 	};
-	if (MCS_MM_NBUF == 2 && g0 < g1) request(g0, 0, lane, wv);
+	if (g0 < g1) request(g0, 0, lane, wv);
 	for (int i = tid; i < 256; i += XQ) lut[i] = spread8((uint32_t)i);
 	__syncthreads();
 
@@ -331,7 +328,6 @@ __global__ __launch_bounds__(XQ) void k_match_mfma(MatchArgs a) {
 	};
 	uint32_t rawLim = limit();
 	for (int g = g0; g < g1; ++g) {
-#if MCS_MM_NBUF == 2
 		const int buf = (g - g0) & 1;
 		// stage g has landed once every wave's own LDS-DMA loads are complete (hipcc does not count them before a barrier: the wait is explicit) and the
 		// waves have met; every wave is then through with stage g - 1 as well
@@ -341,16 +337,6 @@ __global__ __launch_bounds__(XQ) void k_match_mfma(MatchArgs a) {
 		asm volatile("" : "+v"(t2));
 		const int ln = t2 & 63, kh2 = (t2 >> 5) & 1;
 		if (g + 1 < g1) request(g + 1, buf ^ 1, ln, t2 >> 6);
-#else
-		const int buf = 0;
-		int t2 = threadIdx.x;
-		asm volatile("" : "+v"(t2));
-		const int ln = t2 & 63, kh2 = (t2 >> 5) & 1;
-		__syncthreads();
-		request(g, 0, ln, t2 >> 6);
-		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-		__syncthreads();
-#endif
 #pragma unroll
 		for (int tile = 0; tile < TPS; ++tile) {
 			const int row0 = (g * TPS + tile) << 5;

@@ -140,14 +140,6 @@ __global__ __launch_bounds__(256) void k_octree(ExtractBuffers b, int nimg, int 
 		for (int i = tid; i < m; i += 256) scanA[i] = cellCount[c0 + i];
 		__syncthreads();
 		const int tot = block_exscan<IPT>(scanA, m, wsum);
-#ifdef MCS_OCT_WAVE_CELLS   // A/B: round 3's form, a wave per cell — a hundred dependent trips per wave (count -> records -> store) with a handful of lanes each
-		for (int c = wave; c < m; c += 4) {
-			const int cnt = cellCount[c0 + c];
-			const int off = n + scanA[c];
-			const uint32_t* sp = slots + (size_t)(c0 + c) * Lv.capc;
-			for (int j = lane; j < cnt; j += 64) denseG[off + j] = sp[j];
-		}
-#else
 		// a THREAD per cell (a cell holds a handful of records): every thread's loads are independent of everybody else's, four records in flight per thread
 		for (int c = tid; c < m; c += 256) {
 			const int cnt = cellCount[c0 + c];
@@ -165,7 +157,6 @@ __global__ __launch_bounds__(256) void k_octree(ExtractBuffers b, int nimg, int 
 					}
 			}
 		}
-#endif
 		n += tot;
 	}
 	__syncthreads();
@@ -174,9 +165,6 @@ __global__ __launch_bounds__(256) void k_octree(ExtractBuffers b, int nimg, int 
 	OCT_T(1);
 	// keys of small levels live in LDS for the passes below (each pass walks all keys twice; from HBM that is the kernel's latency)
 	const bool inLds = n <= KCACHE;
-#ifdef MCS_OCT_WAVE_CELLS
-	if (inLds) for (int k = tid; k < n; k += 256) kd[k] = denseG[k];
-#endif
 	const uint32_t* dense = inLds ? kd : denseG;
 	unsigned short* knode = inLds ? kn : knodeG;
 	__syncthreads();
@@ -216,142 +204,6 @@ __global__ __launch_bounds__(256) void k_octree(ExtractBuffers b, int nimg, int 
 	// ---------------------------------------------------------------- passes
 	int cur = 0;
 	bool phaseB = false;
-#ifdef MCS_OCT_BLOCK_PASSES   // A/B: round 3's passes — every node-level step by all 256 threads with a workgroup barrier (or two) behind it: ~25 per pass
-	for (int pass = 0; pass < 64; ++pass) {
-		NodeBuf<MAXN>& A = nb[cur];
-		NodeBuf<MAXN>& Bn = nb[cur ^ 1];
-		const int prevL = L;
-		// (1) candidate ranks
-		int M;
-		if (!phaseB) {
-			for (int i = tid; i < L; i += 256) scanA[i] = A.cnt[i] > 1 ? 1 : 0;
-			__syncthreads();
-			M = block_exscan<IPT>(scanA, L, wsum);
-			for (int i = tid; i < L; i += 256) crank[i] = A.cnt[i] > 1 ? (short)scanA[i] : (short)-1;
-		} else {
-			for (int i = tid; i < L; i += 256) scanA[i] = A.cre[i] >= 0 ? 1 : 0;
-			__syncthreads();
-			M = block_exscan<IPT>(scanA, L, wsum);
-			for (int i = tid; i < L; i += 256) {   // rank = number of candidates with a larger (cnt, cre) key
-				short r = -1;
-				if (A.cre[i] >= 0) {
-					const unsigned long long key = ((unsigned long long)A.cnt[i] << 16) | (unsigned)(unsigned short)A.cre[i];
-					int g = 0;
-					for (int j = 0; j < L; ++j) {
-						const int cj = A.cre[j];
-						const unsigned long long kj = ((unsigned long long)A.cnt[j] << 16) | (unsigned)(unsigned short)cj;
-						g += (cj >= 0 && kj > key) ? 1 : 0;
-					}
-					r = (short)g;
-				}
-				crank[i] = r;
-			}
-		}
-		for (int i = tid; i < L * 4; i += 256) cc[i] = 0;
-		__syncthreads();
-		if (M == 0) break;   // nothing can be split: lNodes.size() == prevSize (:767,832)
-		// (2) child key counts of every candidate
-		for (int k = tid; k < n; k += 256) {
-			const int i = knode[k];
-			if (crank[i] >= 0) {
-				const uint32_t rec = dense[k];
-				const int x = rec & 0xFFF, y = (rec >> 12) & 0xFFF;
-				const int mx = A.x0[i] + ((A.x1[i] - A.x0[i] + 1) >> 1);
-				const int my = A.y0[i] + ((A.y1[i] - A.y0[i] + 1) >> 1);
-				const int q = (x < mx ? 0 : 1) + (y < my ? 0 : 2);
-				atomicAdd(&cc[i * 4 + q], 1);
-			}
-		}
-		for (int i = tid; i < L; i += 256)
-			if (crank[i] >= 0) byRank[crank[i]] = (short)i;
-		__syncthreads();
-		// (3) how many candidates are processed: all (phase A) or up to the node that lifts the list to >= N (phase B, :828)
-		int P = M;
-		if (phaseB) {
-			for (int r = tid; r < M; r += 256) {
-				const int i = byRank[r];
-				scanB[r] = (cc[i * 4] > 0) + (cc[i * 4 + 1] > 0) + (cc[i * 4 + 2] > 0) + (cc[i * 4 + 3] > 0) - 1;
-			}
-			if (tid == 0) shR = M - 1;
-			__syncthreads();
-			block_exscan<IPT>(scanB, M, wsum);
-			for (int r = tid; r < M; r += 256) {
-				const int i = byRank[r];
-				const int nch = (cc[i * 4] > 0) + (cc[i * 4 + 1] > 0) + (cc[i * 4 + 2] > 0) + (cc[i * 4 + 3] > 0);
-				const int sizeAfter = L + scanB[r] + nch - 1;
-				if (sizeAfter >= N) atomicMin(&shR, r);
-			}
-			__syncthreads();
-			P = shR + 1;
-			__syncthreads();
-		}
-		// (4) prefix sums in processing order: children (list placement) and big children (creation index)
-		for (int r = tid; r < P; r += 256) {
-			const int i = byRank[r];
-			scanA[r] = (cc[i * 4] > 0) + (cc[i * 4 + 1] > 0) + (cc[i * 4 + 2] > 0) + (cc[i * 4 + 3] > 0);
-			scanB[r] = (cc[i * 4] > 1) + (cc[i * 4 + 1] > 1) + (cc[i * 4 + 2] > 1) + (cc[i * 4 + 3] > 1);
-		}
-		__syncthreads();
-		const int T = block_exscan<IPT>(scanA, P, wsum);
-		const int nToExpand = block_exscan<IPT>(scanB, P, wsum);
-		const int newL = T + L - P;
-		if (newL > MAXN) { if (tid == 0) atomicExch(b.status, MCS_ERR_CAPACITY); L = 0; break; }
-		// children of processed nodes
-		for (int r = tid; r < P; r += 256) {
-			const int i = byRank[r];
-			const int c0 = cc[i * 4], c1 = cc[i * 4 + 1], c2 = cc[i * 4 + 2], c3 = cc[i * 4 + 3];
-			const int nch = (c0 > 0) + (c1 > 0) + (c2 > 0) + (c3 > 0);
-			int pos = T - scanA[r] - nch;        // children of later-processed nodes sit in front
-			int cre = scanB[r];
-			const short x0 = A.x0[i], x1 = A.x1[i], y0 = A.y0[i], y1 = A.y1[i];
-			const short mx = (short)(x0 + ((x1 - x0 + 1) >> 1)), my = (short)(y0 + ((y1 - y0 + 1) >> 1));
-			short p0 = -1, p1 = -1, p2 = -1, p3 = -1;
-			if (c3 > 0) p3 = (short)pos++;       // list order inside the node: n4, n3, n2, n1
-			if (c2 > 0) p2 = (short)pos++;
-			if (c1 > 0) p1 = (short)pos++;
-			if (c0 > 0) p0 = (short)pos++;
-			if (c0 > 0) { Bn.x0[p0] = x0; Bn.x1[p0] = mx; Bn.y0[p0] = y0; Bn.y1[p0] = my; Bn.cnt[p0] = c0; Bn.cre[p0] = c0 > 1 ? (short)cre++ : (short)-1; }
-			if (c1 > 0) { Bn.x0[p1] = mx; Bn.x1[p1] = x1; Bn.y0[p1] = y0; Bn.y1[p1] = my; Bn.cnt[p1] = c1; Bn.cre[p1] = c1 > 1 ? (short)cre++ : (short)-1; }
-			if (c2 > 0) { Bn.x0[p2] = x0; Bn.x1[p2] = mx; Bn.y0[p2] = my; Bn.y1[p2] = y1; Bn.cnt[p2] = c2; Bn.cre[p2] = c2 > 1 ? (short)cre++ : (short)-1; }
-			if (c3 > 0) { Bn.x0[p3] = mx; Bn.x1[p3] = x1; Bn.y0[p3] = my; Bn.y1[p3] = y1; Bn.cnt[p3] = c3; Bn.cre[p3] = c3 > 1 ? (short)cre++ : (short)-1; }
-			mapq[i * 4] = p0; mapq[i * 4 + 1] = p1; mapq[i * 4 + 2] = p2; mapq[i * 4 + 3] = p3;
-		}
-		__syncthreads();
-		// untouched nodes keep their relative order behind the new children
-		for (int i = tid; i < L; i += 256) scanA[i] = (crank[i] >= 0 && crank[i] < P) ? 0 : 1;
-		__syncthreads();
-		block_exscan<IPT>(scanA, L, wsum);
-		for (int i = tid; i < L; i += 256) {
-			if (!(crank[i] >= 0 && crank[i] < P)) {
-				const int p = T + scanA[i];
-				Bn.x0[p] = A.x0[i]; Bn.x1[p] = A.x1[i]; Bn.y0[p] = A.y0[i]; Bn.y1[p] = A.y1[i];
-				Bn.cnt[p] = A.cnt[i]; Bn.cre[p] = -1;
-				mapq[i * 4] = (short)p;
-				crank[i] = -1;
-			}
-		}
-		__syncthreads();
-		// (6) keys follow their node
-		for (int k = tid; k < n; k += 256) {
-			const int i = knode[k];
-			int q = 0;
-			if (crank[i] >= 0) {
-				const uint32_t rec = dense[k];
-				const int x = rec & 0xFFF, y = (rec >> 12) & 0xFFF;
-				const int mx = A.x0[i] + ((A.x1[i] - A.x0[i] + 1) >> 1);
-				const int my = A.y0[i] + ((A.y1[i] - A.y0[i] + 1) >> 1);
-				q = (x < mx ? 0 : 1) + (y < my ? 0 : 2);
-			}
-			knode[k] = (unsigned short)mapq[i * 4 + q];
-		}
-		__syncthreads();
-		cur ^= 1;
-		L = newL;
-		// (7) termination (:767-771, :832)
-		if (L >= N || L == prevL) break;
-		if (!phaseB && L + 3 * nToExpand > N) phaseB = true;
-	}
-#else
 	// Round 4: a pass crosses FOUR workgroup barriers instead of ~25.  The levels of a 754 x 480 image hold 300-900 candidates and at most 256 nodes: the two loops
 	// over the KEYS use all four waves, but every step over the NODES (ranks, processing order, where the list reaches N, the two prefix sums, the children, the
 	// untouched nodes) is a few entries per lane of ONE wave — wave 0 runs them back to back with DPP prefix sums, its LDS accesses stay in program order, and
@@ -499,7 +351,6 @@ __global__ __launch_bounds__(256) void k_octree(ExtractBuffers b, int nimg, int 
 		if (L >= N || L == prevL) break;
 		if (!phaseB && L + 3 * nToExpand > N) phaseB = true;
 	}
-#endif
 	__syncthreads();
 
 	OCT_T(14);
@@ -525,9 +376,7 @@ __global__ __launch_bounds__(256) void k_octree(ExtractBuffers b, int nimg, int 
 	__syncthreads();   // the selection and the table are complete
 	int rstride;
 	const uint8_t* raw = level_ptr(b, d, img, level, &rstride);
-#ifndef MCS_OCT_AB   // A/B (timing only): the kernel without its orientation tail (101 against 157 us before the tail's byte dot products)
 	orient_selected(raw, rstride, otab, selL, L, b.selAngle + (size_t)img * d.selPerImage + Lv.selBase);
-#endif
 #ifdef MCS_OCT_TRACE
 	__syncthreads();
 	OCT_T(16);

@@ -174,10 +174,9 @@ def test_cameras_the_fast_pass_must_not_serve_get_an_infinite_or_large_bound():
 
 
 def test_device_form_of_the_table_and_its_float_tail_term():
-    """mcs_describe_fast_table_packed: the rows as the DEVICE reads them.  Default build: the host's rows of doubles, unchanged, and a zero float term.  A build with
-    MCS_G_PACKED=1 (48-byte rows: g0 .. g3 doubles, g4 .. g6 floats, kept as an A/B switch — it measured slower, profiles/NOTES.md round 6): the doubles must be the
-    table's, the floats its coefficients rounded to nearest, the row polynomial with the tail evaluated in float arithmetic must stay within tailU + f32 term of G, and
-    the term must match its independent derivation (6 relative roundings of 2^-24 on sum |g_j| |tau|^j, j = 4 .. 6, times sqrt(s))."""
+    """mcs_describe_fast_table_packed: the rows as the DEVICE reads them — 48 bytes, g0 .. g3 as doubles, g4 .. g6 as floats.  The doubles must be the table's, the
+    floats its coefficients rounded to nearest, the row polynomial with the tail evaluated in float arithmetic must stay within tailU + f32 term of G, and the term
+    must match its independent derivation (6 relative roundings of 2^-24 on sum |g_j| |tau|^j, j = 4 .. 6, times sqrt(s))."""
     rng = np.random.default_rng(5)
     for cam in _cams()[:4]:
         tab, e0, bpo, info = _table(cam)
@@ -186,9 +185,6 @@ def test_device_form_of_the_table_and_its_float_tail_term():
         mcs.check(mcs.lib().mcs_describe_fast_table_packed(C.byref(oc), None, C.byref(rb), C.byref(f32)))
         raw = np.zeros(tab.shape[0] * rb.value, np.uint8)
         mcs.check(mcs.lib().mcs_describe_fast_table_packed(C.byref(oc), raw.ctypes.data_as(C.c_void_p), None, None))
-        if rb.value == 8 * tab.shape[1]:
-            assert np.array_equal(raw.view(np.float64).reshape(tab.shape), tab) and f32.value == 0.0
-            continue
         assert rb.value == 48 and tab.shape[1] == 7
         rows = raw.reshape(-1, 48)
         d4 = rows[:, :32].copy().view(np.float64)
