@@ -173,6 +173,11 @@ int mcs_extractor_tie_counts(mcs_extractor*, uint64_t* listed, uint64_t* recompu
  *        event only — later batches keep running —, recomputes the listed descriptors with the host's libm (the same code path as mcs_extractor_fix_ties) and
  *        writes them over the batch's device rows; the rows are in place when it returns, so whatever is enqueued afterwards (search, exchange, download) reads
  *        them.  MCS_ERR_CAPACITY: more listed keypoints than max_ties (nothing patched; widen the slots or use mcs_extractor_fix_ties).
+ *        MCS_ERR_UNSUPPORTED: a pattern sample of a listed keypoint lies outside its 81 x 81 window — a camera whose affine part (c, d, e) magnifies the pattern
+ *        beyond 40 px, about 1.9x.  Nothing is patched, the slot stays unpatched and the extractor goes on working; the batch can still be served by
+ *        mcs_extractor_fix_ties as long as it is the extractor's latest.  The window cannot be refetched here: the pyramid may hold a later batch already.
+ *        Host-kind mcs_extract_batch is NOT limited in this way: its levels are still resident when it recomputes, so on a window miss it recomputes every
+ *        listed keypoint from the downloaded levels (the path of mcs_extractor_fix_ties) and returns MCS_OK.
  * The pipelined order of bench.py / host/rig_host.cpp: enqueue extract(n); patch_ties(back = 1) — batch n - 1 has finished or is about to, the device already
  * holds batch n's work —; then enqueue search / exchange of batch n - 1.  One step of result latency, no device idle time, every consumed row the host's. */
 int mcs_extractor_set_tie_capture(mcs_extractor*, int depth, int max_ties);

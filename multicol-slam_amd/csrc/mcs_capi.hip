@@ -773,6 +773,9 @@ static int fix_ties(mcs_extractor* e, int nties, uint8_t* h_desc, uint8_t* h_mas
 
 // The listed keypoints of a batch from what k_tie_capture left in page-locked memory (mcs_tiefix.hip): entry i -> descriptor | mask rows at rowsOut + i * 2 *
 // descSize, its image and slot in where[i]; returns the number of rows recomputed, < 0 = error code.  No device access at all.
+// kTieWindowMiss: a pattern sample of a listed keypoint lies outside its 81 x 81 window — a camera whose affine part stretches the pattern beyond 40 px (c = 3.2, say:
+// legal input).  Nothing is reported yet: the host-kind caller still has the levels and falls back to them, the pipelined one cannot and fails.
+static constexpr int kTieWindowMiss = -1000;
 static int recompute_captured(mcs_extractor* e, const uint8_t* slot, int n, const std::vector<OcamDev>& cams, uint8_t* rowsOut, std::vector<std::pair<int, int> >& where) {
 	const PyrDesc& hd = e->hd;
 	const int wavesPerImage = (hd.kpCap + kSlotAlign - 1) / kSlotAlign * kSlotAlign;
@@ -789,20 +792,22 @@ static int recompute_captured(mcs_extractor* e, const uint8_t* slot, int n, cons
 		HostLevel hl{nullptr, nullptr, L.w, L.h, en->patch, row - kTiePatchR, col - kTiePatchR, kTiePatchDim, &miss};
 		uint8_t* dsc = rowsOut + where.size() * 2 * hd.descSize;
 		describe_host(hd.mode, hd.descSize, kPattern, cam, hd.undistort, en->level, L.scale, row, col, en->angle, hl, dsc, dsc + hd.descSize);
-		if (miss) { ++e->tieWindowMisses; return fail(MCS_ERR_UNSUPPORTED, "a pattern sample of a listed keypoint lies outside the captured window (camera model with > 1.9x local magnification?)"); }
+		if (miss) { ++e->tieWindowMisses; return kTieWindowMiss; }
 		where.push_back(std::make_pair(img, sl));
 	}
 	return (int)where.size();
 }
 
 // Host-kind batches: the listed keypoints from the extractor's own capture slot (written by k_tie_capture in front of the batch's final synchronisation) — a few
-// microseconds per keypoint, no device access; the whole-level download of fix_ties only when more keypoints are listed than the slot holds (widened bands)
+// microseconds per keypoint, no device access; the whole-level download of fix_ties only when more keypoints are listed than the slot holds (widened bands) or
+// when a sample misses a captured window (a camera that stretches the pattern beyond 40 px)
 static int fix_ties_host(mcs_extractor* e, int nties, uint8_t* h_desc, uint8_t* h_mask) {
 	const PyrDesc& hd = e->hd;
 	if (!e->hostTie.host || nties > kHostTieSlots) return fix_ties(e, nties, h_desc, h_mask);
 	std::vector<std::pair<int, int> > where;
 	std::vector<uint8_t> rows((size_t)nties * 2 * hd.descSize);
 	const int done = recompute_captured(e, e->hostTie.host, nties, e->h_cams, rows.data(), where);
+	if (done == kTieWindowMiss) return fix_ties(e, nties, h_desc, h_mask);   // this batch's levels are still resident: every listed keypoint from them instead
 	if (done < 0) return done;
 	for (int i = 0; i < done; ++i) {
 		const size_t r = ((size_t)where[i].first * hd.kpCap + where[i].second) * hd.descSize;
@@ -1224,6 +1229,8 @@ int mcs_extractor_patch_ties(mcs_extractor* e, int back, int* listed, int* recom
 	const ExtractBuffers& b = t.b;
 	std::vector<std::pair<int, int> > where;
 	const int done = recompute_captured(e, t.host, n, t.cams, e->h_patchRows, where);
+	// (no way back here: the pyramid buffers may hold a later batch already.  Nothing is patched, the slot stays unpatched)
+	if (done == kTieWindowMiss) return fail(MCS_ERR_UNSUPPORTED, "a pattern sample of a listed keypoint lies outside the captured 81 x 81 window (camera model with > 1.9x local magnification): use host-kind batches or mcs_extractor_fix_ties with this camera");
 	if (done < 0) return done;
 	for (int i = 0; i < done; ++i) {
 		const uint8_t* dsc = e->h_patchRows + (size_t)i * 2 * hd.descSize;
