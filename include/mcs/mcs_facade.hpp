@@ -977,4 +977,82 @@ int SearchReferencePointsInFrustum(Context& ctx, FR& F, std::vector<MP*>& vpLoca
 	return nrMatches + nmatches;
 }
 
+// ---------------------------------------------------------------------------------------------- the local map and the covisibility counts
+// cTracking::UpdateReferenceKeyFrames / UpdateReferencePoints (src/cTracking.cpp:1024-1123) and the counting and ordering of cMultiKeyFrame::UpdateConnections
+// (src/cMultiKeyFrame.cpp:406-500) over the device-resident observation store (mcs_covis_*).  KF: any type with `mnId`; map points are ids in [0, maxPoints),
+// -1 where the reference holds NULL.  Where the reference orders by heap address the store orders by mnId.
+template <class KF>
+class cCovisibility {
+public:
+	struct Reference {   // what UpdateReferenceKeyFrames / UpdateReferencePoints leave on the tracker
+		std::vector<KF*> mvpLocalKeyFrames; std::vector<int> mvpLocalKeyFramesCovWeights; std::vector<double> mvpLocalKeyFramesDistance2Frame;
+		KF* mpReferenceKF = nullptr; std::vector<int32_t> mvpLocalMapPoints; int32_t nPoints = 0;   // nPoints > cap: the list was cut at cap
+	};
+	struct Connections {   // what UpdateConnections leaves on the keyframe; unchanged: KFcounter was empty, the reference keeps its old lists
+		std::map<KF*, int> mConnectedKeyFrameWeights; std::vector<KF*> mvpOrderedConnectedKeyFrames; std::vector<int> mvOrderedWeights; bool unchanged = false;
+	};
+	cCovisibility(Context& ctx, int maxKeyFrames, int maxFeatures, int maxPoints) : maxPoints_(maxPoints) {
+		mcs_throw(mcs_covis_create(ctx.h, maxKeyFrames, maxFeatures, maxPoints, &h_));
+	}
+	~cCovisibility() { if (h_) mcs_covis_destroy(h_); }
+	cCovisibility(const cCovisibility&) = delete;
+	cCovisibility& operator=(const cCovisibility&) = delete;
+
+	void SetKeyFrame(KF* pKF, const std::vector<int32_t>& points) {
+		const int64_t id = (int64_t)pKF->mnId;
+		mcs_throw(mcs_covis_set_keyframe(h_, id, points.data(), (int)points.size(), MCS_MEM_HOST));
+		if (!obj_.count(id)) slots_.push_back(pKF);
+		obj_[id] = pKF;
+	}
+	void SetPose(KF* pKF, const double t[3]) { const int64_t id = (int64_t)pKF->mnId; mcs_throw(mcs_covis_set_keyframe_pose(h_, 1, &id, t, MCS_MEM_HOST)); }
+	void EraseKeyFrame(KF* pKF) { mcs_throw(mcs_covis_erase_keyframe(h_, (int64_t)pKF->mnId)); }
+	void SetBadFlag(KF* pKF, bool bad = true) { mcs_throw(mcs_covis_set_keyframe_bad(h_, (int64_t)pKF->mnId, bad ? 1 : 0)); }
+	void SetPointsBad(const std::vector<int32_t>& ids, bool bad = true) {
+		const std::vector<uint8_t> f(ids.size(), bad ? 1 : 0);
+		mcs_throw(mcs_covis_set_points_bad(h_, ids.data(), (int)ids.size(), f.data(), MCS_MEM_HOST));
+	}
+	void clear() { mcs_throw(mcs_covis_clear(h_)); obj_.clear(); slots_.clear(); }
+	int size() const { int n = 0; mcs_throw(mcs_covis_size(h_, &n)); return n; }
+	int slots() const { int n = 0; mcs_throw(mcs_covis_slots(h_, &n)); return n; }
+
+	// framePoints: mCurrentFrame.mvpMapPoints as ids, in/out (the entries of bad points become -1); frameT = Hom2T(mCurrentFrame.GetPose())
+	Reference UpdateReference(std::vector<int32_t>& framePoints, const double frameT[3], int cap = -1) {
+		const int S = slots();
+		if (cap < 0) cap = maxPoints_;
+		std::vector<int64_t> kfs((size_t)S + 1); std::vector<int32_t> w((size_t)S + 1), lp((size_t)cap + 1); std::vector<double> d((size_t)S + 1);
+		int32_t nl = 0, np = 0; int64_t ref = -1;
+		mcs_throw(mcs_covis_update_reference(h_, framePoints.data(), (int)framePoints.size(), frameT, cap, MCS_MEM_HOST, kfs.data(), w.data(), d.data(), &nl, &ref,
+		                                     lp.data(), &np));
+		Reference r;
+		for (int k = 0; k < nl; ++k) { r.mvpLocalKeyFrames.push_back(obj_.at(kfs[k])); r.mvpLocalKeyFramesCovWeights.push_back(w[k]); r.mvpLocalKeyFramesDistance2Frame.push_back(d[k]); }
+		r.mpReferenceKF = ref < 0 ? nullptr : obj_.at(ref);
+		r.nPoints = np;
+		r.mvpLocalMapPoints.assign(lp.begin(), lp.begin() + std::min(np, (int32_t)cap));
+		return r;
+	}
+	Connections UpdateConnections(KF* pKF) { return UpdateConnections(std::vector<KF*>{pKF})[0]; }
+	std::vector<Connections> UpdateConnections(const std::vector<KF*>& kfs) {   // the same calls one after another, in one device call
+		const size_t nq = kfs.size(), S = (size_t)slots();
+		std::vector<Connections> out(nq);
+		if (!nq) return out;
+		std::vector<int64_t> ids, od(nq * S); std::vector<int32_t> cnt(nq * S), nc(nq), ow(nq * S), no(nq);
+		for (KF* k : kfs) ids.push_back((int64_t)k->mnId);
+		mcs_throw(mcs_covis_update_connections(h_, (int)nq, ids.data(), MCS_MEM_HOST, cnt.data(), nc.data(), od.data(), ow.data(), no.data()));
+		for (size_t q = 0; q < nq; ++q) {
+			for (size_t k = 0; k < S; ++k)
+				if (cnt[q * S + k] > 0) out[q].mConnectedKeyFrameWeights[slots_[k]] = cnt[q * S + k];
+			out[q].unchanged = no[q] < 0;
+			for (int k = 0; k < no[q]; ++k) { out[q].mvpOrderedConnectedKeyFrames.push_back(obj_.at(od[q * S + k])); out[q].mvOrderedWeights.push_back(ow[q * S + k]); }
+		}
+		return out;
+	}
+	mcs_covis* handle() const { return h_; }
+
+private:
+	mcs_covis* h_ = nullptr;
+	int maxPoints_ = 0;
+	std::map<int64_t, KF*> obj_;
+	std::vector<KF*> slots_;   // slot -> keyframe, erased ones included (slot order is id order)
+};
+
 }  // namespace MultiColSLAM

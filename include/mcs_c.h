@@ -35,8 +35,8 @@ extern "C" {
  * since round 2 — callers built against an older header must be recompiled; mcs_describe_fast_table, FAST types 0 / 1 in round 3; 4: mcs_extractor_tie_stats; 5: mcs_copy_narrow,
  * mcs_ctx_result_stream, mcs_ctx_stream_conflicts, mcs_ctx_transfer_stream in round 4; 8: mcs_extractor_set_tie_capture / _patch_ties in round 6;
  * 9: the keyframe database mcs_kfdb_*, mcs_vocabulary_set_words, mcs_bow_vector; 10: the Sim3 RANSAC mcs_sim3_*).  Purely additive
- * entry points leave it alone: mcs_triangulate_matches / mcs_create_new_map_points and mcs_frustum / mcs_search_local_points arrived within revision 10 (look
- * them up with dlsym).  mcs_abi_version() returns the value the LIBRARY was built with: compare it with MCS_ABI_VERSION after dlopen. */
+ * entry points leave it alone: mcs_triangulate_matches / mcs_create_new_map_points and mcs_frustum / mcs_search_local_points arrived within revision 10, as did the
+ * covisibility store mcs_covis_* with mcs_gather_rows / mcs_scatter_rows (look them up with dlsym).  mcs_abi_version() returns the value the LIBRARY was built with: compare it with MCS_ABI_VERSION after dlopen. */
 #define MCS_ABI_VERSION 10
 
 #define MCS_MAX_POLY 16
@@ -570,6 +570,67 @@ int mcs_frustum(mcs_ctx*, const mcs_local_points* pts, const mcs_rig_view* rig, 
 int mcs_search_local_points(mcs_ctx*, const mcs_local_points* pts, const mcs_rig_view* rig, const mcs_track_state* state, const uint8_t* desc,
                             const uint8_t* mask, int stride, const mcs_frame_view* frame, double th, double nnratio, int dim, mcs_mem_kind kind,
                             int32_t* match, int32_t* nmatches, int32_t* n_to_match, int32_t* visible_inc);
+
+/* ------------------------------------------------------------------ the local map and the covisibility counts on the device
+ * cTracking::UpdateReferenceKeyFrames + UpdateReferencePoints (src/cTracking.cpp:1024-1123), the first step of TrackLocalMap, and the counting and ordering of
+ * cMultiKeyFrame::UpdateConnections (src/cMultiKeyFrame.cpp:406-500) over a device-resident observation store: one row of map point ids per keyframe.
+ * ASSUMPTION: map point p is observed by exactly those live keyframes whose row holds p (the reference keeps mObservations and mvpMapPoints in step except between
+ * two statements; a caller that wants another observation set passes other rows).  DEVIATION: where the reference orders by heap address (the iteration order of
+ * std::map<cMultiKeyFrame*, ...>, the sort of pair<int, cMultiKeyFrame*>) the store orders by mnId, "as if keyframes were allocated at ascending addresses": this
+ * decides the order of the local keyframes, ties for the reference keyframe / pKFmax, and ties among equal weights — nothing else (DESIGN.md sections 4h, 7).
+ *   mcs_covis_create            capacities are fixed: max_keyframes slots, rows of at most max_features entries, map point ids in [0, max_points).  Exceeding one
+ *                               returns MCS_ERR_CAPACITY and changes nothing.
+ *   mcs_covis_clear             forget every keyframe and every point's bad flag;  _size: live keyframes;  _slots: slots, erased ones included — the length
+ *                               of the per-slot outputs below
+ *   mcs_covis_set_keyframe      add keyframe mnId or replace its row.  points[n] = mvpMapPoints as ids, -1 for NULL (host kind: an id outside [-1, max_points) is
+ *                               MCS_ERR_INVALID; device kind: it reads -1).  A NEW mnId must exceed every id present (the reference's nNextId++), so slot order is
+ *                               id order; erased slots stay as holes until _clear and their ids cannot come back.  The store also keeps the row with every
+ *                               repeated point replaced by -1 (built on the device): a multi-camera keyframe holds one point at several features, the
+ *                               reference's observations map holds the keyframe once.  A new keyframe is not bad and has pose translation 0.
+ *   mcs_covis_set_keyframe_pose t[i] = Hom2T(GetPose()) of keyframe mnIds[i]; mnIds is host memory, t lives where `kind` says
+ *   mcs_covis_erase_keyframe    the keyframe leaves the store (its points are no longer observed by it)
+ *   mcs_covis_set_keyframe_bad  cMultiKeyFrame::isBad()
+ *   mcs_covis_set_points_bad    cMapPoint::isBad() of the listed points (ids / bad live where `kind` says)
+ * The shared count, for a voter row Q (the frame's mvpMapPoints, or a keyframe's row): mult[p] = entries of Q equal to p whose point is not bad — both reference
+ * loops run per FEATURE, so a point held at two features votes twice (reproduced) —, count[k] = sum of mult[p] over the DISTINCT points of live keyframe k.  There
+ * is no bad test on the keyframe side (the reference has none).
+ *   mcs_covis_update_reference  frame_points[nf] in/out: a bad point's entry becomes -1 (:1072-1075).  frame_t[3] = Hom2T(mCurrentFrame.GetPose()).  With
+ *                               S = _slots: local_kfs / local_weights / local_dist[S] = mvpLocalKeyFrames (mnIds, ascending) / ...CovWeights /
+ *                               ...Distance2Frame = sqrt(((0 + dx^2) + dy^2) + dz^2) in FP64: every keyframe with count > 4 that is not bad; entries from
+ *                               n_local on read -1 / 0 / 0.0.  ref_kf = the first of them with the strictly greatest count, -1 if there is none (the reference
+ *                               then holds NULL).  local_points[cap] = mvpLocalMapPoints as ids, in the reference's order (local keyframes in order, each one's
+ *                               full row in feature order, -1 and bad points skipped, a point at its first occurrence only); entries from n_points on read -1.
+ *                               n_points is the FULL count: above cap the first cap entries are written.
+ *   mcs_covis_update_connections for each of nq keyframes mnIds[q] (host memory): count[q*S + slot] = KFcounter (0 = absent; the keyframe's own slot and erased
+ *                               slots read 0), n_counted[q] = KFcounter.size(); ordered / ordered_w[q*S ..] = mvpOrderedConnectedKeyFrames / mvOrderedWeights,
+ *                               which are also the (keyframe, weight) pairs handed to AddConnection: every keyframe with count >= 30, or, if there is none, the
+ *                               first keyframe of the greatest count; descending weight, ties by descending mnId; the rest reads -1 / 0.  n_ordered[q] = their
+ *                               number, or -1 where KFcounter is empty (the reference returns and leaves the old lists).  The store keeps no graph: applying
+ *                               AddConnection to the other keyframes and the parent / child bookkeeping stay with the caller.  A batch equals the sequence.
+ * kind: where the array arguments live.  DEVICE: the two update calls only enqueue work on the context's stream (no host wait, no count read back); HOST: they go
+ * through the context's staging block and end with a synchronisation.  Both are refused with MCS_ERR_UNSUPPORTED while deferred searches are on. */
+typedef struct mcs_covis mcs_covis;
+int mcs_covis_create(mcs_ctx*, int max_keyframes, int max_features, int max_points, mcs_covis** out);
+int mcs_covis_destroy(mcs_covis*);
+int mcs_covis_clear(mcs_covis*);
+int mcs_covis_size(const mcs_covis*, int* n);
+int mcs_covis_slots(const mcs_covis*, int* n);
+int mcs_covis_set_keyframe(mcs_covis*, int64_t mnId, const int32_t* points, int n, mcs_mem_kind kind);
+int mcs_covis_set_keyframe_pose(mcs_covis*, int n, const int64_t* mnIds, const double* t, mcs_mem_kind kind);
+int mcs_covis_erase_keyframe(mcs_covis*, int64_t mnId);
+int mcs_covis_set_keyframe_bad(mcs_covis*, int64_t mnId, int bad);
+int mcs_covis_set_points_bad(mcs_covis*, const int32_t* ids, int n, const uint8_t* bad, mcs_mem_kind kind);
+int mcs_covis_update_reference(mcs_covis*, int32_t* frame_points, int nf, const double* frame_t, int cap, mcs_mem_kind kind, int64_t* local_kfs,
+                               int32_t* local_weights, double* local_dist, int32_t* n_local, int64_t* ref_kf, int32_t* local_points, int32_t* n_points);
+int mcs_covis_update_connections(mcs_covis*, int nq, const int64_t* mnIds, mcs_mem_kind kind, int32_t* count, int32_t* n_counted, int64_t* ordered,
+                                 int32_t* ordered_w, int32_t* n_ordered);
+/* device helpers (all pointers but fill_row on the context's GPU; both only enqueue on the context's stream):
+ *   mcs_gather_rows   dst row i = src row idx[i]; where idx[i] < 0, fill_row (HOST pointer to row_bytes bytes; NULL: zeros).  row_bytes <= 256.
+ *   mcs_scatter_rows  dst row idx[i] = src row i; negative indices are skipped.
+ * With the per-point arrays gathered through local_points (flags with fill MCS_LP_BAD) the padded list goes straight into mcs_search_local_points with n = cap: a
+ * bad point is skipped by both of its loops, so the padding neither matches nor blocks; the tracking state is scattered back afterwards. */
+int mcs_gather_rows(mcs_ctx*, const int32_t* idx, int n, const void* src, int row_bytes, const void* fill_row, void* dst);
+int mcs_scatter_rows(mcs_ctx*, const int32_t* idx, int n, const void* src, int row_bytes, void* dst);
 
 /* self-test of an arithmetic shortcut of the descriptor kernel: the omni model's three divisions by the same norm (src/cam_model_omni.cpp:
  * 146-161) share one refined reciprocal; this runs n pseudo-random (numerator, denominator) pairs of the magnitudes the kernel sees through

@@ -78,6 +78,9 @@ EXPORTS = [
     "mcs_sim3_hypotheses", "mcs_sim3_draw",
     "mcs_triangulate_matches", "mcs_create_new_map_points",
     "mcs_frustum", "mcs_search_local_points",
+    "mcs_covis_create", "mcs_covis_destroy", "mcs_covis_clear", "mcs_covis_size", "mcs_covis_slots", "mcs_covis_set_keyframe", "mcs_covis_set_keyframe_pose",
+    "mcs_covis_erase_keyframe", "mcs_covis_set_keyframe_bad", "mcs_covis_set_points_bad", "mcs_covis_update_reference", "mcs_covis_update_connections",
+    "mcs_gather_rows", "mcs_scatter_rows",
 ]
 
 WINDOW_RATIO, WINDOW_BEST, WINDOW_INITIALIZE = 1, 2, 3
@@ -235,6 +238,20 @@ def lib():
     L.mcs_frustum.argtypes = [vp, C.POINTER(LocalPoints), C.POINTER(RigView), vp, C.c_int, C.POINTER(TrackState), C.c_int, vp, vp]
     L.mcs_search_local_points.argtypes = [vp, C.POINTER(LocalPoints), C.POINTER(RigView), C.POINTER(TrackState), vp, vp, C.c_int, C.POINTER(FrameView),
                                           C.c_double, C.c_double, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.mcs_covis_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
+    L.mcs_covis_destroy.argtypes = [vp]
+    L.mcs_covis_clear.argtypes = [vp]
+    L.mcs_covis_size.argtypes = [vp, i32p]
+    L.mcs_covis_slots.argtypes = [vp, i32p]
+    L.mcs_covis_set_keyframe.argtypes = [vp, C.c_int64, vp, C.c_int, C.c_int]
+    L.mcs_covis_set_keyframe_pose.argtypes = [vp, C.c_int, vp, vp, C.c_int]
+    L.mcs_covis_erase_keyframe.argtypes = [vp, C.c_int64]
+    L.mcs_covis_set_keyframe_bad.argtypes = [vp, C.c_int64, C.c_int]
+    L.mcs_covis_set_points_bad.argtypes = [vp, vp, C.c_int, vp, C.c_int]
+    L.mcs_covis_update_reference.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+    L.mcs_covis_update_connections.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp]
+    L.mcs_gather_rows.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp]
+    L.mcs_scatter_rows.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp]
     L.mcs_copy_narrow.argtypes = [vp, vp, vp, C.c_size_t, C.c_int, vp]
     L.mcs_ctx_result_stream.argtypes = [vp, C.POINTER(vp)]
     L.mcs_ctx_stream_conflicts.argtypes = [vp, vp, C.POINTER(C.c_uint)]

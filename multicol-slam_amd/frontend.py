@@ -10,6 +10,7 @@
   cSim3Solver (+ cSim3SolverBatch)     src/cSim3Solver.cpp (the RANSAC of cLoopClosing::ComputeSim3, one round over many candidates per call)
   CreateNewMapPoints                   src/cLocalMapping.cpp:223-381 (the mapping thread's neighbour loop: search, triangulation and checks in one call)
   cMultiFrame.isInFrustum, SearchReferencePointsInFrustum   src/cMultiFrame.cpp:218-270, src/cTracking.cpp:953-1012 (the search step of TrackLocalMap in one call)
+  cCovisibility, TrackLocalMapSearch   src/cTracking.cpp:1024-1123, src/cMultiKeyFrame.cpp:406-500 (local map and covisibility counts from a device-resident store)
 
 Everything numeric runs in libmcs_hip.so on the GPU; this file only shapes inputs/outputs (numpy stands in for cv::Mat).
 """
@@ -1267,3 +1268,243 @@ class cSim3Solver:
 
     def GetEstimatedScale(self):
         return float(self._b().best()[2][self._slot])
+
+
+# ---------------------------------------------------------------------------------------------- the local map and the covisibility counts (mcs_covis_*)
+_hiprt = None
+
+
+def _hip():
+    """the HIP runtime libmcs_hip.so is linked with (already in the process): device arrays for the device-kind chain of TrackLocalMapSearch"""
+    global _hiprt
+    if _hiprt is None:
+        lib()
+        _hiprt = C.CDLL("libamdhip64.so")
+        _hiprt.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+        _hiprt.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        _hiprt.hipFree.argtypes = [C.c_void_p]
+    return _hiprt
+
+
+class DeviceArray:
+    """a numpy array's copy in device memory: .ptr for device-kind calls, .read() synchronises and copies it back"""
+
+    def __init__(self, arr):
+        self.arr = np.ascontiguousarray(arr)
+        self.ptr = C.c_void_p()
+        if _hip().hipMalloc(C.byref(self.ptr), max(self.arr.nbytes, 16)) != 0:
+            raise MemoryError("hipMalloc of %d bytes failed" % self.arr.nbytes)
+        if self.arr.nbytes and _hip().hipMemcpy(self.ptr, self.arr.ctypes.data_as(C.c_void_p), self.arr.nbytes, 1) != 0:
+            raise RuntimeError("hipMemcpy to the device failed")
+
+    def read(self):
+        out = np.empty_like(self.arr)
+        if _hip().hipDeviceSynchronize() != 0 or (out.nbytes and _hip().hipMemcpy(out.ctypes.data_as(C.c_void_p), self.ptr, out.nbytes, 2) != 0):
+            raise RuntimeError("hipMemcpy from the device failed")
+        return out
+
+    def __del__(self):
+        try:
+            if self.ptr:
+                _hip().hipFree(self.ptr)
+        except Exception:
+            pass
+
+
+def _point_ids(points):
+    """mvpMapPoints as ids: None / -1 -> -1, an int, or a map point's mnId"""
+    return np.array([-1 if m is None else int(getattr(m, "mnId", m)) for m in points], np.int32)
+
+
+def _kf_id(kf):
+    return int(getattr(kf, "mnId", kf))
+
+
+class cCovisibility:
+    """The observation store behind cTracking::UpdateReferenceKeyFrames / UpdateReferencePoints (src/cTracking.cpp:1024-1123) and
+    cMultiKeyFrame::UpdateConnections (src/cMultiKeyFrame.cpp:406-500) on the device (mcs_covis_*): one row of map point ids per keyframe.  Keyframes are
+    objects with mnId (and GetMapPointMatches() / GetCameraCenter() where no array is given) or plain ids; map points are objects with mnId or plain ids
+    in [0, max_points).  Where the reference orders by heap address the store orders by mnId."""
+
+    def __init__(self, max_keyframes, max_features, max_points, ctx=None):
+        self.ctx = ctx or default_context()
+        self.h = C.c_void_p()
+        check(lib().mcs_covis_create(self.ctx.h, int(max_keyframes), int(max_features), int(max_points), C.byref(self.h)))
+        self.max_points = int(max_points)
+        self.slot_ids = []   # mnId of every slot, erased ones included (slot order is id order)
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().mcs_covis_destroy(self.h)
+        except Exception:
+            pass
+
+    def _n(self, fn):
+        n = C.c_int32()
+        check(fn(self.h, C.byref(n)))
+        return n.value
+
+    def size(self):
+        return self._n(lib().mcs_covis_size)
+
+    def slots(self):
+        return self._n(lib().mcs_covis_slots)
+
+    def clear(self):
+        check(lib().mcs_covis_clear(self.h))
+        self.slot_ids = []
+
+    def SetKeyFrame(self, pKF, points=None):
+        """add the keyframe or replace its row (points: default pKF.GetMapPointMatches())"""
+        ids = _point_ids(pKF.GetMapPointMatches() if points is None else points)
+        check(lib().mcs_covis_set_keyframe(self.h, _kf_id(pKF), np_ptr(ids), len(ids), MEM_HOST))
+        if not self.slot_ids or _kf_id(pKF) > self.slot_ids[-1]:
+            self.slot_ids.append(_kf_id(pKF))
+
+    def SetPose(self, kfs, ts=None):
+        """Hom2T(GetPose()) of the listed keyframes (ts: default their GetCameraCenter())"""
+        kfs = list(kfs)
+        ids = np.array([_kf_id(k) for k in kfs], np.int64)
+        t = np.ascontiguousarray([np.asarray(k.GetCameraCenter(), np.float64).reshape(-1)[:3] for k in kfs] if ts is None else ts, np.float64).reshape(len(kfs), 3)
+        check(lib().mcs_covis_set_keyframe_pose(self.h, len(kfs), np_ptr(ids), np_ptr(t), MEM_HOST))
+
+    def EraseKeyFrame(self, pKF):
+        check(lib().mcs_covis_erase_keyframe(self.h, _kf_id(pKF)))
+
+    def SetBadFlag(self, pKF, bad=True):
+        check(lib().mcs_covis_set_keyframe_bad(self.h, _kf_id(pKF), int(bool(bad))))
+
+    def SetPointsBad(self, points, bad=True):
+        ids = _point_ids(points)
+        flags = np.ascontiguousarray(np.broadcast_to(np.asarray(bad, bool), ids.shape), np.uint8)
+        check(lib().mcs_covis_set_points_bad(self.h, np_ptr(ids), len(ids), np_ptr(flags), MEM_HOST))
+
+    def UpdateReference(self, F, frame_t=None, cap=None):
+        """UpdateReferenceKeyFrames + UpdateReferencePoints for frame F: an object with mvpMapPoints (entries of bad points become None, as in the reference) and
+        camSystem.M_t, or an array of point ids together with frame_t.  -> dict(frame_points, local_kfs, weights, dists, ref_kf (-1: none), local_points,
+        n_points); n_points above cap means the list was cut at cap."""
+        obj = hasattr(F, "mvpMapPoints")
+        fp = _point_ids(F.mvpMapPoints if obj else F)
+        t = np.ascontiguousarray(np.asarray(F.camSystem.M_t, np.float64)[:3, 3] if frame_t is None else frame_t, np.float64).reshape(3)
+        S = self.slots()
+        cap = self.max_points if cap is None else int(cap)
+        kfs, w, d = np.zeros(max(S, 1), np.int64), np.zeros(max(S, 1), np.int32), np.zeros(max(S, 1))
+        nl, ref, npnt = np.zeros(1, np.int32), np.zeros(1, np.int64), np.zeros(1, np.int32)
+        lp = np.zeros(max(cap, 1), np.int32)
+        check(lib().mcs_covis_update_reference(self.h, np_ptr(fp), len(fp), np_ptr(t), cap, MEM_HOST, np_ptr(kfs), np_ptr(w), np_ptr(d), np_ptr(nl), np_ptr(ref),
+                                               np_ptr(lp), np_ptr(npnt)))
+        if obj:
+            for i in np.flatnonzero(fp < 0):
+                F.mvpMapPoints[int(i)] = None
+        n = int(nl[0])
+        return dict(frame_points=fp, local_kfs=kfs[:n].tolist(), weights=w[:n].tolist(), dists=d[:n].tolist(), ref_kf=int(ref[0]),
+                    local_points=lp[:min(int(npnt[0]), cap)].tolist(), n_points=int(npnt[0]))
+
+    def UpdateConnections(self, kfs):
+        """the counting and ordering of UpdateConnections for every listed keyframe, in one call -> per keyframe dict(counter {mnId: count}, ordered, weights);
+        ordered / weights are None where KFcounter is empty (the reference leaves its lists unchanged).  ordered[:N] is GetBestCovisibilityKeyFrames(N)."""
+        kfs = list(kfs)
+        nq, S = len(kfs), self.slots()
+        if nq == 0:
+            return []
+        ids = np.array([_kf_id(k) for k in kfs], np.int64)
+        cnt, nc = np.zeros(nq * S, np.int32), np.zeros(nq, np.int32)
+        od, ow, no = np.zeros(nq * S, np.int64), np.zeros(nq * S, np.int32), np.zeros(nq, np.int32)
+        check(lib().mcs_covis_update_connections(self.h, nq, np_ptr(ids), MEM_HOST, np_ptr(cnt), np_ptr(nc), np_ptr(od), np_ptr(ow), np_ptr(no)))
+        out = []
+        for q in range(nq):
+            n, c = int(no[q]), cnt[q * S:(q + 1) * S]
+            counter = {self.slot_ids[int(k)]: int(c[k]) for k in np.flatnonzero(c)}   # KFcounter: the counts come per slot
+            assert len(counter) == int(nc[q])
+            out.append(dict(counter=counter, ordered=None if n < 0 else od[q * S:q * S + n].tolist(), weights=None if n < 0 else ow[q * S:q * S + n].tolist()))
+        return out
+
+
+def TrackLocalMapSearch(F, store, points, th=3, nnratio=0.8, featDim=32, havingMasks=False, cap=None, ctx=None):
+    """The first two steps of cTracking::TrackLocalMap (src/cTracking.cpp:834-848) as ONE chain of device-kind calls, nothing in between visiting the host:
+    mcs_covis_update_reference -> mcs_gather_rows of the per-point tables through the local list -> mcs_search_local_points on the padded list (n = cap) ->
+    mcs_scatter_rows of the tracking state.
+    F: a cMultiFrame whose mvpMapPoints holds map point ids (or objects with mnId) or None.  points: the per-point tables indexed by map point id —
+    pos / normal [n][3], min_dist / max_dist [n], flags [n] (LP_BAD; LP_SEEN is set here), desc (/ mask) [n][featDim], in_view / proj_x / proj_y / level /
+    view_cos [n][nr_cams]; the tracking state is updated in place.  The frame's first loop (:957-976) runs here on the arrays.
+    -> dict(nmatches (the reference's return value), n_to_match, local_kfs, weights, dists, ref_kf, local_points, n_points, match [cap][nr_cams],
+    visible_inc [n] (IncreaseVisible() calls per point id, first loop included), frame_points)"""
+    from ._capi import LP_BAD, LP_SEEN, FrameView, LocalPoints, RigView, TrackState
+    ctx = ctx or store.ctx
+    L = lib()
+    nr = F.camSystem.GetNrCams()
+    npts = len(points["flags"])
+    cap = npts if cap is None else int(cap)
+    fp = _point_ids(F.mvpMapPoints)
+    fcam = np.ascontiguousarray(F.keypoint_to_cam, np.int32)
+    flags = np.ascontiguousarray(points["flags"], np.uint8).copy()
+    vis_first = np.zeros(npts, np.int32)
+    first = 0
+    for i in np.flatnonzero(fp >= 0):                 # :957-976 (the entries of bad points are nulled by the device call below, as :1072-1075 did before)
+        p = int(fp[i])
+        if flags[p] & LP_BAD:
+            continue
+        vis_first[p] += 1
+        flags[p] |= LP_SEEN
+        points["in_view"][p, int(fcam[i])] = 0
+        first += 1
+    assigned = np.array([p >= 0 and not (flags[p] & LP_BAD) for p in fp] or [0], np.uint8)
+    S = store.slots()
+    dev = DeviceArray
+    tab = {k: dev(np.ascontiguousarray(points[k], dt)) for k, dt in (("pos", np.float64), ("normal", np.float64), ("min_dist", np.float64), ("max_dist", np.float64),
+                                                                  ("desc", np.uint8), ("in_view", np.uint8), ("proj_x", np.float64), ("proj_y", np.float64),
+                                                                  ("level", np.int32), ("view_cos", np.float64))}
+    tab["flags"] = dev(flags)
+    if havingMasks:
+        tab["mask"] = dev(np.ascontiguousarray(points["mask"], np.uint8))
+    d_fp, d_t = dev(fp), dev(np.ascontiguousarray(np.asarray(F.camSystem.M_t, np.float64)[:3, 3]))
+    o = dict(kfs=dev(np.zeros(max(S, 1), np.int64)), w=dev(np.zeros(max(S, 1), np.int32)), d=dev(np.zeros(max(S, 1))), nl=dev(np.zeros(1, np.int32)),
+             ref=dev(np.zeros(1, np.int64)), lp=dev(np.zeros(max(cap, 1), np.int32)), np=dev(np.zeros(1, np.int32)))
+    check(L.mcs_covis_update_reference(store.h, d_fp.ptr, len(fp), d_t.ptr, cap, MEM_DEVICE, o["kfs"].ptr, o["w"].ptr, o["d"].ptr, o["nl"].ptr, o["ref"].ptr,
+                                       o["lp"].ptr, o["np"].ptr))
+    g = {}
+    for k, a in tab.items():                          # the padded local list: row i = the table's row local_points[i]; the padding reads "bad"
+        row = a.arr.nbytes // max(npts, 1)
+        g[k] = dev(np.zeros((max(cap, 1),) + a.arr.shape[1:], a.arr.dtype))
+        fill = np.array([LP_BAD], np.uint8) if k == "flags" else None
+        check(L.mcs_gather_rows(ctx.h, o["lp"].ptr, cap, a.ptr, row, np_ptr(fill), g[k].ptr))
+    rig = _rig_arrays(F.camSystem)
+    keep = [dev(rig["MtMc_inv"]), dev(rig["MtMc"]), dev(np.frombuffer(rig["ocs"], np.uint8).copy())]
+    mp = None
+    if all(m is not None for m in rig["masks"]):
+        md = [dev(m) for m in rig["masks"]]
+        mp = dev(np.array([m.ptr.value for m in md], np.uint64))
+        keep += md + [mp]
+    rv = RigView(keep[0].ptr, keep[1].ptr, keep[2].ptr, mp.ptr if mp else None, nr)
+    lpv = LocalPoints(g["pos"].ptr, g["normal"].ptr, g["min_dist"].ptr, g["max_dist"].ptr, g["flags"].ptr, cap)
+    ts = TrackState(*[g[k].ptr for k in ("in_view", "proj_x", "proj_y", "level", "view_cos")])
+    sc = np.ascontiguousarray(F.mvScaleFactors, np.float64)
+    fa = [dev(np.ascontiguousarray(F.mvKeys)), dev(np.ascontiguousarray(F.all_descriptors(), np.uint8)),
+          dev(np.ascontiguousarray(F.all_masks(), np.uint8)) if havingMasks else None, dev(fcam), dev(assigned), dev(np.ascontiguousarray(F.mnMaxX, np.int32)),
+          dev(np.ascontiguousarray(F.mnMaxY, np.int32)), dev(sc)]
+    fv = FrameView(fa[0].ptr, fa[1].ptr, fa[2].ptr if fa[2] else None, fa[3].ptr, fa[4].ptr, F.totalN, featDim, nr, fa[5].ptr, fa[6].ptr, fa[7].ptr, len(sc))
+    res = dict(match=dev(np.full(max(cap * nr, 1), -1, np.int32)), nm=dev(np.zeros(1, np.int32)), ntm=dev(np.zeros(1, np.int32)), vis=dev(np.zeros(max(cap, 1), np.int32)))
+    check(L.mcs_search_local_points(ctx.h, C.byref(lpv), C.byref(rv), C.byref(ts), g["desc"].ptr, g["mask"].ptr if havingMasks else None, featDim, C.byref(fv),
+                                    float(th), float(nnratio), featDim, MEM_DEVICE, res["match"].ptr, res["nm"].ptr, res["ntm"].ptr, res["vis"].ptr))
+    for k in ("in_view", "proj_x", "proj_y", "level", "view_cos"):
+        check(L.mcs_scatter_rows(ctx.h, o["lp"].ptr, cap, g[k].ptr, tab[k].arr.nbytes // max(npts, 1), tab[k].ptr))
+    # ---- only now the host looks at anything
+    n_points = int(o["np"].read()[0])
+    lp = o["lp"].read()[:cap]
+    for k in ("in_view", "proj_x", "proj_y", "level", "view_cos"):
+        points[k][...] = tab[k].read().reshape(points[k].shape)
+    vis = vis_first.copy()
+    used = min(n_points, cap)
+    np.add.at(vis, lp[:used], res["vis"].read()[:used])
+    n = int(o["nl"].read()[0])
+    fp_after = d_fp.read()
+    match = res["match"].read()[:cap * nr].reshape(cap, nr)
+    for i in np.flatnonzero(fp_after < 0):
+        F.mvpMapPoints[int(i)] = None
+    for i, c in zip(*np.nonzero(match >= 0)):
+        F.mvpMapPoints[int(match[i, c])] = int(lp[i])            # F.mvpMapPoints[bestIdx] = pMP, src/cORBmatcher.cpp:159
+    nm = int(res["nm"].read()[0])
+    return dict(nmatches=first + nm, search_matches=nm, n_to_match=int(res["ntm"].read()[0]), local_kfs=o["kfs"].read()[:n].tolist(), weights=o["w"].read()[:n].tolist(),
+                dists=o["d"].read()[:n].tolist(), ref_kf=int(o["ref"].read()[0]), local_points=lp[:used].tolist(), n_points=n_points, match=match,
+                visible_inc=vis, search_visible_inc=res["vis"].read()[:cap], frame_points=fp_after)
