@@ -979,7 +979,8 @@ int SearchReferencePointsInFrustum(Context& ctx, FR& F, std::vector<MP*>& vpLoca
 
 // ---------------------------------------------------------------------------------------------- the local map and the covisibility counts
 // cTracking::UpdateReferenceKeyFrames / UpdateReferencePoints (src/cTracking.cpp:1024-1123) and the counting and ordering of cMultiKeyFrame::UpdateConnections
-// (src/cMultiKeyFrame.cpp:406-500) over the device-resident observation store (mcs_covis_*).  KF: any type with `mnId`; map points are ids in [0, maxPoints),
+// (src/cMultiKeyFrame.cpp:406-500), cLocalMapping::KeyFrameCulling / MapPointCulling (src/cLocalMapping.cpp:517-593, 187-221) over the device-resident
+// observation store (mcs_covis_*).  KF: any type with `mnId`; map points are ids in [0, maxPoints),
 // -1 where the reference holds NULL.  Where the reference orders by heap address the store orders by mnId.
 template <class KF>
 class cCovisibility {
@@ -1045,6 +1046,56 @@ public:
 			for (int k = 0; k < no[q]; ++k) { out[q].mvpOrderedConnectedKeyFrames.push_back(obj_.at(od[q * S + k])); out[q].mvOrderedWeights.push_back(ow[q * S + k]); }
 		}
 		return out;
+	}
+	// ---- cLocalMapping::KeyFrameCulling / MapPointCulling (src/cLocalMapping.cpp:517-593, 187-221)
+	struct Culling {   // what KeyFrameCulling decided: SetBadFlag() these / mbToBeErased for these / the map points that went bad on the way
+		std::vector<KF*> vpToSetBad, vpToBeErased; std::vector<int32_t> vBadPoints;
+		std::vector<int32_t> verdict, nMPs, nRedundantObservations;   // per listed keyframe (verdict: 0 kept, 1 culled, 2 to be erased, 3 mnId == 0)
+	};
+	// octaves[i] = pKF->GetKeyPoint(i).octave
+	void SetOctaves(KF* pKF, const std::vector<uint8_t>& octaves) {
+		mcs_throw(mcs_covis_set_keyframe_octaves(h_, (int64_t)pKF->mnId, octaves.data(), (int)octaves.size(), MCS_MEM_HOST));
+	}
+	// vpLocalKeyFrames = mpCurrentMultiKeyFrame->GetVectorCovisibleKeyFrames(), in that order; notErase: mbNotErase per keyframe (empty: none).  Culled keyframes
+	// and bad points are flagged in the store; the keyframes are NOT erased: the caller runs SetBadFlag() on vpToSetBad (spanning tree, mpMap, keyframe
+	// database) and EraseKeyFrame() here.
+	Culling KeyFrameCulling(const std::vector<KF*>& vpLocalKeyFrames, const std::vector<uint8_t>& notErase = std::vector<uint8_t>(), int cap = -1) {
+		const size_t n = vpLocalKeyFrames.size();
+		if (cap < 0) cap = maxPoints_;
+		std::vector<int64_t> ids;
+		for (KF* k : vpLocalKeyFrames) ids.push_back((int64_t)k->mnId);
+		Culling r;
+		r.verdict.assign(n + 1, 0); r.nMPs.assign(n + 1, 0); r.nRedundantObservations.assign(n + 1, 0);
+		std::vector<int32_t> bp((size_t)cap + 1);
+		int32_t nb = 0;
+		mcs_throw(mcs_covis_cull_keyframes(h_, (int)n, ids.data(), notErase.size() == n && n ? notErase.data() : nullptr, cap, MCS_MEM_HOST, r.verdict.data(),
+		                                   r.nMPs.data(), r.nRedundantObservations.data(), bp.data(), &nb));
+		r.verdict.resize(n); r.nMPs.resize(n); r.nRedundantObservations.resize(n);
+		for (size_t k = 0; k < n; ++k) {
+			if (r.verdict[k] == 1) r.vpToSetBad.push_back(vpLocalKeyFrames[k]);
+			if (r.verdict[k] == 2) r.vpToBeErased.push_back(vpLocalKeyFrames[k]);
+		}
+		r.vBadPoints.assign(bp.begin(), bp.begin() + std::min(nb, (int32_t)cap));
+		return r;
+	}
+	// cMapPoint::Observations() of the listed points (0 for a bad one)
+	std::vector<int32_t> Observations(const std::vector<int32_t>& points) {
+		std::vector<int32_t> n(points.size());
+		mcs_throw(mcs_covis_observations(h_, points.data(), (int)points.size(), MCS_MEM_HOST, n.data()));
+		return n;
+	}
+	// recent = mlpRecentAddedMapPoints as ids (distinct), with mnFound / mnVisible / mnFirstKFid per entry; the points that stay remain in `recent`, the
+	// verdicts (0 stays, 1 was bad, 2 / 3 SetBadFlag, 4 old enough) come back per entry of the list as it was
+	std::vector<int32_t> MapPointCulling(KF* pCurrentKF, std::vector<int32_t>& recent, const std::vector<int32_t>& found, const std::vector<int32_t>& visible,
+	                                     const std::vector<int64_t>& firstKFid) {
+		std::vector<int32_t> v(recent.size());
+		mcs_throw(mcs_covis_cull_points(h_, (int64_t)pCurrentKF->mnId, (int)recent.size(), recent.data(), found.data(), visible.data(), firstKFid.data(), MCS_MEM_HOST,
+		                                v.data()));
+		std::vector<int32_t> rest;
+		for (size_t i = 0; i < recent.size(); ++i)
+			if (v[i] == 0) rest.push_back(recent[i]);
+		recent.swap(rest);
+		return v;
 	}
 	mcs_covis* handle() const { return h_; }
 

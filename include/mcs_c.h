@@ -36,7 +36,8 @@ extern "C" {
  * mcs_ctx_result_stream, mcs_ctx_stream_conflicts, mcs_ctx_transfer_stream in round 4; 8: mcs_extractor_set_tie_capture / _patch_ties in round 6;
  * 9: the keyframe database mcs_kfdb_*, mcs_vocabulary_set_words, mcs_bow_vector; 10: the Sim3 RANSAC mcs_sim3_*).  Purely additive
  * entry points leave it alone: mcs_triangulate_matches / mcs_create_new_map_points and mcs_frustum / mcs_search_local_points arrived within revision 10, as did the
- * covisibility store mcs_covis_* with mcs_gather_rows / mcs_scatter_rows (look them up with dlsym).  mcs_abi_version() returns the value the LIBRARY was built with: compare it with MCS_ABI_VERSION after dlopen. */
+ * covisibility store mcs_covis_* with mcs_gather_rows / mcs_scatter_rows and its culling calls mcs_covis_set_keyframe_octaves / _cull_keyframes / _observations / _cull_points
+ * (look them up with dlsym).  mcs_abi_version() returns the value the LIBRARY was built with: compare it with MCS_ABI_VERSION after dlopen. */
 #define MCS_ABI_VERSION 10
 
 #define MCS_MAX_POLY 16
@@ -624,6 +625,50 @@ int mcs_covis_update_reference(mcs_covis*, int32_t* frame_points, int nf, const 
                                int32_t* local_weights, double* local_dist, int32_t* n_local, int64_t* ref_kf, int32_t* local_points, int32_t* n_points);
 int mcs_covis_update_connections(mcs_covis*, int nq, const int64_t* mnIds, mcs_mem_kind kind, int32_t* count, int32_t* n_counted, int64_t* ordered,
                                  int32_t* ordered_w, int32_t* n_ordered);
+/* cLocalMapping::KeyFrameCulling (src/cLocalMapping.cpp:517-593) and cLocalMapping::MapPointCulling (src/cLocalMapping.cpp:187-221) over the same store.  Both
+ * read the observation relation plus one datum per feature, the octave of its key point.  The ASSUMPTION above gains one clause: a keyframe's FIRST observation
+ * of a point (mit->second[0], the first AddObservation, src/cMapPoint.cpp:90-94) is the one with the smallest feature index — what the distinct row encodes;
+ * ProcessNewMultiKeyFrame and CreateNewMapPoints add observations in ascending feature order.
+ *   mcs_covis_set_keyframe_octaves  octaves[i] = GetKeyPoint(i).octave of keyframe mnId; n must equal the keyframe's row length.  Host kind: a value >=
+ *                               MCS_MAX_LEVELS is MCS_ERR_INVALID; device kind: it reads MCS_MAX_LEVELS - 1.  A keyframe whose octaves were never set reads level
+ *                               0 everywhere; mcs_covis_set_keyframe on an existing keyframe keeps them where the row length is unchanged and resets them to 0
+ *                               otherwise.
+ *   mcs_covis_cull_keyframes    mnIds[n] (host memory): mpCurrentMultiKeyFrame->GetVectorCovisibleKeyFrames() in the caller's order — `ordered` of
+ *                               mcs_covis_update_connections is that list; not_erase[n] (host memory, may be NULL): mbNotErase.  An id that is not live in the
+ *                               store, or a repeated one, is MCS_ERR_INVALID before anything runs.  The keyframes are judged ONE AFTER ANOTHER (:527-591): per
+ *                               FEATURE whose point is not bad ++nMPs (a point at two features counts twice); where Observations() > 3, nObs = the OTHER
+ *                               keyframes whose first observation has octave <= this feature's octave + 1, and nObs >= 5 makes the feature redundant;
+ *                               nRedundant > 0.9 * nMPs (int against an FP64 product) culls.  verdict[k]: 0 kept, 1 culled, 2 would be culled but not_erase[k]
+ *                               is set (mbToBeErased, src/cMultiKeyFrame.cpp:580-584; no effect on the store), 3 skipped because mnId == 0 (:531; counts
+ *                               read 0).  n_mps / n_redundant[k]: the two counters as the reference held them when it decided keyframe k.  A culled keyframe
+ *                               stops observing at once (cMultiKeyFrame::SetBadFlag -> EraseAllObservations, src/cMultiKeyFrame.cpp:591-593,
+ *                               src/cMapPoint.cpp:96-116): each of its points that is then observed by two or fewer keyframes goes bad, and the keyframes
+ *                               that follow in the list see that — the verdicts depend on the order of the list.  bad_points[cap]: those points in the order
+ *                               the reference makes them bad (keyframes in list order, within one by the feature index of the point's first entry); entries
+ *                               from n_bad_points on read -1; n_bad_points is the FULL count even above cap.  Effects on the store, the same for both kinds:
+ *                               the points of bad_points get their bad flag (as mcs_covis_set_points_bad), culled keyframes get theirs (as
+ *                               mcs_covis_set_keyframe_bad).  The call does NOT erase keyframes — the host's view of the slots cannot follow a decision taken
+ *                               on the device without a read-back: the caller erases the verdict == 1 keyframes with mcs_covis_erase_keyframe once it has
+ *                               the verdicts (until then their rows still count as observers for every OTHER call).  The spanning tree, mpMap and the
+ *                               keyframe database of cMultiKeyFrame::SetBadFlag (:595-669) are the caller's.
+ *   mcs_covis_observations      nobs[i] = cMapPoint::Observations() of point ids[i] (src/cMapPoint.cpp:158-162): the live keyframes whose row holds it, 0 for a
+ *                               bad point
+ *   mcs_covis_cull_points       mlpRecentAddedMapPoints = ids[n] with mnFound / mnVisible / mnFirstKFid per entry; current_kf_id =
+ *                               mpCurrentMultiKeyFrame->mnId.  verdict[i], the first that holds: 1 the point is bad (leaves the list); 2
+ *                               (double)found / visible < 0.25 (visible == 0 gives NaN or inf, which is not below): SetBadFlag, leaves; 3
+ *                               current - first >= 2 && Observations() <= 2: SetBadFlag, leaves; 4 current - first >= 3: leaves; 0 stays.  The difference is
+ *                               unsigned 64-bit as in the reference (unsigned long minus long): a first id above the current one wraps and passes both tests.
+ *                               Verdicts 2 and 3 set the point's bad flag in the store.  ids must be distinct: host kind refuses a repeat, device kind gives
+ *                               every copy the verdict of the first.
+ * Host kind of the three refuses an id outside [0, max_points); device kind reads such a point as bad (nobs 0, verdict 1).  kind as above: DEVICE only enqueues on
+ * the context's stream (no host wait, nothing read back), HOST goes through the staging block; all three are refused with MCS_ERR_UNSUPPORTED while deferred
+ * searches are on. */
+int mcs_covis_set_keyframe_octaves(mcs_covis*, int64_t mnId, const uint8_t* octaves, int n, mcs_mem_kind kind);
+int mcs_covis_cull_keyframes(mcs_covis*, int n, const int64_t* mnIds, const uint8_t* not_erase, int cap, mcs_mem_kind kind, int32_t* verdict, int32_t* n_mps,
+                             int32_t* n_redundant, int32_t* bad_points, int32_t* n_bad_points);
+int mcs_covis_observations(mcs_covis*, const int32_t* ids, int n, mcs_mem_kind kind, int32_t* nobs);
+int mcs_covis_cull_points(mcs_covis*, int64_t current_kf_id, int n, const int32_t* ids, const int32_t* found, const int32_t* visible,
+                          const int64_t* first_kf_id, mcs_mem_kind kind, int32_t* verdict);
 /* device helpers (all pointers but fill_row on the context's GPU; both only enqueue on the context's stream):
  *   mcs_gather_rows   dst row i = src row idx[i]; where idx[i] < 0, fill_row (HOST pointer to row_bytes bytes; NULL: zeros).  row_bytes <= 256.
  *   mcs_scatter_rows  dst row idx[i] = src row i; negative indices are skipped.

@@ -81,6 +81,7 @@ EXPORTS = [
     "mcs_covis_create", "mcs_covis_destroy", "mcs_covis_clear", "mcs_covis_size", "mcs_covis_slots", "mcs_covis_set_keyframe", "mcs_covis_set_keyframe_pose",
     "mcs_covis_erase_keyframe", "mcs_covis_set_keyframe_bad", "mcs_covis_set_points_bad", "mcs_covis_update_reference", "mcs_covis_update_connections",
     "mcs_gather_rows", "mcs_scatter_rows",
+    "mcs_covis_set_keyframe_octaves", "mcs_covis_cull_keyframes", "mcs_covis_observations", "mcs_covis_cull_points",
 ]
 
 WINDOW_RATIO, WINDOW_BEST, WINDOW_INITIALIZE = 1, 2, 3
@@ -250,6 +251,10 @@ def lib():
     L.mcs_covis_set_points_bad.argtypes = [vp, vp, C.c_int, vp, C.c_int]
     L.mcs_covis_update_reference.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]
     L.mcs_covis_update_connections.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp]
+    L.mcs_covis_set_keyframe_octaves.argtypes = [vp, C.c_int64, vp, C.c_int, C.c_int]
+    L.mcs_covis_cull_keyframes.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
+    L.mcs_covis_observations.argtypes = [vp, vp, C.c_int, C.c_int, vp]
+    L.mcs_covis_cull_points.argtypes = [vp, C.c_int64, C.c_int, vp, vp, vp, vp, C.c_int, vp]
     L.mcs_gather_rows.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp]
     L.mcs_scatter_rows.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp]
     L.mcs_copy_narrow.argtypes = [vp, vp, vp, C.c_size_t, C.c_int, vp]

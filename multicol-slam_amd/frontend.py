@@ -1322,7 +1322,8 @@ def _kf_id(kf):
 
 class cCovisibility:
     """The observation store behind cTracking::UpdateReferenceKeyFrames / UpdateReferencePoints (src/cTracking.cpp:1024-1123) and
-    cMultiKeyFrame::UpdateConnections (src/cMultiKeyFrame.cpp:406-500) on the device (mcs_covis_*): one row of map point ids per keyframe.  Keyframes are
+    cMultiKeyFrame::UpdateConnections (src/cMultiKeyFrame.cpp:406-500) on the device (mcs_covis_*), and behind cLocalMapping::KeyFrameCulling / MapPointCulling
+    (src/cLocalMapping.cpp:517-593, 187-221): one row of map point ids (and one of octaves) per keyframe.  Keyframes are
     objects with mnId (and GetMapPointMatches() / GetCameraCenter() where no array is given) or plain ids; map points are objects with mnId or plain ids
     in [0, max_points).  Where the reference orders by heap address the store orders by mnId."""
 
@@ -1419,6 +1420,63 @@ class cCovisibility:
             assert len(counter) == int(nc[q])
             out.append(dict(counter=counter, ordered=None if n < 0 else od[q * S:q * S + n].tolist(), weights=None if n < 0 else ow[q * S:q * S + n].tolist()))
         return out
+
+    # ---- cLocalMapping::KeyFrameCulling / MapPointCulling (src/cLocalMapping.cpp:517-593, 187-221).  device=True: the same call device-kind — inputs and outputs
+    # in device memory, nothing read back before the call has returned (the pattern of TrackLocalMapSearch) — with the same results.
+    def _arrays(self, device, ins, outs):
+        """-> (pointers of ins + outs, reader of the outs)"""
+        if device:
+            d = [DeviceArray(a) for a in list(ins) + list(outs)]
+            return [x.ptr for x in d], lambda: [x.read() for x in d[len(ins):]]
+        return [np_ptr(a) for a in list(ins) + list(outs)], lambda: list(outs)
+
+    def SetOctaves(self, pKF, octaves=None, device=False):
+        """octaves[i] = pKF.GetKeyPoint(i).octave (default: the keyframe's keypoints)"""
+        o = np.ascontiguousarray(pKF.GetKeyPoints()["octave"] if octaves is None else octaves).astype(np.uint8)
+        (po,), _ = self._arrays(device, [o], [])
+        check(lib().mcs_covis_set_keyframe_octaves(self.h, _kf_id(pKF), po, len(o), MEM_DEVICE if device else MEM_HOST))
+
+    def KeyFrameCulling(self, kfs, not_erase=None, cap=None, device=False):
+        """kfs: mpCurrentMultiKeyFrame->GetVectorCovisibleKeyFrames(), in that order; not_erase: mbNotErase per keyframe (default: the keyframes' attribute, False
+        where there is none).  -> dict(verdict (0 kept, 1 culled, 2 to be erased, 3 mnId == 0), n_mps, n_redundant, culled / to_be_erased (the entries of kfs),
+        bad_points, n_bad_points (above cap: the list was cut)).  Culled keyframes and bad points are flagged in the store; the keyframes are NOT erased:
+        EraseKeyFrame them, and do the spanning-tree / map / database part of cMultiKeyFrame::SetBadFlag, once the verdicts are here."""
+        kfs = list(kfs)
+        n = len(kfs)
+        cap = self.max_points if cap is None else int(cap)
+        ids = np.array([_kf_id(k) for k in kfs], np.int64)
+        ne = np.array([bool(getattr(k, "mbNotErase", False)) for k in kfs] if not_erase is None else not_erase, np.uint8).reshape(n)
+        outs = [np.zeros(max(n, 1), np.int32) for _ in range(3)] + [np.zeros(max(cap, 1), np.int32), np.zeros(1, np.int32)]
+        ptr, read = self._arrays(device, [], outs)
+        check(lib().mcs_covis_cull_keyframes(self.h, n, np_ptr(ids), np_ptr(ne), cap, MEM_DEVICE if device else MEM_HOST, *ptr))
+        v, m, r, bp, nb = read()
+        v = v[:n].tolist()
+        return dict(verdict=v, n_mps=m[:n].tolist(), n_redundant=r[:n].tolist(), culled=[k for k, x in zip(kfs, v) if x == 1],
+                    to_be_erased=[k for k, x in zip(kfs, v) if x == 2], bad_points=bp[:min(int(nb[0]), cap)].tolist(), n_bad_points=int(nb[0]))
+
+    def Observations(self, points, device=False):
+        """cMapPoint::Observations() of the listed points: the live keyframes whose row holds the point, 0 for a bad one"""
+        ids = _point_ids(points)
+        if len(ids) == 0:
+            return []
+        ptr, read = self._arrays(device, [ids], [np.zeros(len(ids), np.int32)])
+        check(lib().mcs_covis_observations(self.h, ptr[0], len(ids), MEM_DEVICE if device else MEM_HOST, ptr[1]))
+        return read()[0].tolist()
+
+    def MapPointCulling(self, current_kf, points, found, visible, first_kf, device=False):
+        """points: mlpRecentAddedMapPoints (distinct) with mnFound / mnVisible / mnFirstKFid per entry -> (verdicts, the list that remains).  Verdicts: 0 stays,
+        1 was bad, 2 found ratio below a quarter (now bad), 3 two or fewer observations after two keyframes (now bad), 4 three keyframes old."""
+        points = list(points)
+        ids = _point_ids(points)
+        n = len(ids)
+        if n == 0:
+            return [], []
+        ins = [ids, np.ascontiguousarray(found, np.int32).reshape(n), np.ascontiguousarray(visible, np.int32).reshape(n),
+               np.array([int(k) for k in first_kf], np.int64).reshape(n)]
+        ptr, read = self._arrays(device, ins, [np.zeros(n, np.int32)])
+        check(lib().mcs_covis_cull_points(self.h, _kf_id(current_kf), n, ptr[0], ptr[1], ptr[2], ptr[3], MEM_DEVICE if device else MEM_HOST, ptr[4]))
+        v = read()[0].tolist()
+        return v, [p for p, x in zip(points, v) if x == 0]
 
 
 def TrackLocalMapSearch(F, store, points, th=3, nnratio=0.8, featDim=32, havingMasks=False, cap=None, ctx=None):
