@@ -444,7 +444,8 @@ int mcs_kfdb_score(mcs_kfdb*, int nw, const int32_t* word_ids, const double* val
  *                                     Xw [i][2][3] world positions of the two map points, cam [i][2] keypoint_to_cam of their first index in their keyframe,
  *                                     sigma2 [i][2] = GetSigma2(octave) of those keypoints, index1 [i] = i1 (mvnIndices1).  seed: see mcs_sim3_draw.  draws: NULL,
  *                                     or per solver 3 * max(1, max_iterations[s]) values randi in [0, N) (iteration k, pick j at 3k + j) that replace the
- *                                     generated ones.  A solver with N < 3 correspondences and N >= minInliers is refused (the reference is undefined there).
+ *                                     generated ones.  A solver with N < 3 correspondences and N >= minInliers is refused (the reference is undefined there), and so
+ *                                     is a sigma2 whose 9.210 * sigma2 is NaN, negative or >= 2^64 (mvnMaxError is a std::vector<size_t>: no defined conversion).
  *   mcs_sim3_set_ransac_parameters    SetRansacParameters for every solver: mnIterations = 0, the best-so-far state is kept (as in the reference)
  *   mcs_sim3_iterate                  iterate(n_iterations[s], bNoMore, vbInliers, nInliers, result) (:167-254) of every solver in one call (= the
  *                                     reference's sequential round over its candidates: the solvers are independent).  n_iterations[s] <= 0: solver s is

@@ -550,6 +550,10 @@ int mcs_sim3_create(mcs_ctx* c, int nr_cams, const double* M_c, const mcs_ocam* 
 			corrSolver[i] = s;
 			if (index1[i] < 0 || index1[i] >= S.mN1) return fail(MCS_ERR_INVALID, who + ": index1 outside [0, mN1)");
 			if (cam[2 * i] < 0 || cam[2 * i] >= nr_cams || cam[2 * i + 1] < 0 || cam[2 * i + 1] >= nr_cams) return fail(MCS_ERR_INVALID, who + ": camera index out of range");
+			for (int side = 0; side < 2; ++side) {   // 9.210 sigma^2 becomes a size_t (k_sim3_setup): NaN, negative and >= 2^64 have no defined conversion
+				const double e = 9.210 * sigma2[2 * (size_t)i + side];
+				if (!(e >= 0.0 && e < 18446744073709551616.0)) return fail(MCS_ERR_INVALID, who + ": 9.210 * sigma2 is NaN, negative or >= 2^64");
+			}
 		}
 		S.minInliers = min_inliers[s];
 		S.maxIts = 0;

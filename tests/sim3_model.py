@@ -3,7 +3,9 @@ cv::Matx products (s = 0; s += a(i,k) * b(k,j) in increasing k), Matx::dot (row-
 symmetric 4x4 (JacobiImpl_, cyclic pivot on the largest off-diagonal element, OpenCV's hypot, selection sort), cv::norm, the one MatExpr scale factor of
 `2 * ang * vec / norm(vec)`, cv::Rodrigues, cv::pow(P3, 2).  The draws are an input.  The projection is the oracle's WorldToCamHom_fast
 (oracle_lib.world_to_cam: glibc atan, pinned against src/cam_model_omni.cpp).  Python floats are IEEE doubles and numpy element-wise operations do
-not contract, so every step below rounds as the reference's does."""
+not contract, so every step below rounds as the reference's does.  Divisions, square roots, cos and sin go through _div / _sqrt / _cos / _sin, which return
+what IEEE arithmetic and C's libm return (an infinity or a NaN) where Python would raise: non-finite and degenerate inputs (tests/hostile_sim3.py) are stated,
+not refused.  Comparisons with a NaN are false in Python as in C++."""
 import math
 
 import numpy as np
@@ -55,8 +57,12 @@ def ransac_max_its(probability, minInliers, maxIterations, N):
 
 
 def max_error(sigma2):
-    """mvnMaxError1/2 are std::vector<size_t>: 9.210 * sigma^2 truncated"""
-    return float(int(9.210 * sigma2))
+    """mvnMaxError1/2 are std::vector<size_t>: 9.210 * sigma^2 truncated.  A product that is NaN, negative or >= 2^64 has no defined conversion (in the
+    reference either): mcs_sim3_create refuses it, and so does the model"""
+    e = 9.210 * float(sigma2)
+    if not (e >= 0.0 and e < 18446744073709551616.0):   # false for NaN
+        raise ValueError("9.210 * sigma2 = %r cannot be converted to size_t" % e)
+    return float(int(e))
 
 
 # ---------------------------------------------------------------------------------------------- cv::Matx / cConverter
@@ -86,20 +92,42 @@ def inv_mat(M):
 
 
 # ---------------------------------------------------------------------------------------------- cv::eigen (JacobiImpl_)
+def _div(a, b):
+    """a / b as IEEE divides: x / 0 is an infinity or NaN, never an exception"""
+    with np.errstate(all="ignore"):
+        return float(np.float64(a) / np.float64(b))
+
+
+def _sqrt(x):
+    """sqrt as IEEE: NaN of a NaN or a negative number"""
+    return math.sqrt(x) if x >= 0.0 else float("nan")
+
+
+def _cos(x):
+    return math.cos(x) if math.isfinite(x) else float("nan")   # glibc's cos for every finite argument; NaN of an infinity as in C
+
+
+def _sin(x):
+    return math.sin(x) if math.isfinite(x) else float("nan")
+
+
 def cv_hypot(a, b):
     a, b = abs(a), abs(b)
     if a > b:
-        b /= a
-        return a * math.sqrt(1 + b * b)
+        b = _div(b, a)
+        return a * _sqrt(1 + b * b)
     if b > 0:
-        a /= b
-        return b * math.sqrt(1 + a * a)
+        a = _div(a, b)
+        return b * _sqrt(1 + a * a)
     return 0.0
 
 
-def jacobi_eigen(A):
-    """symmetric n x n (list of lists, consumed) -> (W descending, V rows = eigenvectors)"""
+def jacobi_eigen(A, info=None):
+    """symmetric n x n (list of lists, consumed) -> (W descending, V rows = eigenvectors).  Comparisons with a NaN are false as in C++: the pivot search
+    keeps its first candidate, `fabs(p) <= eps` does not break (the n * n * 30 cap ends the loop) and the selection sort does not swap.  info (a dict)
+    receives the number of rotations made"""
     n = len(A)
+    rotations = 0
     A = [float(x) for row in A for x in row]
     V = [1.0 if i % (n + 1) == 0 else 0.0 for i in range(n * n)]
     W = [0.0] * n
@@ -138,9 +166,10 @@ def jacobi_eigen(A):
             y = (W[l] - W[k]) * 0.5
             t = abs(y) + cv_hypot(p, y)
             s = cv_hypot(p, t)
-            c = t / s
-            s = p / s
-            t = (p / t) * p
+            c = _div(t, s)
+            s = _div(p, s)
+            t = _div(p, t) * p
+            rotations += 1
             if y < 0:
                 s, t = -s, -t
             A[n * k + l] = 0.0
@@ -183,29 +212,26 @@ def jacobi_eigen(A):
             W[m], W[k] = W[k], W[m]
             for i in range(n):
                 V[n * m + i], V[n * k + i] = V[n * k + i], V[n * m + i]
+    if info is not None:
+        info["rotations"] = rotations
     return W, [V[n * i:n * i + n] for i in range(n)]
 
 
 # ---------------------------------------------------------------------------------------------- computeT (:286-371)
 def rodrigues(r):
     rx, ry, rz = r
-    theta = math.sqrt(rx * rx + ry * ry + rz * rz) if not any(math.isnan(v) for v in r) else float("nan")
+    theta = _sqrt(rx * rx + ry * ry + rz * rz)
     if theta < DBL_EPSILON:
         return [[1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]]
-    c, s = math.cos(theta), math.sin(theta)
+    c, s = _cos(theta), _sin(theta)
     c1 = 1.0 - c
-    itheta = 1.0 / theta if theta else 0.0
+    itheta = _div(1.0, theta) if theta else 0.0
     rx, ry, rz = rx * itheta, ry * itheta, rz * itheta
     rrt = [rx * rx, rx * ry, rx * rz, rx * ry, ry * ry, ry * rz, rx * rz, ry * rz, rz * rz]
     r_x = [0.0, -rz, ry, rz, 0.0, -rx, -ry, rx, 0.0]
     I = [1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0]
     R = [c * I[k] + c1 * rrt[k] + s * r_x[k] for k in range(9)]
     return [R[0:3], R[3:6], R[6:9]]
-
-
-def _div(a, b):
-    with np.errstate(all="ignore"):
-        return float(np.float64(a) / np.float64(b))
 
 
 def centroid(P):
@@ -219,8 +245,9 @@ def centroid(P):
     return Pr, C
 
 
-def compute_t(P1, P2):
-    """P1, P2: 3x3, one point per column -> dict(R, t, s, T12, T21) as lists"""
+def compute_t(P1, P2, ang_ulps=0):
+    """P1, P2: 3x3, one point per column -> dict(R, t, s, T12, T21) as arrays, and what the Jacobi solver did: N (the 4x4 it was given), W, V, rotations.
+    ang_ulps moves the quaternion's angle by that many units in the last place (the model's own sensitivity to the libm behind atan2)"""
     Pr1, O1 = centroid(P1)
     Pr2, O2 = centroid(P2)
     M = matmul(Pr2, [[Pr1[j][i] for j in range(3)] for i in range(3)])
@@ -234,10 +261,14 @@ def compute_t(P1, P2):
     N33 = -M[0][0] + M[1][1] - M[2][2]
     N34 = M[1][2] + M[2][1]
     N44 = -M[0][0] - M[1][1] + M[2][2]
-    W, V = jacobi_eigen([[N11, N12, N13, N14], [N12, N22, N23, N24], [N13, N23, N33, N34], [N14, N24, N34, N44]])
+    N = [[N11, N12, N13, N14], [N12, N22, N23, N24], [N13, N23, N33, N34], [N14, N24, N34, N44]]
+    info = {}
+    W, V = jacobi_eigen([row[:] for row in N], info)
     vec = V[0][1:4]
-    nv = math.sqrt(((0.0 + vec[0] * vec[0]) + vec[1] * vec[1]) + vec[2] * vec[2]) if not any(math.isnan(v) for v in vec) else float("nan")
+    nv = _sqrt(((0.0 + vec[0] * vec[0]) + vec[1] * vec[1]) + vec[2] * vec[2])
     ang = math.atan2(nv, V[0][0])
+    for _ in range(abs(ang_ulps)):
+        ang = math.nextafter(ang, math.inf if ang_ulps > 0 else -math.inf)
     f = (2 * ang) * _div(1.0, nv)
     vec = [v * f for v in vec]
     R = rodrigues(vec)
@@ -258,7 +289,8 @@ def compute_t(P1, P2):
     tinv = [matmul([[-x for x in row] for row in sRinv], [[t[0]], [t[1]], [t[2]]])[i][0] for i in range(3)]
     T12 = [sR[0] + [t[0]], sR[1] + [t[1]], sR[2] + [t[2]], [0.0, 0.0, 0.0, 1.0]]
     T21 = [sRinv[0] + [tinv[0]], sRinv[1] + [tinv[1]], sRinv[2] + [tinv[2]], [0.0, 0.0, 0.0, 1.0]]
-    return dict(R=np.array(R), t=np.array(t), s=s, T12=np.array(T12), T21=np.array(T21))
+    return dict(R=np.array(R), t=np.array(t), s=s, T12=np.array(T12), T21=np.array(T21), N=np.array(N), W=np.array(W), V=np.array(V),
+                rotations=info["rotations"])
 
 
 def hyp_vector(h):
@@ -343,8 +375,10 @@ class Sim3Model:
         P2 = [[float(self.X2c[p, r]) for p in picks] for r in range(3)]
         return picks, compute_t(P1, P2)
 
-    def check_inliers(self, h):
-        """CheckInliers (:374-415) -> (inlier flags [N], near-threshold flags [N])"""
+    def errors(self, h):
+        """the two squared reprojection errors of CheckInliers (:374-415) per pair -> (err1 [N], err2 [N])"""
+        if self.N == 0:
+            return np.zeros(0), np.zeros(0)
         with np.errstate(all="ignore"):
             p21 = _affine(h["T12"], self.X2c)   # row 3 of T12 (X, 1) is exactly 1, so (p21, 1) is the 4-vector the reference multiplies on
             p12 = _affine(h["T21"], self.X1c)
@@ -355,8 +389,14 @@ class Sim3Model:
             d2 = uv2 - self.P2
             err1 = d1[:, 0] * d1[:, 0] + d1[:, 1] * d1[:, 1]
             err2 = d2[:, 0] * d2[:, 0] + d2[:, 1] * d2[:, 1]
+        return err1, err2
+
+    def check_inliers(self, h):
+        """CheckInliers (:374-415) -> (inlier flags [N], near-threshold flags [N]).  A threshold of 0 has no band: err < 0 is false whatever err is"""
+        err1, err2 = self.errors(h)
+        with np.errstate(all="ignore"):
             inl = (err1 < self.e1) & (err2 < self.e2)
-            near = (np.abs(err1 - self.e1) <= FLAG_BAND * self.e1) | (np.abs(err2 - self.e2) <= FLAG_BAND * self.e2)
+            near = ((self.e1 > 0) & (np.abs(err1 - self.e1) <= FLAG_BAND * self.e1)) | ((self.e2 > 0) & (np.abs(err2 - self.e2) <= FLAG_BAND * self.e2))
         return inl, near
 
     def evaluate(self, k, draws):

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import sim3_model as M
+from hostile_sim3 import compare_hypotheses, run_rounds   # the comparisons shared with the hostile suite
 
 pytestmark = pytest.mark.gpu
 
@@ -77,26 +78,6 @@ class Batch:
         return picks, cnt, hyp, inl.astype(bool)
 
 
-def compare_hypotheses(m, draws, got, first, count, label):
-    picks, cnt, hyp, inl = got
-    near_total = 0
-    for i in range(count):
-        k = first + i
-        p, h, einl, near = m.evaluate(k, draws)
-        assert list(picks[i]) == p, (label, k)
-        assert cnt[i] == inl[i].sum()
-        assert np.array_equal(inl[i] & ~near, einl & ~near), (label, k, np.flatnonzero(inl[i] != einl)[:10])
-        if not near.any():
-            assert cnt[i] == einl.sum(), (label, k)
-        near_total += int(near.sum())
-        ev = M.hyp_vector(h)
-        if np.isfinite(ev).all():
-            assert np.allclose(hyp[i], ev, rtol=1e-9, atol=1e-9 * max(1.0, np.abs(ev).max())), (label, k, np.abs(hyp[i] - ev).max())
-        else:
-            assert np.array_equal(np.isnan(hyp[i]), np.isnan(ev)), (label, k)
-    return near_total
-
-
 def pairs_for(rng, M_c, sizes, fracs):
     return [M.make_pair(rng, M_c, n, inlier_frac=f) for n, f in zip(sizes, fracs)]
 
@@ -135,30 +116,6 @@ def test_iteration_budget_at_12282(env):
     e = m.iterate(50, M.generated_draws(5, 1, 12282))
     assert out[1][:2] == e[:2] and out[1][3] == e[3] and np.array_equal(out[1][2], e[2])
     assert b.info()[2].tolist() == [0, m.mnIterations] and (out[1][0] or out[1][1])
-
-
-def run_rounds(b, models, draws, sizes):
-    """drive the batch and the models with the same call sizes (a list cycled over the calls) until every solver is done; -> calls made"""
-    ns = len(models)
-    done = [False] * ns
-    calls = 0
-    while not all(done) and calls < 400:
-        n = sizes[calls % len(sizes)]
-        nit = [0 if done[s] else n for s in range(ns)]
-        out = b.iterate(nit)
-        for s in range(ns):
-            if done[s]:
-                assert out[s][:2] == (False, False) and out[s][3] == 0
-                continue
-            e = models[s].iterate(n, draws[s])
-            assert out[s][0] == e[0] and out[s][1] == e[1] and out[s][3] == e[3], (calls, s, out[s][:2], out[s][3], e[:2], e[3])
-            assert np.array_equal(out[s][2], e[2]), (calls, s)
-            if e[0]:
-                assert np.allclose(out[s][4], e[4], rtol=1e-9, atol=1e-9)
-            done[s] = e[1]
-        calls += 1
-    assert all(done)
-    return calls
 
 
 def loop_pairs(rng, M_c):
