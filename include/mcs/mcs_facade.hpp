@@ -792,7 +792,8 @@ private:
 // vector of 28-byte cv::KeyPoint-layout records), GetKeyPointsRays() (Vec3d or anything indexable by 0..2), keypoint_to_cam and
 // cont_idx_to_local_cam_idx (find(i)->second), GetDescriptorRowPtr(cam, row) and, with havingMasks, GetDescriptorMaskRowPtr(cam, row)
 // (src/cMultiKeyFrame.cpp:356-364); MP: GetWorldPos().  Per neighbour the accepted matches come back in the reference's order with their points; the
-// map-point surgery (new cMapPoint, AddObservation, AddMapPoint, ComputeDistinctiveDescriptors, UpdateNormalAndDepth, :362-377) stays with the caller.
+// map-point surgery (new cMapPoint, AddObservation, AddMapPoint, :362-368) stays with the caller; ComputeDistinctiveDescriptors / UpdateNormalAndDepth of the
+// new points (:370-374) is cCovisibility::UpdateMapPoints once the caller has put their observations into the store.
 struct NewMapPoints {
 	struct Neighbour {
 		std::vector<std::pair<size_t, size_t>> vMatchedIndices;   // accepted (idx1, idx2), ascending idx1
@@ -1097,11 +1098,43 @@ public:
 		recent.swap(rest);
 		return v;
 	}
+	// ---- cMapPoint::UpdateNormalAndDepth / ComputeDistinctiveDescriptors (src/cMapPoint.cpp:449-492, 294-388) for a list of map points
+	struct MapPointUpdate {   // per listed point; status: 0 refreshed, 1 bad point, 2 reference keyframe not in the store, 3 level outside mvScaleFactors
+		std::vector<int32_t> status, nDescriptors, bestFeature;   // an entry whose status is not 0 keeps what it held (zeros / -1 here)
+		std::vector<double> mNormalVector, mfMinDistance, mfMaxDistance, minDistanceInvariance, maxDistanceInvariance;   // mNormalVector: 3 per point
+		std::vector<KF*> bestKF;                                  // where the chosen descriptor lives; nullptr: none was chosen
+	};
+	// desc (/ mask): n rows of dim bytes, GetDescriptor(cam, idx) / GetDescriptorMask(cam, idx) in continuous feature-index order, one per entry of the
+	// keyframe's row; mask may be nullptr.  The first call fixes dim and whether masks exist for the whole store.
+	void SetDescriptors(KF* pKF, const uint8_t* desc, const uint8_t* mask, int dim, int n) {
+		mcs_throw(mcs_covis_set_keyframe_descriptors(h_, (int64_t)pKF->mnId, desc, mask, dim, dim, n, MCS_MEM_HOST));
+		dim_ = dim;
+	}
+	// points (distinct ids) with GetWorldPos() (3 doubles each) and mpRefKF per entry; scaleFactors = mvScaleFactors.  desc (/ mask): the points' current
+	// descriptors, n rows of dim bytes, rewritten where one is chosen; desc == nullptr refreshes normal and depth only (cLoopClosing.cpp:511).
+	MapPointUpdate UpdateMapPoints(const std::vector<int32_t>& points, const std::vector<double>& pos, const std::vector<KF*>& refKF,
+	                               const std::vector<double>& scaleFactors, uint8_t* desc = nullptr, uint8_t* mask = nullptr) {
+		const size_t n = points.size();
+		MapPointUpdate r;
+		r.status.assign(n + 1, 0); r.nDescriptors.assign(n + 1, 0); r.bestFeature.assign(n + 1, -1);
+		r.mNormalVector.assign(3 * n + 1, 0.0); r.mfMinDistance.assign(n + 1, 0.0); r.mfMaxDistance.assign(n + 1, 0.0);
+		r.minDistanceInvariance.assign(n + 1, 0.0); r.maxDistanceInvariance.assign(n + 1, 0.0);
+		std::vector<int64_t> ref, best(n + 1, -1);
+		for (KF* k : refKF) ref.push_back((int64_t)k->mnId);
+		mcs_throw(mcs_covis_update_points(h_, (int)n, points.data(), pos.data(), ref.data(), scaleFactors.data(), (int)scaleFactors.size(), MCS_MEM_HOST,
+		                                  r.mNormalVector.data(), r.mfMinDistance.data(), r.mfMaxDistance.data(), r.minDistanceInvariance.data(),
+		                                  r.maxDistanceInvariance.data(), desc, mask, r.nDescriptors.data(), best.data(), r.bestFeature.data(), r.status.data()));
+		r.status.resize(n); r.nDescriptors.resize(n); r.bestFeature.resize(n); r.mNormalVector.resize(3 * n); r.mfMinDistance.resize(n); r.mfMaxDistance.resize(n);
+		r.minDistanceInvariance.resize(n); r.maxDistanceInvariance.resize(n);
+		for (size_t i = 0; i < n; ++i) r.bestKF.push_back(best[i] < 0 ? nullptr : obj_.at(best[i]));
+		return r;
+	}
+	int descriptorSize() const { return dim_; }
 	mcs_covis* handle() const { return h_; }
 
 private:
 	mcs_covis* h_ = nullptr;
-	int maxPoints_ = 0;
+	int maxPoints_ = 0, dim_ = 0;
 	std::map<int64_t, KF*> obj_;
 	std::vector<KF*> slots_;   // slot -> keyframe, erased ones included (slot order is id order)
 };

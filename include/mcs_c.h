@@ -670,6 +670,47 @@ int mcs_covis_cull_keyframes(mcs_covis*, int n, const int64_t* mnIds, const uint
 int mcs_covis_observations(mcs_covis*, const int32_t* ids, int n, mcs_mem_kind kind, int32_t* nobs);
 int mcs_covis_cull_points(mcs_covis*, int64_t current_kf_id, int n, const int32_t* ids, const int32_t* found, const int32_t* visible,
                           const int64_t* first_kf_id, mcs_mem_kind kind, int32_t* verdict);
+/* cMapPoint::UpdateNormalAndDepth (src/cMapPoint.cpp:449-492) and cMapPoint::ComputeDistinctiveDescriptors (src/cMapPoint.cpp:294-388) for a list of map points,
+ * over the same store: the pair the reference calls for every matched and every new point of a keyframe (src/cLocalMapping.cpp:173-174, 370-374), after fusing,
+ * after bundle adjustment (src/cOptimizer.cpp:254, 866-867) and during loop correction (src/cLoopClosing.cpp:511, 540).  Both are functions of who observes the
+ * point, at which feature, at which octave, from which camera centre.  ASSUMPTIONS as above; where the reference iterates std::map<cMultiKeyFrame*, ...> the order
+ * is ascending mnId (slot order), and a keyframe's observations of a point are its features in ascending index.
+ *   mcs_covis_set_keyframe_descriptors  desc / mask[n] rows of `stride` bytes (a multiple of 4, >= dim): GetDescriptor(cam, idx) / GetDescriptorMask(cam, idx) in
+ *                               continuous feature-index order, one row per entry of keyframe mnId's row; n must equal the row length; mask may be NULL; dim is
+ *                               16, 32 or 64.  The store COPIES the rows into slabs of its own (one of descriptors, one of masks, both in the slot layout of
+ *                               the rows), allocated at the first call: that call fixes dim and whether masks exist for the whole store, a later call that
+ *                               disagrees is MCS_ERR_INVALID.  mcs_covis_set_keyframe on an existing keyframe keeps them where the row length is unchanged and
+ *                               forgets them otherwise (as the octaves); mcs_covis_erase_keyframe and mcs_covis_clear forget them (dim and masks stay fixed).
+ *   mcs_covis_update_points     every array is LIST-indexed (entry i belongs to ids[i]) and lives where `kind` says.  ids[n]; pos[n][3] = GetWorldPos();
+ *                               ref_kf[n] = mnId of mpRefKF; scale_factors[nlevels] = mvScaleFactors, 2 <= nlevels <= MCS_MAX_LEVELS.  Outputs, each may be
+ *                               NULL (status not in host kind): normal[n][3]; min_dist / max_dist[n] = mfMinDistance / mfMaxDistance; min_inv / max_inv[n] =
+ *                               0.8 * mfMinDistance / 1.2 * mfMaxDistance (what mcs_local_points reads); desc / mask[n][dim] IN/OUT, rows of dim bytes, 4-byte aligned, written
+ *                               only where a descriptor is chosen (mask only if the store has masks); n_desc[n] = N of :336; best_kf / best_feat[n] = mnId and
+ *                               feature of the chosen row, -1 where status is 0 and none is chosen; status[n].  desc == NULL: UpdateNormalAndDepth only (no
+ *                               stored descriptors needed; n_desc / best_* are not written).  desc != NULL while a live keyframe has no stored descriptors:
+ *                               MCS_ERR_INVALID before anything runs.
+ *                               status[i], the first that holds: 1 the point is bad (:304, :457; device kind also for an id outside [0, max_points), which host
+ *                               kind refuses); 2 ref_kf[i] is not live in the store; 3 the level lies outside [0, nlevels) (the reference indexes
+ *                               mvScaleFactors out of bounds); 0 refreshed.  For a status other than 0 NOTHING but status[i] is written.  A repeated id is
+ *                               refused in host kind; in device kind every copy gets the result of its own pos / ref_kf.
+ *                               Normal (:464-474, :490): the sum, from (0, 0, 0), in ascending slot order, over every live keyframe that observes the point —
+ *                               bad ones included, each once however many of its features hold the point — of d * (1. / sqrt(((0 + dx^2) + dy^2) + dz^2)),
+ *                               d = pos - t of mcs_covis_set_keyframe_pose; times 1. / (double)(int)n.  A point on a camera centre gives NaN, a point without
+ *                               observers NaN in all three components.  The sum is one ordered chain.
+ *                               Depth range (:476-489): dist = cv::norm(pos - t_ref); level = the octave of the reference keyframe's FIRST feature that holds
+ *                               the point (0 when its octaves were never set), 1 if it does not observe the point; mfMinDistance = ((1.0 / sf) * dist) / sf,
+ *                               mfMaxDistance = (sf * dist) * scale_factors[nlevels - 1 - level], sf = scale_factors[level].  A bad reference keyframe that
+ *                               is still live is used.
+ *                               Descriptor (:312-387): the rows of the observing keyframes that are NOT bad, ascending slot, every feature that holds the
+ *                               point in ascending index; N = 0 leaves the old descriptor; otherwise the choice of mcs_distinctive_descriptors (the same
+ *                               kernel; at most 65 536 rows per point).
+ * n = 0 is a successful no-op.  DEVICE: the call only enqueues on the context's stream — no host wait, nothing read back; its scratch comes from the context's
+ * grow-only buffer and is sized by the store's total number of row entries, the one bound the host knows.  HOST: through the staging block.  Refused with
+ * MCS_ERR_UNSUPPORTED while deferred searches are on. */
+int mcs_covis_set_keyframe_descriptors(mcs_covis*, int64_t mnId, const uint8_t* desc, const uint8_t* mask, int stride, int dim, int n, mcs_mem_kind kind);
+int mcs_covis_update_points(mcs_covis*, int n, const int32_t* ids, const double* pos, const int64_t* ref_kf, const double* scale_factors, int nlevels,
+                            mcs_mem_kind kind, double* normal, double* min_dist, double* max_dist, double* min_inv, double* max_inv, uint8_t* desc, uint8_t* mask,
+                            int32_t* n_desc, int64_t* best_kf, int32_t* best_feat, int32_t* status);
 /* device helpers (all pointers but fill_row on the context's GPU; both only enqueue on the context's stream):
  *   mcs_gather_rows   dst row i = src row idx[i]; where idx[i] < 0, fill_row (HOST pointer to row_bytes bytes; NULL: zeros).  row_bytes <= 256.
  *   mcs_scatter_rows  dst row idx[i] = src row i; negative indices are skipped.

@@ -82,6 +82,7 @@ EXPORTS = [
     "mcs_covis_erase_keyframe", "mcs_covis_set_keyframe_bad", "mcs_covis_set_points_bad", "mcs_covis_update_reference", "mcs_covis_update_connections",
     "mcs_gather_rows", "mcs_scatter_rows",
     "mcs_covis_set_keyframe_octaves", "mcs_covis_cull_keyframes", "mcs_covis_observations", "mcs_covis_cull_points",
+    "mcs_covis_set_keyframe_descriptors", "mcs_covis_update_points",
 ]
 
 WINDOW_RATIO, WINDOW_BEST, WINDOW_INITIALIZE = 1, 2, 3
@@ -255,6 +256,8 @@ def lib():
     L.mcs_covis_cull_keyframes.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
     L.mcs_covis_observations.argtypes = [vp, vp, C.c_int, C.c_int, vp]
     L.mcs_covis_cull_points.argtypes = [vp, C.c_int64, C.c_int, vp, vp, vp, vp, C.c_int, vp]
+    L.mcs_covis_set_keyframe_descriptors.argtypes = [vp, C.c_int64, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.mcs_covis_update_points.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int] + [vp] * 11
     L.mcs_gather_rows.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp]
     L.mcs_scatter_rows.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp]
     L.mcs_copy_narrow.argtypes = [vp, vp, vp, C.c_size_t, C.c_int, vp]

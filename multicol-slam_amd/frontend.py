@@ -1479,6 +1479,53 @@ class cCovisibility:
         return v, [p for p, x in zip(points, v) if x == 0]
 
 
+    # ---- cMapPoint::UpdateNormalAndDepth / ComputeDistinctiveDescriptors (src/cMapPoint.cpp:449-492, 294-388) over the store
+    def SetDescriptors(self, pKF, desc=None, mask=None, device=False):
+        """the keyframe's descriptor (and mask) rows in continuous feature-index order.  desc=None: the keyframe's own rows (a cMultiKeyFrame's flat copies, or
+        all_descriptors() / all_masks()), with its masks unless mask=False; the first call fixes the row width and whether masks exist for the whole store"""
+        if desc is None:
+            desc = pKF._d if hasattr(pKF, "_d") else pKF.all_descriptors()
+            if mask is None:
+                mask = pKF._m if hasattr(pKF, "_m") else pKF.all_masks()
+        if mask is False:
+            mask = None
+        d = np.ascontiguousarray(desc, np.uint8)
+        d = d.reshape(len(d), -1)
+        ins = [d] + ([np.ascontiguousarray(mask, np.uint8).reshape(d.shape)] if mask is not None else [])
+        ptr, _ = self._arrays(device, ins, [])
+        check(lib().mcs_covis_set_keyframe_descriptors(self.h, _kf_id(pKF), ptr[0], ptr[1] if mask is not None else None, d.shape[1], d.shape[1], len(d),
+                                                        MEM_DEVICE if device else MEM_HOST))
+
+    UPDATE_OUTPUTS = ("normal", "min_dist", "max_dist", "min_inv", "max_inv", "desc", "mask", "n_desc", "best_kf", "best_feat", "status")
+
+    def UpdateMapPoints(self, points, pos, ref_kf, scale_factors, desc=None, mask=None, device=False, init=None, skip=()):
+        """UpdateNormalAndDepth + ComputeDistinctiveDescriptors for the listed points.  pos [n][3]; ref_kf: mpRefKF per point (keyframes or ids); desc (/ mask)
+        [n][dim]: the points' current descriptors, kept where none is chosen — desc=None refreshes normal and depth only.  init: {output: array} to start an
+        output from (entries whose status is not 0 keep it; default zeros, -1 for best_kf / best_feat); skip: outputs passed as NULL.
+        -> dict of the outputs (list-indexed): normal, min_dist, max_dist, min_inv, max_inv, [desc, mask, n_desc, best_kf, best_feat,] status"""
+        ids = _point_ids(points)
+        n = len(ids)
+        sf = np.ascontiguousarray(scale_factors, np.float64).reshape(-1)
+        m = max(n, 1)
+        ins = [ids, np.ascontiguousarray(pos, np.float64).reshape(n, 3), np.array([_kf_id(k) for k in ref_kf], np.int64).reshape(n), sf]
+        outs = dict(normal=np.zeros((m, 3)), min_dist=np.zeros(m), max_dist=np.zeros(m), min_inv=np.zeros(m), max_inv=np.zeros(m), status=np.zeros(m, np.int32))
+        if desc is not None:
+            d = np.ascontiguousarray(desc, np.uint8)
+            d = d.reshape(n, d.size // m)
+            outs.update(desc=d.copy(), n_desc=np.zeros(m, np.int32), best_kf=np.full(m, -1, np.int64), best_feat=np.full(m, -1, np.int32))
+            if mask is not None:
+                outs["mask"] = np.ascontiguousarray(mask, np.uint8).reshape(d.shape).copy()
+        for k, a in (init or {}).items():
+            if k in outs:
+                outs[k] = np.ascontiguousarray(a, outs[k].dtype).reshape(outs[k].shape).copy()
+        names = [k for k in self.UPDATE_OUTPUTS if k in outs and k not in skip]
+        ptr, read = self._arrays(device, ins, [outs[k] for k in names])
+        at = dict(zip(names, ptr[4:]))
+        check(lib().mcs_covis_update_points(self.h, n, ptr[0], ptr[1], ptr[2], ptr[3], len(sf), MEM_DEVICE if device else MEM_HOST,
+                                            *[at.get(k) for k in self.UPDATE_OUTPUTS]))
+        return {k: a[:n] for k, a in zip(names, read())}
+
+
 def TrackLocalMapSearch(F, store, points, th=3, nnratio=0.8, featDim=32, havingMasks=False, cap=None, ctx=None):
     """The first two steps of cTracking::TrackLocalMap (src/cTracking.cpp:834-848) as ONE chain of device-kind calls, nothing in between visiting the host:
     mcs_covis_update_reference -> mcs_gather_rows of the per-point tables through the local list -> mcs_search_local_points on the padded list (n = cap) ->
