@@ -188,16 +188,14 @@ static int local_points_common(mcs_ctx* c, const mcs_local_points* pts, const mc
 	}
 	if (int r = ctx_join_greedy(c, s)) return r;   // the frame's arrays may come from a search whose greedy pass runs on the side stream
 	// per-slot scratch, in the context's own buffer for either kind (struct mcs_ctx)
-	Carve cv;
-	const size_t oFresh = cv.take(ns), oActive = cv.take(search ? ns : 0), oCam = cv.take(search ? ns * 4 : 0), oCnt = cv.take(search ? ns * 4 : 0),
-	             oLists = cv.take(search ? ns * kProjListK * 8 : 0);
-	HIPCHK(c->lmBuf.reserve(cv.total));
-	uint8_t* base = c->lmBuf.p;
 	FrustumArgs fa{};
 	fa.npoints = np; fa.nrCams = nr; fa.nlevels = nlevels;
-	fa.fresh = base + oFresh;
-	if (search) { fa.active = base + oActive; fa.pcam = (int*)(base + oCam); }
 	ProjArgs a{};
+	Layout lay;   // the pieces of the search keep their places without it, and bind nothing
+	lay.piece(&fa.fresh, ns); lay.piece(search ? &fa.active : nullptr, search ? ns : 0); lay.piece(search ? &fa.pcam : nullptr, search ? ns * 4 : 0);
+	lay.piece(search ? &a.counts : nullptr, search ? ns * 4 : 0); lay.piece(search ? &a.lists : nullptr, search ? ns * kProjListK * 8 : 0);
+	HIPCHK(c->lmBuf.reserve(lay.total));
+	lay.place(c->lmBuf.p);
 	Staging st(c, kind == MCS_MEM_HOST);
 	st.in(&fa.pos, pts->pos, (size_t)np * 24); st.in(&fa.normal, pts->normal, (size_t)np * 24); st.in(&fa.minDist, pts->min_dist, (size_t)np * 8);
 	st.in(&fa.maxDist, pts->max_dist, (size_t)np * 8); st.in(&fa.flags, pts->flags, (size_t)np);
@@ -215,7 +213,6 @@ static int local_points_common(mcs_ctx* c, const mcs_local_points* pts, const mc
 		a.nproj = (int)ns; a.pstride = stride; a.nfeat = f->n; a.fstride = f->stride; a.nrCams = f->nr_cams;
 		a.th = th; a.ratio = nnratio; a.dim = dim; a.rule = 0; a.cap = kProjListK;
 		a.thHigh = mask ? (int)floor(1.5 * dim) : 3 * dim;   // TH_HIGH_ (src/cORBmatcher.cpp:46-65)
-		a.lists = (unsigned long long*)(base + oLists); a.counts = (int*)(base + oCnt);
 		a.pcam = fa.pcam; a.active = fa.active; a.rowDiv = nr;
 		st.in(&a.pdesc, desc, (size_t)np * stride); st.in(&a.pmask, mask, (size_t)np * stride);
 		st.in(&a.keys, f->keys, nf * sizeof(mcs_keypoint)); st.in(&a.fdesc, f->desc, nf * f->stride); st.in(&a.fmask, f->mask, nf * f->stride); st.in(&a.fcam, f->cam, nf * 4);

@@ -643,63 +643,62 @@ static int kfdb_detect(mcs_kfdb* db, int loop, int nq, const int64_t* query_ids,
 	}
 	const int dcap = diag ? std::max(diag->cap, 0) : 0;
 	const size_t NS = (size_t)nq * S;
-	Carve cv;   // scratch layout
-	const size_t oBm = cv.take((size_t)nq * db->bmWords * 4), oErr = cv.take(4), oQOff = cv.take(((size_t)nq + 1) * 4), oQId = cv.take((size_t)nq * 8),
-	             oMinS = cv.take((size_t)nq * 8), oMinC = cv.take((size_t)nq * 4), oNApp = cv.take((size_t)nq * 4), oCnt = cv.take(NS * 4), oMinw = cv.take(NS * 4),
-	             oWA = cv.take(NS * 4), oFl = cv.take(NS), oSc = cv.take(NS * 8), oConn = cv.take(loop ? NS : 1), oLSlot = cv.take(NS * 4), oLKey = cv.take(NS * 8),
-	             oLAcc = cv.take(NS * 8), oLBest = cv.take(NS * 4), oLOrd = cv.take(NS * 4), oSeen = cv.take(NS), oCandN = cv.take((size_t)nq * 4),
-	             oCand = cv.take((size_t)nq * std::max(cap, 1) * 8), oDN = cv.take((size_t)nq * 4), oDId = cv.take((size_t)nq * std::max(dcap, 1) * 8),
-	             oDW = cv.take((size_t)nq * std::max(dcap, 1) * 4), oDS = cv.take((size_t)nq * std::max(dcap, 1) * 8), oDA = cv.take((size_t)nq * std::max(dcap, 1) * 8),
-	             oDB = cv.take((size_t)nq * std::max(dcap, 1) * 8), oQW = cv.take(host ? total * 4 : 8), oQV = cv.take(host ? total * 8 : 8);
-	HIPCHK(db->scratch.reserve(cv.total));
-	uint8_t* X = db->scratch.p;
-	const int* dQWords = host ? (const int*)(X + oQW) : word_ids;
-	const double* dQVals = host ? (const double*)(X + oQV) : values;
-	HIPCHK(hipMemcpyAsync(X + oQOff, off.data(), ((size_t)nq + 1) * 4, hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemcpyAsync(X + oQId, qid.data(), (size_t)nq * 8, hipMemcpyHostToDevice, st));
+	// scratch layout
+	uint32_t* bm = nullptr; int* err = nullptr; int* qOff = nullptr; int64_t* xQId = nullptr; double* xMinS = nullptr; int* xMinC = nullptr; int* xNApp = nullptr;
+	int* xCnt = nullptr; int* xMinw = nullptr; int* xWA = nullptr; uint8_t* xFl = nullptr; double* xSc = nullptr; uint8_t* xConn = nullptr; int* xLSlot = nullptr;
+	uint64_t* xLKey = nullptr; double* xLAcc = nullptr; int* xLBest = nullptr; int* xLOrd = nullptr; uint8_t* xSeen = nullptr; int* xCandN = nullptr;
+	int64_t* xCand = nullptr; int* xDN = nullptr; int64_t* xDId = nullptr; int* xDW = nullptr; double* xDS = nullptr; double* xDA = nullptr; int64_t* xDB = nullptr;
+	int* xQW = nullptr; double* xQV = nullptr;
+	const size_t QC = (size_t)nq * std::max(cap, 1), QD = (size_t)nq * std::max(dcap, 1);
+	Layout lay;
+	lay.piece(&bm, (size_t)nq * db->bmWords * 4); lay.piece(&err, 4); lay.piece(&qOff, ((size_t)nq + 1) * 4); lay.piece(&xQId, (size_t)nq * 8);
+	lay.piece(&xMinS, (size_t)nq * 8); lay.piece(&xMinC, (size_t)nq * 4); lay.piece(&xNApp, (size_t)nq * 4); lay.piece(&xCnt, NS * 4); lay.piece(&xMinw, NS * 4);
+	lay.piece(&xWA, NS * 4); lay.piece(&xFl, NS); lay.piece(&xSc, NS * 8); lay.piece(&xConn, loop ? NS : 1); lay.piece(&xLSlot, NS * 4); lay.piece(&xLKey, NS * 8);
+	lay.piece(&xLAcc, NS * 8); lay.piece(&xLBest, NS * 4); lay.piece(&xLOrd, NS * 4); lay.piece(&xSeen, NS); lay.piece(&xCandN, (size_t)nq * 4);
+	lay.piece(&xCand, QC * 8); lay.piece(&xDN, (size_t)nq * 4); lay.piece(&xDId, QD * 8); lay.piece(&xDW, QD * 4); lay.piece(&xDS, QD * 8); lay.piece(&xDA, QD * 8);
+	lay.piece(&xDB, QD * 8); lay.piece(&xQW, host ? total * 4 : 8); lay.piece(&xQV, host ? total * 8 : 8);
+	HIPCHK(db->scratch.reserve(lay.total));
+	lay.place(db->scratch.p);
+	const int* dQWords = host ? xQW : word_ids;
+	const double* dQVals = host ? xQV : values;
+	HIPCHK(hipMemcpyAsync(qOff, off.data(), ((size_t)nq + 1) * 4, hipMemcpyHostToDevice, st));
+	HIPCHK(hipMemcpyAsync(xQId, qid.data(), (size_t)nq * 8, hipMemcpyHostToDevice, st));
 	if (loop) {
 		std::vector<double> ms;
 		HIPCHK(fetch(ms, min_scores, nq, kind));
-		HIPCHK(hipMemcpyAsync(X + oMinS, ms.data(), (size_t)nq * 8, hipMemcpyHostToDevice, st));
-		if (conn.empty()) HIPCHK(hipMemsetAsync(X + oConn, 0, NS, st));
-		else HIPCHK(hipMemcpyAsync(X + oConn, conn.data(), NS, hipMemcpyHostToDevice, st));
+		HIPCHK(hipMemcpyAsync(xMinS, ms.data(), (size_t)nq * 8, hipMemcpyHostToDevice, st));
+		if (conn.empty()) HIPCHK(hipMemsetAsync(xConn, 0, NS, st));
+		else HIPCHK(hipMemcpyAsync(xConn, conn.data(), NS, hipMemcpyHostToDevice, st));
 	}
 	if (host && total) {
-		HIPCHK(hipMemcpyAsync(X + oQW, word_ids, total * 4, hipMemcpyHostToDevice, st));
-		HIPCHK(hipMemcpyAsync(X + oQV, values, total * 8, hipMemcpyHostToDevice, st));
+		HIPCHK(hipMemcpyAsync(xQW, word_ids, total * 4, hipMemcpyHostToDevice, st));
+		HIPCHK(hipMemcpyAsync(xQV, values, total * 8, hipMemcpyHostToDevice, st));
 	}
-	HIPCHK(hipMemsetAsync(X + oBm, 0, (size_t)nq * db->bmWords * 4, st));
-	HIPCHK(hipMemsetAsync(X + oErr, 0, 4, st));
-	HIPCHK(hipMemsetAsync(X + oSeen, 0, NS, st));
-	uint32_t* bm = (uint32_t*)(X + oBm);
-	int* err = (int*)(X + oErr);
-	const int* qOff = (const int*)(X + oQOff);
-	hipLaunchKernelGGL(k_qbitmap, dim3(nq), dim3(256), 0, st, qOff, dQWords, nq, db->nWords, db->bmWords, bm, err);
-	CountArgs ca{bm, db->bmWords, nq, S, db->dRowOff, db->dRowLen, db->dActive, db->words, (int*)(X + oCnt), (int*)(X + oMinw)};
+	HIPCHK(hipMemsetAsync(bm, 0, (size_t)nq * db->bmWords * 4, st));
+	HIPCHK(hipMemsetAsync(err, 0, 4, st));
+	HIPCHK(hipMemsetAsync(xSeen, 0, NS, st));
+	hipLaunchKernelGGL(k_qbitmap, dim3(nq), dim3(256), 0, st, (const int*)qOff, dQWords, nq, db->nWords, db->bmWords, bm, err);
+	CountArgs ca{bm, db->bmWords, nq, S, db->dRowOff, db->dRowLen, db->dActive, db->words, xCnt, xMinw};
 	const size_t ldsBytes = (size_t)KF_QG * db->bmWords * 4;
 	const dim3 gc((S + 3) / 4, (nq + KF_QG - 1) / KF_QG);
 	if (ldsBytes <= (size_t)KF_LDS_BYTES) hipLaunchKernelGGL(k_count<true>, gc, dim3(256), ldsBytes, st, ca);
 	else hipLaunchKernelGGL(k_count<false>, gc, dim3(256), 0, st, ca);
 	const int m = loop ? 1 : 0;
 	const int cu = db->cur[m], nx = 1 - cu;
-	WalkArgs wa{nq, S, loop, (const int64_t*)(X + oQId), X + oConn, (const int*)(X + oCnt), db->stQ[m][cu], db->stW[m][cu], db->stQ[m][nx], db->stW[m][nx],
-	            (int*)(X + oWA), X + oFl};
+	WalkArgs wa{nq, S, loop, xQId, xConn, xCnt, db->stQ[m][cu], db->stW[m][cu], db->stQ[m][nx], db->stW[m][nx], xWA, xFl};
 	hipLaunchKernelGGL(k_walk, dim3((S + 255) / 256), dim3(256), 0, st, wa);
-	hipLaunchKernelGGL(k_maxc, dim3(nq), dim3(256), 0, st, S, (const int*)(X + oWA), (const uint8_t*)(X + oFl), (int*)(X + oMinC), (int*)(X + oNApp));
-	ScoreArgs sa{nq, S, loop, qOff, dQWords, dQVals, (const double*)(X + oMinS), db->dRowOff, db->dRowLen, db->words, db->vals, (const int*)(X + oWA),
-	             (const int*)(X + oMinC), X + oFl, (double*)(X + oSc)};
+	hipLaunchKernelGGL(k_maxc, dim3(nq), dim3(256), 0, st, S, (const int*)xWA, (const uint8_t*)xFl, xMinC, xNApp);
+	ScoreArgs sa{nq, S, loop, qOff, dQWords, dQVals, xMinS, db->dRowOff, db->dRowLen, db->words, db->vals, xWA, xMinC, xFl, xSc};
 	hipLaunchKernelGGL(k_score, dim3((S + 255) / 256, nq), dim3(256), 0, st, sa);
-	hipLaunchKernelGGL(k_carry, dim3((S + 255) / 256), dim3(256), 0, st, nq, S, (const uint8_t*)(X + oFl), (double*)(X + oSc), db->stS[m][cu], db->stS[m][nx]);
-	FinalArgs fa{nq, S, loop, (const double*)(X + oMinS), (const int*)(X + oMinC), (const int*)(X + oNApp), (const int*)(X + oWA), (const uint8_t*)(X + oFl),
-	             (const double*)(X + oSc), (const int*)(X + oMinw), db->dAddSeq, db->dId, db->dCovis, db->dCovisN, (int*)(X + oLSlot), (uint64_t*)(X + oLKey),
-	             (double*)(X + oLAcc), (int*)(X + oLBest), (int*)(X + oLOrd), X + oSeen, cap, (int64_t*)(X + oCand), (int*)(X + oCandN), dcap, (int*)(X + oDN),
-	             (int64_t*)(X + oDId), (int*)(X + oDW), (double*)(X + oDS), (double*)(X + oDA), (int64_t*)(X + oDB)};
+	hipLaunchKernelGGL(k_carry, dim3((S + 255) / 256), dim3(256), 0, st, nq, S, (const uint8_t*)xFl, xSc, db->stS[m][cu], db->stS[m][nx]);
+	FinalArgs fa{nq, S, loop, xMinS, xMinC, xNApp, xWA, xFl, xSc, xMinw, db->dAddSeq, db->dId, db->dCovis, db->dCovisN, xLSlot, xLKey, xLAcc, xLBest, xLOrd, xSeen, cap,
+	             xCand, xCandN, dcap, xDN, xDId, xDW, xDS, xDA, xDB};
 	hipLaunchKernelGGL(k_final, dim3(nq), dim3(1024), 0, st, fa);
 	HIPCHK(hipGetLastError());
 	std::vector<int> candN(nq), dN(nq);
 	int errv = 0;
-	HIPCHK(hipMemcpyAsync(candN.data(), X + oCandN, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipMemcpyAsync(dN.data(), X + oDN, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipMemcpyAsync(candN.data(), xCandN, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipMemcpyAsync(dN.data(), xDN, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
 	HIPCHK(hipMemcpyAsync(&errv, err, 4, hipMemcpyDeviceToHost, st));
 	HIPCHK(hipStreamSynchronize(st));
 	if (errv & 1) return fail(MCS_ERR_INVALID, "query BowVector: word id out of range");
@@ -710,17 +709,17 @@ static int kfdb_detect(mcs_kfdb* db, int loop, int nq, const int64_t* query_ids,
 	for (int q = 0; q < nq; ++q) { needC = std::max(needC, candN[q]); needD = std::max(needD, dN[q]); }
 	if (host) memcpy(cand_count, candN.data(), (size_t)nq * 4);
 	else HIPCHK(hipMemcpy(cand_count, candN.data(), (size_t)nq * 4, hipMemcpyHostToDevice));
-	if (cap > 0) HIPCHK(hipMemcpy(cand_ids, X + oCand, (size_t)nq * cap * 8, toUser));
+	if (cap > 0) HIPCHK(hipMemcpy(cand_ids, xCand, (size_t)nq * cap * 8, toUser));
 	if (diag && diag->count) {
 		if (host) memcpy(diag->count, dN.data(), (size_t)nq * 4);
 		else HIPCHK(hipMemcpy(diag->count, dN.data(), (size_t)nq * 4, hipMemcpyHostToDevice));
 		if (dcap > 0) {
 			const size_t nd = (size_t)nq * dcap;
-			HIPCHK(hipMemcpy(diag->kf_id, X + oDId, nd * 8, toUser));
-			HIPCHK(hipMemcpy(diag->words, X + oDW, nd * 4, toUser));
-			HIPCHK(hipMemcpy(diag->score, X + oDS, nd * 8, toUser));
-			HIPCHK(hipMemcpy(diag->acc, X + oDA, nd * 8, toUser));
-			HIPCHK(hipMemcpy(diag->best, X + oDB, nd * 8, toUser));
+			HIPCHK(hipMemcpy(diag->kf_id, xDId, nd * 8, toUser));
+			HIPCHK(hipMemcpy(diag->words, xDW, nd * 4, toUser));
+			HIPCHK(hipMemcpy(diag->score, xDS, nd * 8, toUser));
+			HIPCHK(hipMemcpy(diag->acc, xDA, nd * 8, toUser));
+			HIPCHK(hipMemcpy(diag->best, xDB, nd * 8, toUser));
 		}
 	}
 	if (needC > cap) return fail(MCS_ERR_CAPACITY, "keyframe database: a query has " + std::to_string(needC) + " candidates, cap is " + std::to_string(cap) +

@@ -337,13 +337,12 @@ static int np_chain_device(mcs_ctx* c, int nsets, const mcs_kf_geom* kf1, const 
 	int maxMp = 0;
 	for (int p = 0; p < nsets; ++p) maxMp = std::max(maxMp, kf2[p].n_mp);
 	const size_t eBlock = (size_t)nr * nr * 9;
-	Carve cv;
-	const size_t oE = cv.take(E ? 0 : eBlock * 8 * nsets), oZ = cv.take((size_t)maxMp * 8), oR = cv.take(4), oF = cv.take((size_t)nsets * 4);
-	HIPCHK(c->npBuf.reserve(cv.total));
-	double* Ework = E ? nullptr : (double*)(c->npBuf.p + oE);
-	double* z = (double*)(c->npBuf.p + oZ);
-	int* removed = (int*)(c->npBuf.p + oR);
-	if (!fallbacks) fallbacks = (int32_t*)(c->npBuf.p + oF);
+	double* Ework = nullptr; double* z = nullptr; int* removed = nullptr; int32_t* ownFallbacks = nullptr;
+	Layout lay;
+	lay.piece(E ? nullptr : &Ework, E ? 0 : eBlock * 8 * nsets); lay.piece(&z, (size_t)maxMp * 8); lay.piece(&removed, 4); lay.piece(&ownFallbacks, (size_t)nsets * 4);
+	HIPCHK(c->npBuf.reserve(lay.total));
+	lay.place(c->npBuf.p);
+	if (!fallbacks) fallbacks = ownFallbacks;
 	if (int r = ctx_join_greedy(c, s)) return r;   // an earlier search's greedy pass may still read valid1
 	if (n1 > 0 && valid1 != d1->valid) {
 		if (d1->valid) HIPCHK(hipMemcpyAsync(valid1, d1->valid, (size_t)n1, hipMemcpyDeviceToDevice, s));

@@ -1,5 +1,6 @@
 """The layout half of the host-kind staging (csrc/mcs_carve.h) on its own, without a GPU: every piece 256-byte aligned and at least as long as asked,
-pieces disjoint and in the order of declaration, a zero-byte piece legal with a slot of its own, the block's size the sum of the slots."""
+pieces disjoint and in the order of declaration, a zero-byte piece legal with a slot of its own, the block's size the sum of the slots; and the binding layout
+next to it (Layout), whose offsets and total are Carve's."""
 import os
 import subprocess
 
@@ -22,3 +23,9 @@ def test_carve_layout(tmp_path):
         end = off + size
     assert total == end == sum(size for _, size in pieces)
     assert len({off for off, _ in pieces}) == len(pieces)           # zero-byte pieces have addresses of their own
+    # the binding layout (Layout::piece / place): every bound pointer reads base + the offset Carve::take gives, in declaration order; a piece without a
+    # pointer takes its room (100 bytes -> one 256-byte slot behind the rest)
+    rest = lines[len(sizes) + 1:]
+    bound = [int(v) for v in rest[:len(sizes)]]
+    assert bound == [off for off, _ in pieces]
+    assert int(rest[len(sizes)]) == total + 256
