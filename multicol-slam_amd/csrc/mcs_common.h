@@ -77,7 +77,7 @@ struct OcamDev {
 // Per-camera table of G(s) = rho(theta(s)) / sqrt(s), s = x^2 + y^2 the squared norm of an undistorted pattern point, theta = atan(p0 / sqrt(s)), for the
 // fast descriptor pass: u, v = affine(x * G, y * G) needs neither the square root, the reciprocal nor atan.  Log-spaced bins: row = exponent and top kGM
 // mantissa bits of s (read from the bit pattern), s in [2^kGE0, 2^kGE1); a row holds the degree-kGDeg Taylor coefficients of G about the bin centre in the
-// variable tau = (low mantissa fraction of s) - 2^-(kGM+1), which is exact.  Built by build_g_table() in mcs_capi.hip, which also bounds the truncated tail.
+// variable tau = (low mantissa fraction of s) - 2^-(kGM+1), which is exact.  Built by build_g_table() in mcs_gtable.hip, which also bounds the truncated tail.
 #ifndef MCS_G_M
 #define MCS_G_M 5     // 32 bins per octave, degree 6: 56-byte rows, 54 KB (64 bins, degree 5: 48-byte rows, 0.675 against 0.696 ms, but 92 KB for the same range; 16 bins, degree 8: 0.753 ms)
 #define MCS_G_DEG 6
@@ -88,7 +88,7 @@ struct OcamDev {
 #endif
 constexpr int kGM = MCS_G_M, kGDeg = MCS_G_DEG, kGE0 = MCS_G_E0, kGE1 = MCS_G_E1, kGRows = (kGE1 - kGE0) << kGM, kGRow = kGDeg + 1, kGTabDoubles = kGRows * kGRow;
 // ... as the HOST builds it (kGRow doubles per row).  The DEVICE reads a packed form (round 6): 48-byte rows in three 16-byte slots, [g0 g1] [g2 g3] doubles and
-// [g4 g5 g6 0] floats — three ds_read_b128 per row from LDS instead of seven 8-byte loads; the float tail's roundings are bounded by GTabInfo.f32U (mcs_capi.hip).
+// [g4 g5 g6 0] floats — three ds_read_b128 per row from LDS instead of seven 8-byte loads; the float tail's roundings are bounded by GTabInfo.f32U (mcs_gtable.hip).
 // (Against rows of kGRow doubles, which the compiler reads as three ds_read2_b64 + one ds_read_b64 at half rate: 27 % fewer LDS-array cycles per keypoint, 0.456 against 0.493 ms.)
 static_assert(kGDeg == 6, "the packed device rows hold degree 6");
 constexpr int kGDevRowBytes = 48, kGDevDoubles = kGRows * kGDevRowBytes / 8;
@@ -100,6 +100,8 @@ constexpr int kGDevRowBytes = 48, kGDevDoubles = kGRows * kGDevRowBytes / 8;
 #define MCS_FAST_WAVES 16   // waves per workgroup of the fast descriptor pass (mcs_describe.hip): they share the camera's table in LDS
 #endif
 constexpr int kSlotAlign = MCS_FAST_WAVES > 8 ? MCS_FAST_WAVES : 8;       // keypoint slots per image are a multiple of this (the fast pass walks groups of kFastWaves keypoints of ONE image, a wave each)
+
+inline int kp_slots_per_image(const PyrDesc& d) { return (d.kpCap + kSlotAlign - 1) / kSlotAlign * kSlotAlign; }   // "wavesPerImage" of the kernels: one slot per output row
 
 // Per-keypoint scratch of the descriptor passes (mcs_describe.hip), one array per field over all keypoint slots of the batch (thread-per-keypoint kernels
 // write full cache lines).  lvl: -1 no keypoint, else level | kAuxExact if the keypoint is on the exact pass's list already.

@@ -23,7 +23,7 @@
 //   k_describe_fast   every keypoint.  The 2*8*descSize*npat omni-model evaluations use a cheaper arithmetic (explicit FMAs; G(s) = rho(atan(p0 / sqrt(s))) / sqrt(s)
 //                     from a per-camera table indexed by the bit pattern of s = x^2 + y^2: no square root, no division, no atan, no backward polynomial) and the
 //                     pattern mean is a wave tree sum instead of the reference's sequential chain.  The results differ from the reference's by at most a bound
-//                     delta known per camera (host, mcs_capi.hip: describe_fast_bound) — far below half a pixel, but cvRound(coordinate - mean) only agrees for
+//                     delta known per camera (host, mcs_gtable.hip: describe_fast_bound) — far below half a pixel, but cvRound(coordinate - mean) only agrees for
 //                     sure when no coordinate lies within delta of a rounding tie.  Every coordinate is therefore checked against a guard band eps >= delta
 //                     around the ties (|frac - 0.5| < eps); a keypoint with ANY coordinate inside the band (or out of range / NaN) is not written, its slot goes
 //                     onto the fallback list.  Persistent 16-wave workgroups (table and pattern in LDS once per CU) walk the batch; the walk is software-pipelined
@@ -718,7 +718,7 @@ __global__ __launch_bounds__((64 * SplitGeom<MODE, NB>::WAVES)) void k_describe_
 //      u, v     = affine(xr * G, yr * G)                              without the principal point: it cancels against the pattern mean
 // and a wave tree sum for the mean.  None of this is the reference's rounding; it is only USED when every one of the keypoint's
 // 2 * npat * 2*8*descSize coordinates (minus the mean) stays clear of the rounding ties by more than the guard band b.guardEps, which the host keeps
-// above the worst-case difference between this arithmetic and the reference's (describe_fast_bound in mcs_capi.hip).  Otherwise the
+// above the worst-case difference between this arithmetic and the reference's (describe_fast_bound in mcs_gtable.hip).  Otherwise the
 // keypoint goes to the exact pass.  A point outside the table (s < 2^kGE0, s >= 2^kGE1, NaN / Inf) takes the same way out.
 #ifndef MCS_FAST_FENCE
 #define MCS_FAST_FENCE 4
@@ -1287,7 +1287,7 @@ static void launch_fast_passes(const ExtractBuffers& b, int nimg, int wavesPerIm
 	if (fblocks >= kNumXCD) fblocks = (fblocks + kNumXCD - 1) / kNumXCD * kNumXCD;   // whole XCD rounds: the kernel's block -> group mapping is XCD-contiguous
 	const size_t fLds = (size_t)kFastWaves * fast_wave_lds(NB) + kGDevDoubles * sizeof(double) + fast_pat_bytes(NB);
 	// PRECONDITION: fbCount and preCount — neighbours — were cleared by k_octree's first workgroup, i.e. every launch_describe follows a launch_octree of the same
-	// batch on the same stream, and the previous batch's side-stream pre-list kernel has been joined (the evDescJoin wait below); extract_impl in mcs_capi.hip is
+	// batch on the same stream, and the previous batch's side-stream pre-list kernel has been joined (the evDescJoin wait below); extract_impl in mcs_extract.hip is
 	// the only caller and keeps that order
 	hipLaunchKernelGGL((k_orient_b<MODE>), dim3((nslots + 255) / 256), dim3(256), 0, s, b, wavesPerImage, nslots);
 	// the pre-list (about one keypoint in a hundred: the ones next to the optical axis) through the exact pass BESIDE the fast pass
@@ -1313,7 +1313,7 @@ template <int MODE>
 static void launch_mode(const ExtractBuffers& b, const PyrDesc& hd, int nimg, hipStream_t s) {
 	// ORB: 4 keypoints (waves) per 256-thread block.  dBRIEF/mdBRIEF exact pass: one wave per block with a private 2*NB KiB LDS slice.
 	const int wpb = MODE == 0 ? 4 : 1;
-	const int wavesPerImage = (hd.kpCap + kSlotAlign - 1) / kSlotAlign * kSlotAlign;   // one slot per output row; a multiple of kSlotAlign in every mode
+	const int wavesPerImage = kp_slots_per_image(hd);   // one slot per output row; a multiple of kSlotAlign in every mode
 	const int blocks = nimg * wavesPerImage / wpb;
 	const size_t ldsBytes = (size_t)wpb * (coord_bytes(MODE, hd.npoints) + kPatchBytes);   // coordinates + blurred patch per wave
 	const int nb = hd.descSize / 8;

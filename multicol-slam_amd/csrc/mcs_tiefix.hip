@@ -146,13 +146,13 @@ void describe_host(int mode, int descSize, const signed char* pattern, const Oca
 // ---- the pipelined form (round 6): device-kind batches are consumed on-stream, one step late, while the extractor's pyramid buffers already hold the NEXT
 // batch — so what the host needs of a listed keypoint is captured right behind the descriptor kernels into page-locked memory: its slot, level, position,
 // angle and the (2R + 1)^2 window of Sampler::at values around it (R = kTiePatchR: the pattern's radius is 15 * sqrt(2) = 21.2 px before distortion, and the
-// omni model compresses away from the optical axis).  mcs_extractor_patch_ties (mcs_capi.hip) reads it behind the batch's event.
+// omni model compresses away from the optical axis).  mcs_extractor_patch_ties (mcs_ties.hip) reads it behind the batch's event.
 __global__ __launch_bounds__(256) void k_tie_capture(ExtractBuffers b, int nimg, int wavesPerImage, int maxTies, uint8_t* __restrict__ out) {
 	tie_capture_body(b, nimg, wavesPerImage, maxTies, out, blockIdx.x, gridDim.x);
 }
 
 void launch_tie_capture(const ExtractBuffers& b, const PyrDesc& hd, int nimg, int maxTies, uint8_t* devOut, hipStream_t s) {
-	const int wavesPerImage = (hd.kpCap + kSlotAlign - 1) / kSlotAlign * kSlotAlign;
+	const int wavesPerImage = kp_slots_per_image(hd);
 	hipLaunchKernelGGL(k_tie_capture, dim3(maxTies < 64 ? maxTies : 64), dim3(256), 0, s, b, nimg, wavesPerImage, maxTies, devOut);
 }
 

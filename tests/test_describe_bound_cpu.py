@@ -1,5 +1,5 @@
 """CPU (no GPU): the host-side table and error bound of the guarded fast descriptor arithmetic (mcs_describe_fast_table / mcs_describe_fast_bound,
-csrc/mcs_capi.hip).  The fast pass replaces the reference's WorldToImg (src/cam_model_omni.cpp:146-161) by u, v = affine(x G(s), y G(s)),
+csrc/mcs_gtable.hip).  The fast pass replaces the reference's WorldToImg (src/cam_model_omni.cpp:146-161) by u, v = affine(x G(s), y G(s)),
 G(s) = rho(atan(p0 / sqrt(s))) / sqrt(s) read from a per-camera table indexed by the bit pattern of s = x^2 + y^2.  The bound decides which cameras the
 fast pass may serve, so it is checked here three ways, independently of the C++ that builds it:
   * the table's rows against G itself (numpy long double, atan included) at 40 000 random s: the error never exceeds the tail bound the library claims;

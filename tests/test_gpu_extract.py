@@ -130,6 +130,59 @@ def test_portrait_levels_without_an_octree_root(G, w, h, sf, nl):
     ex.close()
 
 
+def test_replay_second_argument_set_and_return_to_the_first(G):
+    """One small host-kind batch (160x120, mdBRIEF, up to 3 images: the in-order launch sequence, captured into a hipGraph per argument set) with two sets of
+    page-locked outputs.  A host-kind call's output arrays do not enter the kernels' arguments (the kernels write the extractor's staging; k_extract_out copies
+    behind the graph), so a second output set alone is the SAME graph key; what makes a key here is the rays array (ExtractBuffers.rays is null without it) and
+    the image count.  Key A (3 images, rays) six times: calls 2-6 replay; key B (second output set, no rays) twice; A again: a cached key; then C, D, E (2 images
+    with / without rays, 1 image): the fifth key evicts A from the cache of four; A and B once more: captured again behind an eviction.  Every call's keypoints,
+    descriptors, masks and (where asked for) rays are the first call's bit for bit, and the oracle's.  (That calls HIT the cache shows in latency only.)"""
+    import ctypes as C
+    W, H, N = 160, 120, 3
+    kw = dict(nfeatures=300, nlevels=4, fastThreshold=12, do_dBrief=1, learnMasks=1)
+    cams = [G.synth.scaled_camera(c, W, H) for c in G.cams3()]
+    imgs = [G.synth.synth_image(2, i, cams[i]) for i in range(N)]
+    masks = [G.synth.mirror_mask(c) for c in cams]
+    ex = G.mcs.Extractor(G.ctx(), W, H, max_batch=N, **kw)
+    cap, ds = ex.cap, ex.descSize
+    held = []
+
+    def pinned(dtype, shape):
+        n = int(np.prod(shape)) * np.dtype(dtype).itemsize
+        p = C.c_void_p()
+        G.mcs.check(G.mcs.lib().mcs_host_alloc(G.ctx().h, n, C.byref(p)))
+        held.append(p)
+        a = np.frombuffer((C.c_uint8 * n).from_address(p.value), np.uint8)
+        a[:] = 0
+        return p, a.view(dtype).reshape(shape)
+
+    sets = [[pinned(np.int32, (N,)), pinned(G.mcs.KP_DTYPE, (N, cap)), pinned(np.uint8, (N, cap, ds)), pinned(np.uint8, (N, cap, ds)), pinned(np.float64, (N, cap, 3))]
+            for _ in range(2)]
+    im, mk = np.ascontiguousarray(np.stack(imgs)), np.ascontiguousarray(np.stack(masks))
+    camarr = (G.mcs.Ocam * N)(*[G.mcs.make_ocam(c) for c in cams])
+    want = [G.oracle_extract(imgs[i], masks[i], cams[i], **kw)[1:] for i in range(N)]
+    assert sum(len(w[0]) for w in want) > 100
+    first = None
+    A, B, Ck, D, E = (0, N, True), (1, N, False), (1, 2, True), (0, 2, False), (1, 1, True)   # (output set, images, rays)
+    for call, (which, n, with_rays) in enumerate([A] * 6 + [B, B, A, Ck, D, E, A, B]):
+        (p_n, nkp), (p_k, kps), (p_d, desc), (p_m, dmask), (p_r, rays) = sets[which]
+        for _, a in sets[which]:
+            a.view(np.uint8)[...] = 0
+        G.mcs.check(G.mcs.lib().mcs_extract_batch(ex.h, n, G.mcs.np_ptr(im), W * H, W, G.mcs.np_ptr(mk), W * H, W, camarr, G.mcs.MEM_HOST, p_n, p_k, p_d, p_m,
+                                                  p_r if with_rays else None))
+        got = [(kps[i, :nkp[i]].copy(), desc[i, :nkp[i]].copy(), dmask[i, :nkp[i]].copy(), rays[i, :nkp[i]].copy()) for i in range(n)]
+        if first is None:
+            first = got
+            for g, w in zip(got, want):
+                assert all(G.first_diff(a, b) is None for a, b in zip(g, w)), "call 0 against the oracle"
+        assert with_rays or not rays.any()
+        for i, (g, f) in enumerate(zip(got, first)):
+            assert all(G.first_diff(a.view(np.uint8), b.view(np.uint8)) is None for a, b in zip(g[:4 if with_rays else 3], f)), (call, which, n, with_rays, i)
+    for p in held:
+        G.mcs.check(G.mcs.lib().mcs_host_free(G.ctx().h, p))
+    ex.close()
+
+
 def test_empty_image_gives_no_keypoints(G):
     ex = G.mcs.Extractor(G.ctx(), 754, 480, max_batch=1)
     res = ex.extract_host([np.zeros((480, 754), np.uint8)], None, None, want_rays=False)

@@ -1,5 +1,5 @@
 """-m gpu: an extractor that meets more than 64 distinct camera models (the per-camera G(s) tables of the fast descriptor pass are cached per model,
-csrc/mcs_capi.hip).  The 65th model arrives in the SAME batch as an image of a cached model: the table uploaded for every image must be its own camera's
+resolve_cameras in csrc/mcs_extract.hip).  The 65th model arrives in the SAME batch as an image of a cached model: the table uploaded for every image must be its own camera's
 (a cache trimmed in the middle of a batch would hand the fast pass another camera's G(s) — wrong descriptors without any fallback)."""
 import numpy as np
 import pytest
