@@ -978,6 +978,122 @@ int SearchReferencePointsInFrustum(Context& ctx, FR& F, std::vector<MP*>& vpLoca
 	return nrMatches + nmatches;
 }
 
+// ---------------------------------------------------------------------------------------------- the frame-to-frame searches of cTracking
+// A frame flattened for mcs_tracked_frame / mcs_frame_view.  FR as for SearchReferencePointsInFrustum: mvKeys, keypoint_to_cam, cont_idx_to_local_cam_idx,
+// GetDescriptorRowPtr(cam, row) and, with havingMasks, GetDescriptorMaskRowPtr(cam, row).
+struct FlatFrame {
+	std::vector<mcs_keypoint> keys;
+	std::vector<int32_t> cam;
+	std::vector<uint8_t> desc, mask;
+	template <class FR>
+	FlatFrame(const FR& F, int descDim, bool havingMasks) {
+		const size_t nf = F.mvKeys.size();
+		keys.resize(nf); cam.resize(nf); desc.resize(nf * (size_t)descDim); mask.resize(havingMasks ? nf * (size_t)descDim : 0);
+		for (size_t i = 0; i < nf; ++i) {
+			static_assert(sizeof(F.mvKeys[0]) == sizeof(mcs_keypoint), "mvKeys must hold cv::KeyPoint-layout records");
+			std::memcpy(&keys[i], &F.mvKeys[i], sizeof(mcs_keypoint));
+			const int c = (int)F.keypoint_to_cam.find(i)->second, row = (int)F.cont_idx_to_local_cam_idx.find(i)->second;
+			cam[i] = c;
+			std::memcpy(&desc[i * (size_t)descDim], F.GetDescriptorRowPtr(c, row), (size_t)descDim);
+			if (havingMasks) std::memcpy(&mask[i * (size_t)descDim], F.GetDescriptorMaskRowPtr(c, row), (size_t)descDim);
+		}
+	}
+};
+// mvpMapPoints as ids into per-point tables: ids are assigned from pointer identity in first-seen order
+template <class MP>
+struct PointIds {
+	std::map<MP*, int32_t> id;
+	std::vector<MP*> byId;
+	std::vector<double> pos;
+	std::vector<uint8_t> flags;
+	std::vector<int32_t> of(const std::vector<MP*>& v) {
+		std::vector<int32_t> out(v.size(), -1);
+		for (size_t i = 0; i < v.size(); ++i) {
+			MP* p = v[i];
+			if (!p) continue;
+			auto it = id.find(p);
+			if (it == id.end()) {
+				it = id.emplace(p, (int32_t)byId.size()).first;
+				byId.push_back(p);
+				const auto X = p->GetWorldPos();
+				for (int k = 0; k < 3; ++k) pos.push_back(Sim3At(X, k));
+				flags.push_back(p->isBad() ? MCS_LP_BAD : 0);
+			}
+			out[i] = it->second;
+		}
+		return out;
+	}
+	mcs_point_table table() const { return mcs_point_table{pos.data(), flags.data(), (int32_t)byId.size()}; }
+};
+
+// int cORBmatcher::SearchByProjection(cMultiFrame& CurrentFrame, const cMultiFrame& LastFrame, double th) (src/cORBmatcher.cpp:1990-2118), the search of
+// cTracking::TrackWithMotionModel, as ONE device call (mcs_search_last_frame, host kind): CurrentFrame.mvpMapPoints is filled, the reference's value is
+// returned.  FR additionally: camSystem (CurrentFrame), mvpMapPoints, mvbOutlier (LastFrame), mvScaleFactors (CurrentFrame).  MP: GetWorldPos(), isBad().
+template <class FR, class MP>
+int SearchByProjectionLastFrame(Context& ctx, FR& CurrentFrame, const FR& LastFrame, double th, int descDim = 32, bool havingMasks = false,
+                                bool checkOrientation = false) {
+	cMultiCamSys_& cs = CurrentFrame.camSystem;
+	const int nr = cs.GetNrCams();
+	FlatFrame last(LastFrame, descDim, havingMasks), cur(CurrentFrame, descDim, havingMasks);
+	const size_t nl = last.keys.size(), nc = cur.keys.size();
+	PointIds<MP> ids;
+	std::vector<int32_t> lastPoints = ids.of(LastFrame.mvpMapPoints), curPoints = ids.of(CurrentFrame.mvpMapPoints);
+	std::vector<uint8_t> outlier(std::max<size_t>(nl, 1), 0), assigned(std::max<size_t>(nc, 1), 0);
+	for (size_t i = 0; i < nl; ++i) outlier[i] = LastFrame.mvbOutlier[i] ? 1 : 0;
+	for (size_t j = 0; j < nc; ++j) assigned[j] = CurrentFrame.mvpMapPoints[j] ? 1 : 0;
+	std::vector<mcs_ocam> oc;
+	std::vector<const uint8_t*> mm;
+	std::vector<int32_t> w, h;
+	std::vector<double> MtMc((size_t)nr * 16), MtMcInv((size_t)nr * 16);
+	bool any = false;
+	for (int c = 0; c < nr; ++c) {
+		cCamModelGeneral_& m = cs.camModels[c];
+		oc.push_back(m.ocam); w.push_back(m.ocam.width); h.push_back(m.ocam.height);
+		mm.push_back(m.mirrorMask0.empty() ? nullptr : m.mirrorMask0.data); any = any || !m.mirrorMask0.empty();
+		std::memcpy(&MtMc[16 * (size_t)c], cs.MtMc[c].data(), 128); std::memcpy(&MtMcInv[16 * (size_t)c], cs.MtMc_inv[c].data(), 128);
+	}
+	mcs_tracked_frame tf{last.keys.data(), last.desc.data(), havingMasks ? last.mask.data() : nullptr, last.cam.data(), lastPoints.data(), outlier.data(), (int32_t)nl,
+	                     descDim};
+	const mcs_point_table tab = ids.table();
+	mcs_rig_view rig{MtMcInv.data(), MtMc.data(), oc.data(), any ? mm.data() : nullptr, nr};
+	mcs_frame_view fv{cur.keys.data(), cur.desc.data(), havingMasks ? cur.mask.data() : nullptr, cur.cam.data(), assigned.data(), (int32_t)nc, descDim, nr, w.data(),
+	                  h.data(), CurrentFrame.mvScaleFactors.data(), (int32_t)CurrentFrame.mvScaleFactors.size()};
+	std::vector<int32_t> matchCur(std::max<size_t>(nc, 1), -1);
+	int32_t nmatches = 0;
+	mcs_throw(mcs_search_last_frame(ctx.h, &tf, &tab, &rig, &fv, th, descDim, checkOrientation ? 1 : 0, MCS_MEM_HOST, matchCur.data(), curPoints.data(), &nmatches));
+	for (size_t j = 0; j < nc; ++j)
+		if (matchCur[j] >= 0) CurrentFrame.mvpMapPoints[j] = LastFrame.mvpMapPoints[(size_t)matchCur[j]];   // :2075
+	return nmatches;
+}
+
+// int cORBmatcher::WindowSearch(F1, F2, windowSize, vpMapPointMatches2, minScaleLevel, maxScaleLevel) (src/cORBmatcher.cpp:326-473), the first search of
+// cTracking::TrackPreviousFrame, as ONE device call (mcs_window_search_frames, host kind).  vpMapPointMatches2 is rebuilt (F2.mvpMapPoints.size() entries, :333);
+// nnratio is the matcher's mfNNratio.  FR: F2.camSystem gives the cameras and image sizes.
+template <class FR, class MP>
+int WindowSearchFrames(Context& ctx, FR& F1, FR& F2, int windowSize, std::vector<MP*>& vpMapPointMatches2, int minScaleLevel = 0, int maxScaleLevel = 0x7FFFFFFF,
+                       double nnratio = 0.8, int descDim = 32, bool havingMasks = false, bool checkOrientation = false) {
+	cMultiCamSys_& cs = F2.camSystem;
+	const int nr = cs.GetNrCams();
+	FlatFrame f1(F1, descDim, havingMasks), f2(F2, descDim, havingMasks);
+	const size_t n1 = f1.keys.size(), n2 = f2.keys.size();
+	PointIds<MP> ids;
+	std::vector<int32_t> points1 = ids.of(F1.mvpMapPoints);
+	std::vector<int32_t> w, h;
+	for (int c = 0; c < nr; ++c) { w.push_back(cs.camModels[c].ocam.width); h.push_back(cs.camModels[c].ocam.height); }
+	mcs_tracked_frame tf{f1.keys.data(), f1.desc.data(), havingMasks ? f1.mask.data() : nullptr, f1.cam.data(), points1.data(), nullptr, (int32_t)n1, descDim};
+	const mcs_point_table tab = ids.table();
+	mcs_frame_view fv{f2.keys.data(), f2.desc.data(), havingMasks ? f2.mask.data() : nullptr, f2.cam.data(), nullptr, (int32_t)n2, descDim, nr, w.data(), h.data(),
+	                  nullptr, 0};
+	std::vector<int32_t> match21(std::max<size_t>(n2, 1), -1);
+	int32_t nmatches = 0;
+	mcs_throw(mcs_window_search_frames(ctx.h, &tf, &tab, &fv, windowSize, minScaleLevel, maxScaleLevel, nnratio, descDim, checkOrientation ? 1 : 0, MCS_MEM_HOST,
+	                                   match21.data(), nullptr, &nmatches));
+	vpMapPointMatches2.assign(F2.mvpMapPoints.size(), static_cast<MP*>(nullptr));   // :333
+	for (size_t j = 0; j < n2 && j < vpMapPointMatches2.size(); ++j)
+		if (match21[j] >= 0) vpMapPointMatches2[j] = F1.mvpMapPoints[(size_t)match21[j]];   // :428
+	return nmatches;
+}
+
 // ---------------------------------------------------------------------------------------------- the local map and the covisibility counts
 // cTracking::UpdateReferenceKeyFrames / UpdateReferencePoints (src/cTracking.cpp:1024-1123) and the counting and ordering of cMultiKeyFrame::UpdateConnections
 // (src/cMultiKeyFrame.cpp:406-500), cLocalMapping::KeyFrameCulling / MapPointCulling (src/cLocalMapping.cpp:517-593, 187-221) over the device-resident

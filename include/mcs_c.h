@@ -573,6 +573,44 @@ int mcs_search_local_points(mcs_ctx*, const mcs_local_points* pts, const mcs_rig
                             const uint8_t* mask, int stride, const mcs_frame_view* frame, double th, double nnratio, int dim, mcs_mem_kind kind,
                             int32_t* match, int32_t* nmatches, int32_t* n_to_match, int32_t* visible_inc);
 
+/* ------------------------------------------------------------------ the frame-to-frame searches of cTracking, one device call each
+ *   int cORBmatcher::SearchByProjection(cMultiFrame& CurrentFrame, const cMultiFrame& LastFrame, double th)   (src/cORBmatcher.cpp:1990-2118), the search of
+ *       cTracking::TrackWithMotionModel (src/cTracking.cpp:809)
+ *   int cORBmatcher::WindowSearch(F1, F2, windowSize, vpMapPointMatches2, minScaleLevel, maxScaleLevel)        (:326-473), the first search of
+ *       cTracking::TrackPreviousFrame (src/cTracking.cpp:737/743)
+ * A tracked frame is the frame whose map points are carried over (LastFrame / F1): flat in mvKeys order as mcs_frame_view, plus points[i] = mvpMapPoints[i] as an
+ * id into the point table (-1 for NULL) and outlier[i] = mvbOutlier[i] (NULL: none set; WindowSearch never reads it).  The point table is what a resident tracker
+ * keeps for mcs_local_points, indexed by map point id: pos = GetWorldPos() (3 doubles), flags bit0 = MCS_LP_BAD = isBad(), other bits ignored.
+ * mcs_search_last_frame     slot i = feature i of `last`, visited in that order.  A slot is searched unless points[i] < 0, the point is bad, outlier[i] is set, or
+ *     WorldToCamHom_fast + isPointInMirrorMask(u, v, 0) into camera last->cam[i] of `rig` (the CURRENT frame's rig; bounds test alone without mirror_masks) fails;
+ *     the bool of WorldToCamHom_fast (ptRot.z <= 0) is ignored as the reference ignores it.  Window: radius th * cur->scale_factors[octave], levels
+ *     [octave - 1, octave + 1] (octave 0: [-1, 1], a checked range), rule MCS_WINDOW_BEST on cur (cur->assigned read and updated in place).
+ *     match_cur[j] = the feature of `last` whose map point feature j of cur receives, else -1; cur_points (optional, in/out): cur_points[j] = last->points[match_cur[j]]
+ *     for those j only.  check_orientation: mcs_rotation_consistency variant 0; a dropped match ends with match_cur[j] = -1, assigned[j] = 0, cur_points[j] = -1,
+ *     and nmatches is the count minus the drops.
+ * mcs_window_search_frames  a probe for every feature of f1 that holds a good point and passes the octave filters (min_level > 0 / max_level < INT_MAX switch them
+ *     on, as bMinLevel / bMaxLevel): centre (double)kp.pt.x / y, radius window_size, no level check, camera f1->cam[i]; rule MCS_WINDOW_RATIO from an all-free frame
+ *     (f2->assigned, scale_factors, nlevels are neither read nor written).  match21[j] (vnMatches21) and points2[j] (optional; vpMapPointMatches2 as ids) are fully
+ *     written, -1 where unmatched.  check_orientation: variant 1; the histogram is applied only with the flag (:442).
+ * Guards: a point id >= table->n, a camera outside [0, nr_cams) or (mcs_search_last_frame, where it indexes scale_factors) a key octave outside [0, cur->nlevels)
+ * is refused with MCS_ERR_INVALID in host kind before anything runs; in device kind that slot is idle.  n = 0 on either side is a successful no-op (all -1,
+ * nmatches = 0).  Features per frame <= 65536; masks on both sides or neither; rig->nr_cams == cur->nr_cams.  DEVICE: both only enqueue work on the context's
+ * stream — no host wait, no count read back — and every output is complete in the order of that stream when they return; scratch comes from the grow-only buffer
+ * mcs_search_local_points uses.  Refused with MCS_ERR_UNSUPPORTED while deferred searches are on (mcs_ctx_set_async_search). */
+typedef struct {
+	const mcs_keypoint* keys; const uint8_t* desc; const uint8_t* mask; const int32_t* cam;
+	const int32_t* points;    /* mvpMapPoints as ids into the point table, -1 for NULL */
+	const uint8_t* outlier;   /* mvbOutlier; NULL = none set */
+	int32_t n; int32_t stride;
+} mcs_tracked_frame;
+typedef struct { const double* pos; const uint8_t* flags; int32_t n; } mcs_point_table;
+int mcs_search_last_frame(mcs_ctx*, const mcs_tracked_frame* last, const mcs_point_table* pts, const mcs_rig_view* rig /* of the CURRENT frame */,
+                          const mcs_frame_view* cur, double th, int dim, int check_orientation, mcs_mem_kind kind,
+                          int32_t* match_cur /* [cur->n] */, int32_t* cur_points /* optional, [cur->n], in/out */, int32_t* nmatches);
+int mcs_window_search_frames(mcs_ctx*, const mcs_tracked_frame* f1, const mcs_point_table* pts, const mcs_frame_view* f2, int window_size,
+                             int min_level, int max_level, double nnratio, int dim, int check_orientation, mcs_mem_kind kind,
+                             int32_t* match21 /* [f2->n] */, int32_t* points2 /* optional, [f2->n], out */, int32_t* nmatches);
+
 /* ------------------------------------------------------------------ the local map and the covisibility counts on the device
  * cTracking::UpdateReferenceKeyFrames + UpdateReferencePoints (src/cTracking.cpp:1024-1123), the first step of TrackLocalMap, and the counting and ordering of
  * cMultiKeyFrame::UpdateConnections (src/cMultiKeyFrame.cpp:406-500) over a device-resident observation store: one row of map point ids per keyframe.

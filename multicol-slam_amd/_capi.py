@@ -78,6 +78,7 @@ EXPORTS = [
     "mcs_sim3_hypotheses", "mcs_sim3_draw",
     "mcs_triangulate_matches", "mcs_create_new_map_points",
     "mcs_frustum", "mcs_search_local_points",
+    "mcs_search_last_frame", "mcs_window_search_frames",
     "mcs_covis_create", "mcs_covis_destroy", "mcs_covis_clear", "mcs_covis_size", "mcs_covis_slots", "mcs_covis_set_keyframe", "mcs_covis_set_keyframe_pose",
     "mcs_covis_erase_keyframe", "mcs_covis_set_keyframe_bad", "mcs_covis_set_points_bad", "mcs_covis_update_reference", "mcs_covis_update_connections",
     "mcs_gather_rows", "mcs_scatter_rows",
@@ -137,6 +138,15 @@ class TrackState(C.Structure):   # mcs_track_state: mbTrackInView / mTrackProjX 
 
 
 LP_BAD, LP_SEEN = 1, 2   # MCS_LP_* of include/mcs_c.h
+
+
+class TrackedFrame(C.Structure):   # mcs_tracked_frame: the frame whose map points mcs_search_last_frame / mcs_window_search_frames carry over
+    _fields_ = [("keys", C.c_void_p), ("desc", C.c_void_p), ("mask", C.c_void_p), ("cam", C.c_void_p), ("points", C.c_void_p), ("outlier", C.c_void_p),
+                ("n", C.c_int32), ("stride", C.c_int32)]
+
+
+class PointTable(C.Structure):   # mcs_point_table: GetWorldPos() and isBad() (LP_BAD) per map point id
+    _fields_ = [("pos", C.c_void_p), ("flags", C.c_void_p), ("n", C.c_int32)]
 
 
 _lib = None
@@ -240,6 +250,10 @@ def lib():
     L.mcs_frustum.argtypes = [vp, C.POINTER(LocalPoints), C.POINTER(RigView), vp, C.c_int, C.POINTER(TrackState), C.c_int, vp, vp]
     L.mcs_search_local_points.argtypes = [vp, C.POINTER(LocalPoints), C.POINTER(RigView), C.POINTER(TrackState), vp, vp, C.c_int, C.POINTER(FrameView),
                                           C.c_double, C.c_double, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.mcs_search_last_frame.argtypes = [vp, C.POINTER(TrackedFrame), C.POINTER(PointTable), C.POINTER(RigView), C.POINTER(FrameView), C.c_double, C.c_int, C.c_int,
+                                        C.c_int, vp, vp, vp]
+    L.mcs_window_search_frames.argtypes = [vp, C.POINTER(TrackedFrame), C.POINTER(PointTable), C.POINTER(FrameView), C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
+                                           C.c_int, C.c_int, vp, vp, vp]
     L.mcs_covis_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
     L.mcs_covis_destroy.argtypes = [vp]
     L.mcs_covis_clear.argtypes = [vp]

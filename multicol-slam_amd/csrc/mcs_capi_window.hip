@@ -247,6 +247,136 @@ int mcs_search_local_points(mcs_ctx* c, const mcs_local_points* pts, const mcs_r
 	                           n_to_match, visible_inc);
 }
 
+// ---------------------------------------------------------------------------------------------- cTracking::TrackWithMotionModel / TrackPreviousFrame
+// rig != nullptr: SearchByProjection(CurrentFrame, LastFrame, th) (src/cORBmatcher.cpp:1990-2118), tf = LastFrame, f = CurrentFrame;
+// else WindowSearch(F1, F2, ...) (:326-473), tf = F1, f = F2.  matchFeat[f->n] = tracked feature per frame feature, featPoints[f->n] = its point id.
+static int tracked_common(mcs_ctx* c, const mcs_tracked_frame* tf, const mcs_point_table* pts, const mcs_rig_view* rig, const mcs_frame_view* f, double th,
+                          int windowSize, int minLevel, int maxLevel, double nnratio, int dim, int checkOrientation, mcs_mem_kind kind, int32_t* matchFeat,
+                          int32_t* featPoints, int32_t* nmatches) {
+	const bool project = rig != nullptr;
+	if (!c || !tf || !pts || !f || !matchFeat || !nmatches) return fail(MCS_ERR_INVALID, "null argument");
+	if (dim != 16 && dim != 32 && dim != 64) return fail(MCS_ERR_INVALID, "dim must be 16, 32 or 64");
+	if (tf->n < 0 || tf->n > 65536 || f->n < 0 || f->n > 65536 || pts->n < 0 || f->nr_cams < 1 || f->nr_cams > 32)
+		return fail(MCS_ERR_INVALID, "bad sizes (frame features must be <= 65536)");
+	if (project && (rig->nr_cams != f->nr_cams || f->nlevels < 1 || f->nlevels > MCS_MAX_LEVELS)) return fail(MCS_ERR_INVALID, "bad sizes (rig and frame must agree on the cameras)");
+	if ((tf->mask == nullptr) != (f->mask == nullptr)) return fail(MCS_ERR_INVALID, "masks must be given for both sides or neither");
+	if (tf->stride < dim || f->stride < dim || (tf->stride & 3) || (f->stride & 3)) return fail(MCS_ERR_INVALID, "descriptor stride must be >= dim and a multiple of 4");
+	if (c->asyncSearch) return fail(MCS_ERR_UNSUPPORTED, "the probes and the search run in order: switch deferred searches off (mcs_ctx_set_async_search)");
+	const int np = tf->n, nf = f->n, nr = f->nr_cams;
+	if (np > 0 && nf > 0) {
+		if (!tf->keys || !tf->desc || !tf->cam || !tf->points || !f->keys || !f->desc || !f->cam || !f->width || !f->height || (pts->n > 0 && (!pts->pos || !pts->flags)))
+			return fail(MCS_ERR_INVALID, "null argument");
+		if (project && (!rig->MtMc_inv || !rig->cams || !f->scale_factors || !f->assigned)) return fail(MCS_ERR_INVALID, "null argument");
+	}
+	HIPCHK(hipSetDevice(c->device));
+	hipStream_t s = c->stream;
+	if (np == 0 || nf == 0) {   // nobody to track or nothing to find: every entry -1 (WindowSearch starts vpMapPointMatches2 from NULLs), no match
+		if (kind == MCS_MEM_HOST) {
+			for (int j = 0; j < nf; ++j) { matchFeat[j] = -1; if (!project && featPoints) featPoints[j] = -1; }
+			*nmatches = 0;
+			return MCS_OK;
+		}
+		if (nf > 0) HIPCHK(hipMemsetAsync(matchFeat, 0xFF, (size_t)nf * 4, s));
+		if (nf > 0 && !project && featPoints) HIPCHK(hipMemsetAsync(featPoints, 0xFF, (size_t)nf * 4, s));
+		HIPCHK(hipMemsetAsync(nmatches, 0, 4, s));
+		c->lastResultStream = s;   // the memsets are this call's outputs
+		return MCS_OK;
+	}
+	if (kind == MCS_MEM_HOST) {   // what the kernels index with (device kind: such a slot is idle, k_track_probes)
+		if (project)
+			for (int k = 0; k < nr; ++k) {
+				if (rig->cams[k].invP_deg < 1 || rig->cams[k].invP_deg > MCS_MAX_POLY) return fail(MCS_ERR_INVALID, "bad polynomial degree");
+				if (rig->cams[k].width < 1 || rig->cams[k].height < 1) return fail(MCS_ERR_INVALID, "bad image size");
+				if (rig->mirror_masks && !rig->mirror_masks[k]) return fail(MCS_ERR_INVALID, "null mirror mask");
+			}
+		for (int i = 0; i < np; ++i) {
+			if (tf->points[i] < 0) continue;   // NULL: nothing of this feature is read
+			if (tf->points[i] >= pts->n) return fail(MCS_ERR_INVALID, "map point id outside [0, points->n)");
+			if (tf->cam[i] < 0 || tf->cam[i] >= nr) return fail(MCS_ERR_INVALID, "camera index outside [0, nr_cams)");
+			if (project && (tf->keys[i].octave < 0 || tf->keys[i].octave >= f->nlevels)) return fail(MCS_ERR_INVALID, "key octave outside [0, nlevels)");
+		}
+	}
+	if (int r = ctx_join_greedy(c, s)) return r;   // the frame's arrays may come from a search whose greedy pass runs on the side stream
+	// per-slot scratch, in the context's own buffer for either kind (struct mcs_ctx): a device-kind call returns while its kernels still use it
+	TrackArgs t{};
+	ProjArgs a{};
+	TrackTailArgs tail{};
+	int *matchSlot = nullptr, *removed = nullptr;
+	uint8_t* taken = nullptr;
+	Layout lay;
+	lay.piece(&t.px, (size_t)np * 8); lay.piece(&t.py, (size_t)np * 8); lay.piece(&t.rad, (size_t)np * 8); lay.piece(&t.minLvl, (size_t)np * 4);
+	lay.piece(&t.maxLvl, (size_t)np * 4); lay.piece(&t.pcam, (size_t)np * 4); lay.piece(&t.active, (size_t)np);
+	lay.piece(&a.counts, (size_t)np * 4); lay.piece(&a.lists, (size_t)np * kProjListK * 8);
+	lay.piece(&matchSlot, (size_t)np * 4); lay.piece(&removed, 4); lay.piece(&taken, (size_t)nf);
+	HIPCHK(c->lmBuf.reserve(lay.total));
+	lay.place(c->lmBuf.p);
+	// the window form reads neither the rig (MtMcInv, cams, masks stay null) nor outlier, scales, nlevels and th; the projection form none of the last three
+	t.n = np; t.npoints = pts->n; t.project = project ? 1 : 0; t.nrCams = nr; t.nlevels = f->nlevels; t.th = th;
+	t.windowSize = (double)windowSize; t.minLevel = minLevel; t.maxLevel = maxLevel;
+	Staging st(c, kind == MCS_MEM_HOST);
+	st.in(&t.keys, tf->keys, (size_t)np * sizeof(mcs_keypoint)); st.in(&t.cam, tf->cam, (size_t)np * 4); st.in(&t.points, tf->points, (size_t)np * 4);
+	st.in(&t.outlier, project ? tf->outlier : nullptr, (size_t)np);
+	st.in(&t.pos, pts->pos, (size_t)pts->n * 24); st.in(&t.flags, pts->flags, (size_t)pts->n);
+	st.in(&a.pdesc, tf->desc, (size_t)np * tf->stride); st.in(&a.pmask, tf->mask, (size_t)np * tf->stride);
+	std::vector<const uint8_t*> mp(nr, nullptr);
+	if (project) {
+		st.in(&t.MtMcInv, rig->MtMc_inv, (size_t)nr * 128); st.in(&t.cams, rig->cams, (size_t)nr * sizeof(mcs_ocam));
+		if (kind == MCS_MEM_HOST && rig->mirror_masks) {
+			for (int k = 0; k < nr; ++k) st.in(&mp[k], rig->mirror_masks[k], (size_t)rig->cams[k].width * rig->cams[k].height);
+			st.upload(&t.masks, mp.data(), sizeof(void*) * nr);   // commit() binds mp[] before it reads the sources
+		} else t.masks = rig->mirror_masks;
+		st.in(&t.scales, f->scale_factors, (size_t)f->nlevels * 8);
+	}
+	const bool havingMasks = tf->mask != nullptr;
+	a.nproj = np; a.pstride = tf->stride; a.nfeat = nf; a.fstride = f->stride; a.nrCams = nr;
+	a.th = 1.0; a.ratio = nnratio; a.dim = dim; a.rule = project ? (int)MCS_WINDOW_BEST : (int)MCS_WINDOW_RATIO; a.cap = kProjListK;
+	a.thHigh = havingMasks ? (int)floor(1.5 * dim) : 3 * dim;   // TH_HIGH_ / TH_LOW_ (src/cORBmatcher.cpp:46-65)
+	a.thLow = havingMasks ? (int)floor((double)dim) : 2 * dim;
+	a.px = t.px; a.py = t.py; a.rad = t.rad; a.minLvl = t.minLvl; a.maxLvl = t.maxLvl; a.pcam = t.pcam; a.active = t.active; a.rowDiv = 0;
+	st.in(&a.keys, f->keys, (size_t)nf * sizeof(mcs_keypoint)); st.in(&a.fdesc, f->desc, (size_t)nf * f->stride); st.in(&a.fmask, f->mask, (size_t)nf * f->stride);
+	st.in(&a.fcam, f->cam, (size_t)nf * 4); st.in(&a.width, f->width, (size_t)nr * 4); st.in(&a.height, f->height, (size_t)nr * 4);
+	if (project) st.inout(&a.assigned, f->assigned, (size_t)nf);
+	else a.assigned = taken;   // vpMapPointMatches2 starts from NULLs (:333): F2's own matches are neither read nor written
+	a.match = matchSlot;
+	st.out(&a.nmatches, nmatches, 4);
+	tail.matchSlot = matchSlot; tail.n = np; tail.nfeat = nf; tail.clearDropped = project ? 1 : 0;
+	st.out(&tail.matchFeat, matchFeat, (size_t)nf * 4);
+	if (featPoints) { if (project) st.inout(&tail.featPoints, featPoints, (size_t)nf * 4); else st.out(&tail.featPoints, featPoints, (size_t)nf * 4); }
+	if (int r = st.commit()) return r;
+	tail.points = t.points; tail.assigned = project ? a.assigned : nullptr; tail.removed = checkOrientation ? removed : nullptr; tail.nmatches = a.nmatches;
+	if (!project) HIPCHK(hipMemsetAsync(taken, 0, (size_t)nf, s));
+	c->tic("track_probes"); launch_track_probes(t, s); c->toc("track_probes");
+	// grids sized by the host-known slot count; an idle slot leaves at once (k_proj_candidates) and the greedy pass resolves it to -1
+	c->tic("track_candidates"); launch_proj_candidates(a, s); c->toc("track_candidates");
+	c->tic("track_greedy"); launch_proj_greedy(a, s); c->toc("track_greedy");
+	c->tic("track_tail");
+	HIPCHK(hipMemsetAsync(tail.matchFeat, 0xFF, (size_t)nf * 4, s));
+	if (!project && tail.featPoints) HIPCHK(hipMemsetAsync(tail.featPoints, 0xFF, (size_t)nf * 4, s));
+	launch_track_invert(tail, s);
+	if (checkOrientation) {   // :2096-2115 variant 0, :442-462 variant 1; rot = tracked angle - frame angle: the slot is the frame's feature, so swapped
+		const float* angF = reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.keys) + offsetof(mcs_keypoint, angle));
+		const float* angT = reinterpret_cast<const float*>(reinterpret_cast<const char*>(t.keys) + offsetof(mcs_keypoint, angle));
+		launch_rotation_consistency(project ? 0 : 1, angF, (int)sizeof(mcs_keypoint), angT, (int)sizeof(mcs_keypoint), nullptr, tail.matchFeat, nf, 1, removed, s);
+	}
+	launch_track_finish(tail, s);
+	c->toc("track_tail");
+	c->lastResultStream = s;   // every output is complete on the context's stream
+	HIPCHK(hipGetLastError());
+	return st.finish(MCS_OK);
+}
+
+int mcs_search_last_frame(mcs_ctx* c, const mcs_tracked_frame* last, const mcs_point_table* pts, const mcs_rig_view* rig, const mcs_frame_view* cur, double th,
+                          int dim, int check_orientation, mcs_mem_kind kind, int32_t* match_cur, int32_t* cur_points, int32_t* nmatches) {
+	if (!rig) return fail(MCS_ERR_INVALID, "null argument");
+	return tracked_common(c, last, pts, rig, cur, th, 0, 0, 0x7FFFFFFF, 1.0, dim, check_orientation, kind, match_cur, cur_points, nmatches);
+}
+
+int mcs_window_search_frames(mcs_ctx* c, const mcs_tracked_frame* f1, const mcs_point_table* pts, const mcs_frame_view* f2, int window_size, int min_level,
+                             int max_level, double nnratio, int dim, int check_orientation, mcs_mem_kind kind, int32_t* match21, int32_t* points2,
+                             int32_t* nmatches) {
+	return tracked_common(c, f1, pts, nullptr, f2, 0.0, window_size, min_level, max_level, nnratio, dim, check_orientation, kind, match21, points2, nmatches);
+}
+
 int mcs_distinctive_descriptors(mcs_ctx* c, const uint8_t* desc, const uint8_t* mask, int stride, int dim, const int32_t* offsets, int npoints,
                                 mcs_mem_kind kind, int32_t* best_idx) {
 	if (!c || !desc || !offsets || !best_idx) return fail(MCS_ERR_INVALID, "null argument");

@@ -327,6 +327,30 @@ struct FrustumArgs {
 };
 void launch_frustum(const FrustumArgs& a, hipStream_t s);
 
+// the frame-to-frame tracking searches, SearchByProjection(Cur, Last, th) and WindowSearch(F1, F2, ...), on the slots as they lie (mcs_lastframe.hip):
+// slot i = feature i of the tracked frame; the probes go into the window matcher's ProjArgs (px / py / rad / minLvl / maxLvl / pcam / active)
+struct TrackArgs {
+	const mcs_keypoint* keys; const int* cam; const int* points; const uint8_t* outlier; int n;   // the tracked frame; outlier may be nullptr
+	const double* pos; const uint8_t* flags; int npoints;                                          // per-point tables, indexed by points[i]
+	int project;                                                                                   // 1: SearchByProjection(Cur, Last), 0: WindowSearch
+	const double* MtMcInv; const mcs_ocam* cams; const uint8_t* const* masks; int nrCams;          // project: the rig of the frame searched in
+	const double* scales; int nlevels; double th;                                                  // project: mvScaleFactors of the frame searched in
+	double windowSize; int minLevel; int maxLevel;                                                 // window form (minLevel <= 0 / maxLevel == INT_MAX: no filter)
+	double* px; double* py; double* rad; int* minLvl; int* maxLvl; int* pcam; uint8_t* active;     // out, [n]
+};
+void launch_track_probes(const TrackArgs& t, hipStream_t s);
+// the tail: matchSlot[n] (feature per slot) -> matchFeat[nfeat] (slot per feature), then, after the optional rotation filter on matchFeat, the point ids,
+// the features the filter freed and the count
+struct TrackTailArgs {
+	const int* matchSlot; int n; int* matchFeat; int nfeat;
+	const int* points; int* featPoints;   // featPoints optional: [nfeat], the id of the slot's point where feature j keeps its match
+	uint8_t* assigned;                    // optional: cleared where the filter dropped the match
+	int clearDropped;                     // featPoints[j] = -1 where the filter dropped the match
+	const int* removed; int* nmatches;    // removed optional (no filter ran)
+};
+void launch_track_invert(const TrackTailArgs& t, hipStream_t s);
+void launch_track_finish(const TrackTailArgs& t, hipStream_t s);
+
 struct DistinctArgs {   // cMapPoint::ComputeDistinctiveDescriptors for a batch of map points (mcs_distinct.hip)
 	const uint8_t* desc; const uint8_t* mask; int stride; int dim;
 	const int* offsets;   // [npoints + 1] CSR row offsets of the observations of each map point

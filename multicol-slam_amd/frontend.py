@@ -1613,3 +1613,87 @@ def TrackLocalMapSearch(F, store, points, th=3, nnratio=0.8, featDim=32, havingM
     return dict(nmatches=first + nm, search_matches=nm, n_to_match=int(res["ntm"].read()[0]), local_kfs=o["kfs"].read()[:n].tolist(), weights=o["w"].read()[:n].tolist(),
                 dists=o["d"].read()[:n].tolist(), ref_kf=int(o["ref"].read()[0]), local_points=lp[:used].tolist(), n_points=n_points, match=match,
                 visible_inc=vis, search_visible_inc=res["vis"].read()[:cap], frame_points=fp_after)
+
+
+# ---------------------------------------------------------------------------------------------- the frame-to-frame searches of the tracker, one device call each
+def _tracked_call(Fs, Ft, points, featDim, havingMasks, device, rig_of=None):
+    """the arrays of mcs_tracked_frame (Ft: the frame whose points are carried over), mcs_point_table, mcs_frame_view (Fs: the frame searched in) and, with
+    rig_of, mcs_rig_view, in host or device memory -> (structs, arrays by name, keepalive)"""
+    from ._capi import FrameView, PointTable, RigView, TrackedFrame
+    put = (lambda a: DeviceArray(a)) if device else (lambda a: np.ascontiguousarray(a))
+    ptr = (lambda a: None if a is None else a.ptr) if device else np_ptr
+    nr = Fs.camSystem.GetNrCams()
+    a = dict(tkeys=put(np.ascontiguousarray(Ft.mvKeys)), tdesc=put(np.ascontiguousarray(Ft.all_descriptors(), np.uint8)),
+             tmask=put(np.ascontiguousarray(Ft.all_masks(), np.uint8)) if havingMasks else None, tcam=put(np.ascontiguousarray(Ft.keypoint_to_cam, np.int32)),
+             tpoints=put(_point_ids(Ft.mvpMapPoints)), toutlier=put(np.ascontiguousarray(getattr(Ft, "mvbOutlier", np.zeros(Ft.totalN)), np.uint8)),
+             pos=put(np.ascontiguousarray(points["pos"], np.float64)), flags=put(np.ascontiguousarray(points["flags"], np.uint8)),
+             keys=put(np.ascontiguousarray(Fs.mvKeys)), desc=put(np.ascontiguousarray(Fs.all_descriptors(), np.uint8)),
+             mask=put(np.ascontiguousarray(Fs.all_masks(), np.uint8)) if havingMasks else None, cam=put(np.ascontiguousarray(Fs.keypoint_to_cam, np.int32)),
+             assigned=put(np.array([m is not None for m in Fs.mvpMapPoints] or [0], np.uint8)), w=put(np.ascontiguousarray(Fs.mnMaxX, np.int32)),
+             h=put(np.ascontiguousarray(Fs.mnMaxY, np.int32)), sc=put(np.ascontiguousarray(Fs.mvScaleFactors, np.float64)))
+    nsc = len(Fs.mvScaleFactors)
+    tf = TrackedFrame(ptr(a["tkeys"]), ptr(a["tdesc"]), ptr(a["tmask"]), ptr(a["tcam"]), ptr(a["tpoints"]), ptr(a["toutlier"]), Ft.totalN, featDim)
+    tab = PointTable(ptr(a["pos"]), ptr(a["flags"]), len(points["flags"]))
+    fv = FrameView(ptr(a["keys"]), ptr(a["desc"]), ptr(a["mask"]), ptr(a["cam"]), ptr(a["assigned"]), Fs.totalN, featDim, nr, ptr(a["w"]), ptr(a["h"]), ptr(a["sc"]), nsc)
+    rv, keep = None, []
+    if rig_of is not None:
+        rig = _rig_arrays(rig_of)
+        has = all(m is not None for m in rig["masks"])
+        if device:
+            keep = [DeviceArray(rig["MtMc_inv"]), DeviceArray(rig["MtMc"]), DeviceArray(np.frombuffer(rig["ocs"], np.uint8).copy())]
+            mp = None
+            if has:
+                md = [DeviceArray(m) for m in rig["masks"]]
+                mp = DeviceArray(np.array([m.ptr.value for m in md], np.uint64))
+                keep += md + [mp]
+            rv = RigView(keep[0].ptr, keep[1].ptr, keep[2].ptr, mp.ptr if mp else None, nr)
+        else:
+            rv, keep = rig["struct"], [rig]
+    return (tf, tab, fv, rv), a, keep
+
+
+def _track_outputs(n, device, entry_points=None):
+    put = (lambda a: DeviceArray(a)) if device else (lambda a: a)
+    return dict(match=put(np.full(max(n, 1), -1, np.int32)), points=put(np.full(max(n, 1), -1, np.int32) if entry_points is None else entry_points),
+                nm=put(np.zeros(1, np.int32)))
+
+
+def TrackWithMotionModelSearch(Cur, Last, points, th, featDim=32, havingMasks=False, checkOrientation=False, device=False, ctx=None):
+    """The search of cTracking::TrackWithMotionModel, cORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th) (src/cORBmatcher.cpp:1990-2118), as ONE
+    call (mcs_search_last_frame); device=True: device kind — every array in device memory, nothing read back before the call has returned (the pattern of
+    TrackLocalMapSearch).  Cur / Last: cMultiFrames whose mvpMapPoints hold map point ids (or objects with mnId) or None; Last.mvbOutlier per feature.
+    points: the per-id tables pos [n][3] and flags [n] (LP_BAD).  Cur.mvpMapPoints receives the ids of the new matches.
+    -> dict(nmatches, match_cur, cur_points, assigned)"""
+    ctx = ctx or default_context()
+    (tf, tab, fv, rv), a, keep = _tracked_call(Cur, Last, points, featDim, havingMasks, device, Cur.camSystem)
+    n = Cur.totalN
+    o = _track_outputs(n, device, np.resize(_point_ids(Cur.mvpMapPoints), max(n, 1)).astype(np.int32))
+    ptr = (lambda x: x.ptr) if device else np_ptr
+    check(lib().mcs_search_last_frame(ctx.h, C.byref(tf), C.byref(tab), C.byref(rv), C.byref(fv), float(th), featDim, int(bool(checkOrientation)),
+                                      MEM_DEVICE if device else MEM_HOST, ptr(o["match"]), ptr(o["points"]), ptr(o["nm"])))
+    # ---- only now the host looks at anything
+    rd = (lambda x: x.read()) if device else (lambda x: x)
+    match, cp, asg = rd(o["match"])[:n], rd(o["points"])[:n], rd(a["assigned"])[:n]
+    for j in np.flatnonzero(match >= 0):
+        Cur.mvpMapPoints[int(j)] = int(cp[j])          # CurrentFrame.mvpMapPoints[bestIdx2] = pMP, :2075
+    return dict(nmatches=int(rd(o["nm"])[0]), match_cur=match, cur_points=cp, assigned=asg)
+
+
+def TrackPreviousFrameWindowSearch(Last, Cur, points, windowSize, minScaleLevel=0, maxScaleLevel=2**31 - 1, nnratio=0.8, featDim=32, havingMasks=False,
+                                   checkOrientation=False, device=False, ctx=None):
+    """The first search of cTracking::TrackPreviousFrame, cORBmatcher::WindowSearch(LastFrame, CurrentFrame, windowSize, vpMapPointMatches, minScaleLevel,
+    maxScaleLevel) (src/cORBmatcher.cpp:326-473), as ONE call (mcs_window_search_frames); frames and tables as for TrackWithMotionModelSearch (Cur's own
+    matches and Last.mvbOutlier are not read, as in the reference).  Cur.mvpMapPoints becomes vpMapPointMatches2 (ids, None where unmatched), which is what
+    TrackPreviousFrame assigns (src/cTracking.cpp:751).  -> dict(nmatches, match21, points2)"""
+    ctx = ctx or default_context()
+    (tf, tab, fv, rv), a, keep = _tracked_call(Cur, Last, points, featDim, havingMasks, device)
+    n = Cur.totalN
+    o = _track_outputs(n, device)
+    ptr = (lambda x: x.ptr) if device else np_ptr
+    check(lib().mcs_window_search_frames(ctx.h, C.byref(tf), C.byref(tab), C.byref(fv), int(windowSize), int(minScaleLevel), int(min(maxScaleLevel, 2**31 - 1)),
+                                         float(nnratio), featDim, int(bool(checkOrientation)), MEM_DEVICE if device else MEM_HOST, ptr(o["match"]), ptr(o["points"]),
+                                         ptr(o["nm"])))
+    rd = (lambda x: x.read()) if device else (lambda x: x)
+    match, p2 = rd(o["match"])[:n], rd(o["points"])[:n]
+    Cur.mvpMapPoints = [int(p) if p >= 0 else None for p in p2]
+    return dict(nmatches=int(rd(o["nm"])[0]), match21=match, points2=p2)
