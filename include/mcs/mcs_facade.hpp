@@ -453,6 +453,10 @@ public:
 		const KeyPoint* mvKeys = nullptr; const uint8_t* descriptors = nullptr; const uint8_t* masks = nullptr;
 		std::vector<int32_t> keypoint_to_cam; std::vector<uint8_t> hasMapPoint;   // hasMapPoint[i] = mvpMapPoints[i] != NULL (updated by the searches)
 		std::vector<int32_t> width, height; std::vector<double> mvScaleFactors; int n = 0;
+		mcs_frame_view view(int dim, bool havingMasks, uint8_t* assigned) const {
+			return mcs_frame_view{reinterpret_cast<const mcs_keypoint*>(mvKeys), descriptors, havingMasks ? masks : nullptr, keypoint_to_cam.data(), assigned, n, dim,
+			                      (int32_t)width.size(), width.data(), height.data(), mvScaleFactors.data(), (int32_t)mvScaleFactors.size()};
+		}
 	};
 	// WindowSearch(F1, F2, windowSize, vpMapPointMatches2, minScaleLevel, maxScaleLevel): good1[i1] = map point non-NULL && !isBad();
 	// vnMatches21[i2] = i1 or -1.  (:326-473)
@@ -508,9 +512,7 @@ public:
 	int SearchByProjection(FrameGridView& F, const Projections& mp, double th, std::vector<int>& match) {
 		const int n = (int)mp.x.size();
 		mcs_projection_set ps{mp.x.data(), mp.y.data(), mp.viewCos.data(), mp.level.data(), mp.cam.data(), mp.desc, havingMasks ? mp.mask : nullptr, n, mbFeatDim};
-		mcs_frame_view fv{reinterpret_cast<const mcs_keypoint*>(F.mvKeys), F.descriptors, havingMasks ? F.masks : nullptr, F.keypoint_to_cam.data(),
-		                  F.hasMapPoint.data(), F.n, mbFeatDim, (int32_t)F.width.size(), F.width.data(), F.height.data(), F.mvScaleFactors.data(),
-		                  (int32_t)F.mvScaleFactors.size()};
+		const mcs_frame_view fv = F.view(mbFeatDim, havingMasks, F.hasMapPoint.data());
 		match.assign(n > 0 ? n : 1, -1);
 		int32_t nm = 0;
 		mcs_throw(mcs_search_by_projection(ctx_.h, &ps, &fv, th, mfNNratio, mbFeatDim, MCS_MEM_HOST, match.data(), &nm));
@@ -523,9 +525,7 @@ public:
 	int BestInWindows(FrameGridView& F, const Windows& w, int maxDist, bool skipTaken, std::vector<int>& match, std::vector<int>& dist) {
 		const int n = (int)w.x.size();
 		mcs_window_probes pr{w.x.data(), w.y.data(), w.r.data(), w.lo.data(), w.hi.data(), w.cam.data(), w.desc, havingMasks ? w.mask : nullptr, n, mbFeatDim};
-		mcs_frame_view fv{reinterpret_cast<const mcs_keypoint*>(F.mvKeys), F.descriptors, havingMasks ? F.masks : nullptr, F.keypoint_to_cam.data(),
-		                  skipTaken ? F.hasMapPoint.data() : nullptr, F.n, mbFeatDim, (int32_t)F.width.size(), F.width.data(), F.height.data(),
-		                  F.mvScaleFactors.data(), (int32_t)F.mvScaleFactors.size()};
+		const mcs_frame_view fv = F.view(mbFeatDim, havingMasks, skipTaken ? F.hasMapPoint.data() : nullptr);
 		match.assign(n > 0 ? n : 1, -1); dist.assign(n > 0 ? n : 1, 0);
 		int32_t nm = 0;
 		mcs_throw(mcs_window_best(ctx_.h, &pr, &fv, maxDist, skipTaken ? 1 : 0, mbFeatDim, MCS_MEM_HOST, match.data(), dist.data(), &nm));
@@ -559,9 +559,7 @@ private:
 			if (havingMasks) std::memcpy(&m[(size_t)k * mbFeatDim], from.masks + (size_t)p.src[k] * mbFeatDim, mbFeatDim);
 		}
 		mcs_window_probes pr{p.x.data(), p.y.data(), p.r.data(), p.lo.data(), p.hi.data(), p.cam.data(), d.data(), havingMasks ? m.data() : nullptr, n, mbFeatDim};
-		mcs_frame_view fv{reinterpret_cast<const mcs_keypoint*>(in.mvKeys), in.descriptors, havingMasks ? in.masks : nullptr, in.keypoint_to_cam.data(),
-		                  rule == MCS_WINDOW_INITIALIZE ? nullptr : in.hasMapPoint.data(), in.n, mbFeatDim, (int32_t)in.width.size(), in.width.data(),
-		                  in.height.data(), in.mvScaleFactors.data(), (int32_t)in.mvScaleFactors.size()};
+		const mcs_frame_view fv = in.view(mbFeatDim, havingMasks, rule == MCS_WINDOW_INITIALIZE ? nullptr : in.hasMapPoint.data());
 		match.assign(n > 0 ? n : 1, -1);
 		int32_t nm = 0;
 		mcs_throw(mcs_window_match(ctx_.h, &pr, &fv, rule, mfNNratio, mbFeatDim, MCS_MEM_HOST, match.data(), &nm));
@@ -889,6 +887,51 @@ NewMapPoints CreateNewMapPoints(Context& ctx, KF* pKF, const std::vector<KF*>& v
 	return out;
 }
 
+// A camera system flattened for mcs_rig_view, with the image sizes mcs_frame_view carries (matrices = false: the sizes alone, the poses are not read).
+struct FlatRig {
+	std::vector<mcs_ocam> oc;
+	std::vector<const uint8_t*> mm;
+	std::vector<int32_t> w, h;
+	std::vector<double> MtMc, MtMcInv;
+	bool any = false;
+	explicit FlatRig(cMultiCamSys_& cs, bool matrices = true) {
+		for (int c = 0; c < cs.GetNrCams(); ++c) {
+			cCamModelGeneral_& m = cs.camModels[c];
+			oc.push_back(m.ocam); w.push_back(m.ocam.width); h.push_back(m.ocam.height);
+			mm.push_back(m.mirrorMask0.empty() ? nullptr : m.mirrorMask0.data); any = any || !m.mirrorMask0.empty();
+			if (!matrices) continue;
+			MtMc.insert(MtMc.end(), cs.MtMc[c].begin(), cs.MtMc[c].end()); MtMcInv.insert(MtMcInv.end(), cs.MtMc_inv[c].begin(), cs.MtMc_inv[c].end());
+		}
+	}
+	mcs_rig_view view() const { return mcs_rig_view{MtMcInv.data(), MtMc.data(), oc.data(), any ? mm.data() : nullptr, (int32_t)oc.size()}; }
+};
+// A frame flattened for mcs_tracked_frame / mcs_frame_view.  FR: mvKeys (28-byte cv::KeyPoint-layout records), keypoint_to_cam and cont_idx_to_local_cam_idx
+// (find(i)->second), GetDescriptorRowPtr(cam, row) and, with havingMasks, GetDescriptorMaskRowPtr(cam, row).
+struct FlatFrame {
+	std::vector<mcs_keypoint> keys;
+	std::vector<int32_t> cam;
+	std::vector<uint8_t> desc, mask;
+	int dim; bool masks;
+	template <class FR>
+	FlatFrame(const FR& F, int descDim, bool havingMasks) : dim(descDim), masks(havingMasks) {
+		const size_t nf = F.mvKeys.size();
+		keys.resize(nf); cam.resize(nf); desc.resize(nf * (size_t)descDim); mask.resize(havingMasks ? nf * (size_t)descDim : 0);
+		for (size_t i = 0; i < nf; ++i) {
+			static_assert(sizeof(F.mvKeys[0]) == sizeof(mcs_keypoint), "mvKeys must hold cv::KeyPoint-layout records");
+			std::memcpy(&keys[i], &F.mvKeys[i], sizeof(mcs_keypoint));
+			const int c = (int)F.keypoint_to_cam.find(i)->second, row = (int)F.cont_idx_to_local_cam_idx.find(i)->second;
+			cam[i] = c;
+			std::memcpy(&desc[i * (size_t)descDim], F.GetDescriptorRowPtr(c, row), (size_t)descDim);
+			if (havingMasks) std::memcpy(&mask[i * (size_t)descDim], F.GetDescriptorMaskRowPtr(c, row), (size_t)descDim);
+		}
+	}
+	// scales: mvScaleFactors of the frame (null, 0 where the call does not read them)
+	mcs_frame_view view(uint8_t* assigned, const FlatRig& rig, const double* scales, size_t nlevels) const {
+		return mcs_frame_view{keys.data(), desc.data(), masks ? mask.data() : nullptr, cam.data(), assigned, (int32_t)keys.size(), dim, (int32_t)rig.w.size(),
+		                      rig.w.data(), rig.h.data(), scales, (int32_t)nlevels};
+	}
+};
+
 // cTracking::SearchReferencePointsInFrustum (src/cTracking.cpp:953-1012) over mcs_search_local_points: the first loop (:957-976) runs here as written, then
 // cMultiFrame::isInFrustum for every local point in every camera, the nToMatch gate and cORBmatcher::SearchByProjection(F, mvpLocalMapPoints, th) are ONE
 // device call.  Afterwards the tracking fields and visible counts are written back onto the map points, F.mvpMapPoints is filled and the reference's value
@@ -913,9 +956,9 @@ int SearchReferencePointsInFrustum(Context& ctx, FR& F, std::vector<MP*>& vpLoca
 		pMP->mbTrackInView[(int)F.keypoint_to_cam.find(i)->second] = false;
 		++nrMatches;
 	}
-	const size_t np = vpLocalMapPoints.size(), ns = np * (size_t)nr, nf = F.mvKeys.size();
+	const size_t np = vpLocalMapPoints.size(), ns = np * (size_t)nr;
 	if (np == 0) return nrMatches;
-	std::vector<double> pos(3 * np), nrm(3 * np), minD(np), maxD(np), px(ns), py(ns), vc(ns), MtMc((size_t)nr * 16), MtMcInv((size_t)nr * 16);
+	std::vector<double> pos(3 * np), nrm(3 * np), minD(np), maxD(np), px(ns), py(ns), vc(ns);
 	std::vector<uint8_t> flags(np), inView(ns), desc(np * (size_t)descDim), mask(havingMasks ? np * (size_t)descDim : 0);
 	std::vector<int32_t> lvl(ns), vis(np), match(ns, -1);
 	for (size_t i = 0; i < np; ++i) {
@@ -933,33 +976,14 @@ int SearchReferencePointsInFrustum(Context& ctx, FR& F, std::vector<MP*>& vpLoca
 		std::memcpy(&desc[i * (size_t)descDim], pMP->GetDescriptorPtr(), (size_t)descDim);
 		if (havingMasks) std::memcpy(&mask[i * (size_t)descDim], pMP->GetDescriptorMaskPtr(), (size_t)descDim);
 	}
-	std::vector<mcs_ocam> oc;
-	std::vector<const uint8_t*> mm;
-	std::vector<int32_t> w, h;
-	bool any = false;
-	for (int c = 0; c < nr; ++c) {
-		cCamModelGeneral_& m = cs.camModels[c];
-		oc.push_back(m.ocam); w.push_back(m.ocam.width); h.push_back(m.ocam.height);
-		mm.push_back(m.mirrorMask0.empty() ? nullptr : m.mirrorMask0.data); any = any || !m.mirrorMask0.empty();
-		std::memcpy(&MtMc[16 * (size_t)c], cs.MtMc[c].data(), 128); std::memcpy(&MtMcInv[16 * (size_t)c], cs.MtMc_inv[c].data(), 128);
-	}
-	std::vector<mcs_keypoint> keys(nf);
-	std::vector<int32_t> fcam(nf);
-	std::vector<uint8_t> fdesc(nf * (size_t)descDim), fmask(havingMasks ? nf * (size_t)descDim : 0), assigned(std::max<size_t>(nf, 1));
-	for (size_t i = 0; i < nf; ++i) {
-		static_assert(sizeof(F.mvKeys[0]) == sizeof(mcs_keypoint), "mvKeys must hold cv::KeyPoint-layout records");
-		std::memcpy(&keys[i], &F.mvKeys[i], sizeof(mcs_keypoint));
-		const int c = (int)F.keypoint_to_cam.find(i)->second, row = (int)F.cont_idx_to_local_cam_idx.find(i)->second;
-		fcam[i] = c;
-		std::memcpy(&fdesc[i * (size_t)descDim], F.GetDescriptorRowPtr(c, row), (size_t)descDim);
-		if (havingMasks) std::memcpy(&fmask[i * (size_t)descDim], F.GetDescriptorMaskRowPtr(c, row), (size_t)descDim);
-		assigned[i] = F.mvpMapPoints[i] ? 1 : 0;
-	}
+	const FlatRig flatRig(cs);
+	const FlatFrame frame(F, descDim, havingMasks);
+	std::vector<uint8_t> assigned(std::max<size_t>(frame.keys.size(), 1));
+	for (size_t i = 0; i < frame.keys.size(); ++i) assigned[i] = F.mvpMapPoints[i] ? 1 : 0;
 	mcs_local_points lp{pos.data(), nrm.data(), minD.data(), maxD.data(), flags.data(), (int32_t)np};
-	mcs_rig_view rig{MtMcInv.data(), MtMc.data(), oc.data(), any ? mm.data() : nullptr, nr};
+	const mcs_rig_view rig = flatRig.view();
 	mcs_track_state st{inView.data(), px.data(), py.data(), lvl.data(), vc.data()};
-	mcs_frame_view fv{keys.data(), fdesc.data(), havingMasks ? fmask.data() : nullptr, fcam.data(), assigned.data(), (int32_t)nf, descDim, nr, w.data(), h.data(),
-	                  F.mvScaleFactors.data(), (int32_t)F.mvScaleFactors.size()};
+	const mcs_frame_view fv = frame.view(assigned.data(), flatRig, F.mvScaleFactors.data(), F.mvScaleFactors.size());
 	int32_t nmatches = 0, nToMatch = 0;
 	mcs_throw(mcs_search_local_points(ctx.h, &lp, &rig, &st, desc.data(), havingMasks ? mask.data() : nullptr, descDim, &fv, th, nnratio, descDim, MCS_MEM_HOST,
 	                                  match.data(), &nmatches, &nToMatch, vis.data()));
@@ -979,26 +1003,6 @@ int SearchReferencePointsInFrustum(Context& ctx, FR& F, std::vector<MP*>& vpLoca
 }
 
 // ---------------------------------------------------------------------------------------------- the frame-to-frame searches of cTracking
-// A frame flattened for mcs_tracked_frame / mcs_frame_view.  FR as for SearchReferencePointsInFrustum: mvKeys, keypoint_to_cam, cont_idx_to_local_cam_idx,
-// GetDescriptorRowPtr(cam, row) and, with havingMasks, GetDescriptorMaskRowPtr(cam, row).
-struct FlatFrame {
-	std::vector<mcs_keypoint> keys;
-	std::vector<int32_t> cam;
-	std::vector<uint8_t> desc, mask;
-	template <class FR>
-	FlatFrame(const FR& F, int descDim, bool havingMasks) {
-		const size_t nf = F.mvKeys.size();
-		keys.resize(nf); cam.resize(nf); desc.resize(nf * (size_t)descDim); mask.resize(havingMasks ? nf * (size_t)descDim : 0);
-		for (size_t i = 0; i < nf; ++i) {
-			static_assert(sizeof(F.mvKeys[0]) == sizeof(mcs_keypoint), "mvKeys must hold cv::KeyPoint-layout records");
-			std::memcpy(&keys[i], &F.mvKeys[i], sizeof(mcs_keypoint));
-			const int c = (int)F.keypoint_to_cam.find(i)->second, row = (int)F.cont_idx_to_local_cam_idx.find(i)->second;
-			cam[i] = c;
-			std::memcpy(&desc[i * (size_t)descDim], F.GetDescriptorRowPtr(c, row), (size_t)descDim);
-			if (havingMasks) std::memcpy(&mask[i * (size_t)descDim], F.GetDescriptorMaskRowPtr(c, row), (size_t)descDim);
-		}
-	}
-};
 // mvpMapPoints as ids into per-point tables: ids are assigned from pointer identity in first-seen order
 template <class MP>
 struct PointIds {
@@ -1032,8 +1036,7 @@ struct PointIds {
 template <class FR, class MP>
 int SearchByProjectionLastFrame(Context& ctx, FR& CurrentFrame, const FR& LastFrame, double th, int descDim = 32, bool havingMasks = false,
                                 bool checkOrientation = false) {
-	cMultiCamSys_& cs = CurrentFrame.camSystem;
-	const int nr = cs.GetNrCams();
+	const FlatRig flatRig(CurrentFrame.camSystem);
 	FlatFrame last(LastFrame, descDim, havingMasks), cur(CurrentFrame, descDim, havingMasks);
 	const size_t nl = last.keys.size(), nc = cur.keys.size();
 	PointIds<MP> ids;
@@ -1041,23 +1044,11 @@ int SearchByProjectionLastFrame(Context& ctx, FR& CurrentFrame, const FR& LastFr
 	std::vector<uint8_t> outlier(std::max<size_t>(nl, 1), 0), assigned(std::max<size_t>(nc, 1), 0);
 	for (size_t i = 0; i < nl; ++i) outlier[i] = LastFrame.mvbOutlier[i] ? 1 : 0;
 	for (size_t j = 0; j < nc; ++j) assigned[j] = CurrentFrame.mvpMapPoints[j] ? 1 : 0;
-	std::vector<mcs_ocam> oc;
-	std::vector<const uint8_t*> mm;
-	std::vector<int32_t> w, h;
-	std::vector<double> MtMc((size_t)nr * 16), MtMcInv((size_t)nr * 16);
-	bool any = false;
-	for (int c = 0; c < nr; ++c) {
-		cCamModelGeneral_& m = cs.camModels[c];
-		oc.push_back(m.ocam); w.push_back(m.ocam.width); h.push_back(m.ocam.height);
-		mm.push_back(m.mirrorMask0.empty() ? nullptr : m.mirrorMask0.data); any = any || !m.mirrorMask0.empty();
-		std::memcpy(&MtMc[16 * (size_t)c], cs.MtMc[c].data(), 128); std::memcpy(&MtMcInv[16 * (size_t)c], cs.MtMc_inv[c].data(), 128);
-	}
 	mcs_tracked_frame tf{last.keys.data(), last.desc.data(), havingMasks ? last.mask.data() : nullptr, last.cam.data(), lastPoints.data(), outlier.data(), (int32_t)nl,
 	                     descDim};
 	const mcs_point_table tab = ids.table();
-	mcs_rig_view rig{MtMcInv.data(), MtMc.data(), oc.data(), any ? mm.data() : nullptr, nr};
-	mcs_frame_view fv{cur.keys.data(), cur.desc.data(), havingMasks ? cur.mask.data() : nullptr, cur.cam.data(), assigned.data(), (int32_t)nc, descDim, nr, w.data(),
-	                  h.data(), CurrentFrame.mvScaleFactors.data(), (int32_t)CurrentFrame.mvScaleFactors.size()};
+	const mcs_rig_view rig = flatRig.view();
+	const mcs_frame_view fv = cur.view(assigned.data(), flatRig, CurrentFrame.mvScaleFactors.data(), CurrentFrame.mvScaleFactors.size());
 	std::vector<int32_t> matchCur(std::max<size_t>(nc, 1), -1);
 	int32_t nmatches = 0;
 	mcs_throw(mcs_search_last_frame(ctx.h, &tf, &tab, &rig, &fv, th, descDim, checkOrientation ? 1 : 0, MCS_MEM_HOST, matchCur.data(), curPoints.data(), &nmatches));
@@ -1072,18 +1063,14 @@ int SearchByProjectionLastFrame(Context& ctx, FR& CurrentFrame, const FR& LastFr
 template <class FR, class MP>
 int WindowSearchFrames(Context& ctx, FR& F1, FR& F2, int windowSize, std::vector<MP*>& vpMapPointMatches2, int minScaleLevel = 0, int maxScaleLevel = 0x7FFFFFFF,
                        double nnratio = 0.8, int descDim = 32, bool havingMasks = false, bool checkOrientation = false) {
-	cMultiCamSys_& cs = F2.camSystem;
-	const int nr = cs.GetNrCams();
+	const FlatRig sizes(F2.camSystem, false);
 	FlatFrame f1(F1, descDim, havingMasks), f2(F2, descDim, havingMasks);
 	const size_t n1 = f1.keys.size(), n2 = f2.keys.size();
 	PointIds<MP> ids;
 	std::vector<int32_t> points1 = ids.of(F1.mvpMapPoints);
-	std::vector<int32_t> w, h;
-	for (int c = 0; c < nr; ++c) { w.push_back(cs.camModels[c].ocam.width); h.push_back(cs.camModels[c].ocam.height); }
 	mcs_tracked_frame tf{f1.keys.data(), f1.desc.data(), havingMasks ? f1.mask.data() : nullptr, f1.cam.data(), points1.data(), nullptr, (int32_t)n1, descDim};
 	const mcs_point_table tab = ids.table();
-	mcs_frame_view fv{f2.keys.data(), f2.desc.data(), havingMasks ? f2.mask.data() : nullptr, f2.cam.data(), nullptr, (int32_t)n2, descDim, nr, w.data(), h.data(),
-	                  nullptr, 0};
+	const mcs_frame_view fv = f2.view(nullptr, sizes, nullptr, 0);
 	std::vector<int32_t> match21(std::max<size_t>(n2, 1), -1);
 	int32_t nmatches = 0;
 	mcs_throw(mcs_window_search_frames(ctx.h, &tf, &tab, &fv, windowSize, minScaleLevel, maxScaleLevel, nnratio, descDim, checkOrientation ? 1 : 0, MCS_MEM_HOST,

@@ -1,4 +1,5 @@
-// mcs_capi_match.hip — matcher half of the C ABI: top-K Hamming lists and the three brute-force searches of cORBmatcher.
+// mcs_capi_match.hip — matcher half of the C ABI: top-K Hamming lists, the three brute-force searches of cORBmatcher and the single-purpose descriptor calls
+// (distances, valid rows, the distinctive descriptor of a map point, the reciprocal self-test).
 #include "mcs_host.h"
 
 #include <algorithm>
@@ -10,6 +11,7 @@ void launch_single_distance(const uint8_t* a, const uint8_t* b, const uint8_t* m
 void launch_rows_valid(const int* nkp, int nimg, int cap, uint8_t* valid, hipStream_t s);
 void launch_rig_pack_headers(const int* nkp, int nimg, int cap, uint8_t* blocks, int rowStride, hipStream_t s);
 void launch_rig_rows_valid(const uint8_t* blocks, int nimg, int cap, int rowStride, uint8_t* valid, int* nkpOut, hipStream_t s);
+void launch_selftest_recip(unsigned long long seed, int n, int* mismatches, hipStream_t s);
 }
 using namespace mcs;
 
@@ -341,6 +343,46 @@ int mcs_descriptor_distance(mcs_ctx* c, const uint8_t* a, const uint8_t* b, int 
 int mcs_descriptor_distance_masked(mcs_ctx* c, const uint8_t* a, const uint8_t* b, const uint8_t* ma, const uint8_t* mb, int dim, int* out) {
 	if (!ma || !mb) return fail(MCS_ERR_INVALID, "null masks");
 	return single_distance(c, a, b, ma, mb, dim, out);
+}
+
+int mcs_distinctive_descriptors(mcs_ctx* c, const uint8_t* desc, const uint8_t* mask, int stride, int dim, const int32_t* offsets, int npoints,
+                                mcs_mem_kind kind, int32_t* best_idx) {
+	if (!c || !desc || !offsets || !best_idx) return fail(MCS_ERR_INVALID, "null argument");
+	if (dim != 16 && dim != 32 && dim != 64) return fail(MCS_ERR_INVALID, "dim must be 16, 32 or 64");
+	if (stride < dim || (stride & 3) || npoints < 0) return fail(MCS_ERR_INVALID, "bad stride / count");
+	if (npoints == 0) return MCS_OK;
+	size_t rows = 0;
+	if (kind == MCS_MEM_HOST) {   // (device kind: offsets are validated by the caller, and nothing is staged)
+		if (offsets[0] != 0) return fail(MCS_ERR_INVALID, "offsets[0] must be 0");
+		for (int k = 0; k < npoints; ++k)
+			if (offsets[k + 1] < offsets[k] || offsets[k + 1] - offsets[k] > 65535) return fail(MCS_ERR_INVALID, "offsets must be non-decreasing, <= 65535 rows per map point");
+		rows = (size_t)offsets[npoints];
+	}
+	HIPCHK(hipSetDevice(c->device));
+	DistinctArgs a{};
+	a.stride = stride; a.dim = dim; a.npoints = npoints;
+	Staging st(c, kind == MCS_MEM_HOST);
+	st.in(&a.desc, desc, rows * stride); st.in(&a.mask, mask, rows * stride); st.in(&a.offsets, offsets, ((size_t)npoints + 1) * 4);
+	st.out(&a.bestIdx, best_idx, (size_t)npoints * 4);
+	if (int r = st.commit()) return r;
+	launch_distinct(a, c->stream);
+	HIPCHK(hipGetLastError());
+	return st.finish(MCS_OK);
+}
+
+int mcs_selftest_shared_reciprocal(mcs_ctx* c, uint64_t seed, int n, int32_t* mismatches) {
+	if (!c || !mismatches || n < 1) return fail(MCS_ERR_INVALID, "bad argument");
+	HIPCHK(hipSetDevice(c->device));
+	int* d = nullptr;
+	HIPCHK(hipMalloc((void**)&d, 4));
+	(void)hipMemsetAsync(d, 0, 4, c->stream);
+	launch_selftest_recip(seed, n, d, c->stream);
+	const hipError_t e1 = hipGetLastError();
+	const hipError_t e2 = hipMemcpyAsync(mismatches, d, 4, hipMemcpyDeviceToHost, c->stream);
+	const hipError_t e3 = hipStreamSynchronize(c->stream);
+	(void)hipFree(d);
+	if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return fail(MCS_ERR_HIP, "selftest kernel failed");
+	return MCS_OK;
 }
 
 }  // extern "C"

@@ -79,8 +79,9 @@ struct mcs_ctx {
 	// returns without a host wait while its kernels (and the greedy pass on the side stream) still use it, so it cannot live in a block that the next
 	// call lays out afresh.
 	DevBuf npBuf;
-	// mcs_frustum / mcs_search_local_points: per-slot scratch (fresh / active flags, slot cameras, candidate lists and counts; mcs_capi_window.hip).  Its own
-	// buffer for the same reason: the device-kind call returns while its kernels run, and successive calls reuse it in the order of the context's stream.
+	// mcs_frustum / mcs_search_local_points and mcs_search_last_frame / mcs_window_search_frames: per-slot scratch (fresh / active flags, slot cameras, probe
+	// windows, candidate lists and counts, the slot matches; mcs_capi_track.hip).  Its own buffer for the same reason: the device-kind call returns while its
+	// kernels run, and successive calls reuse it in the order of the context's stream.
 	DevBuf lmBuf;
 	// Second HIP stream for the latency-bound / independent kernels (blur next to FAST+oct-tree, the greedy resolution next to the
 	// following batch's extraction): they leave most CUs idle, so overlapping them with the VALU-bound kernels is free throughput.
@@ -120,9 +121,10 @@ inline int ctx_join_greedy(mcs_ctx* c, hipStream_t s) {
 	return MCS_OK;
 }
 
+inline int bad_polynomial_degree() { return fail(MCS_ERR_INVALID, "bad polynomial degree"); }   // also the rig check of the window family (mcs_window_guard.hip)
 // mcs_ocam -> the kernels' camera model (fastOk / tabIdx stay 0: the extractor sets them)
 inline int ocam_to_dev(const mcs_ocam& m, mcs::OcamDev* o) {
-	if (m.p_deg < 1 || m.p_deg > MCS_MAX_POLY || m.invP_deg < 1 || m.invP_deg > MCS_MAX_POLY) return fail(MCS_ERR_INVALID, "bad polynomial degree");
+	if (m.p_deg < 1 || m.p_deg > MCS_MAX_POLY || m.invP_deg < 1 || m.invP_deg > MCS_MAX_POLY) return bad_polynomial_degree();
 	memset(o, 0, sizeof(*o));
 	o->c = m.c; o->d = m.d; o->e = m.e; o->u0 = m.u0; o->v0 = m.v0; o->invAffine = m.c - m.d * m.e;
 	for (int k = 0; k < m.p_deg; ++k) o->p[k] = m.p[k];

@@ -255,13 +255,13 @@ class cMultiFrame:
         as in the reference (:249-250)."""
         pts = _local_points([pMP], None)
         pts["flags"][:] = 0                       # the function itself does not look at isBad() / mnLastFrameSeen
-        rig = _rig_arrays(self.camSystem, [cam])
+        rv, keep = _rig_view(self.camSystem, cams=[cam])
         st = dict(in_view=np.zeros(1, np.uint8), proj_x=np.zeros(1), proj_y=np.zeros(1), level=np.zeros(1, np.int32), view_cos=np.zeros(1))
         vis, ntm = np.zeros(1, np.int32), np.zeros(1, np.int32)
         sc = np.ascontiguousarray(self.mvScaleFactors, np.float64)
         from ._capi import TrackState
         ts = TrackState(*[np_ptr(st[k]) for k in ("in_view", "proj_x", "proj_y", "level", "view_cos")])
-        check(lib().mcs_frustum((ctx or default_context()).h, C.byref(pts["struct"]), C.byref(rig["struct"]), np_ptr(sc), len(sc), C.byref(ts), MEM_HOST,
+        check(lib().mcs_frustum((ctx or default_context()).h, C.byref(pts["struct"]), C.byref(rv), np_ptr(sc), len(sc), C.byref(ts), MEM_HOST,
                                 np_ptr(vis), np_ptr(ntm)))
         pMP.mbTrackInView[cam] = bool(st["in_view"][0])
         if st["in_view"][0]:
@@ -427,7 +427,7 @@ class cORBmatcher:
             if rest:
                 return self.SearchByProjectionFrames(F, vpMapPoints, th, rest[0])
             return self.SearchByProjectionLast(F, vpMapPoints, th)
-        from ._capi import FrameView, ProjectionSet
+        from ._capi import ProjectionSet
         nr = F.camSystem.GetNrCams()
         owner, px, py, vc, lv, pc, dd, mm = [], [], [], [], [], [], [], []
         for pMP in vpMapPoints:                       # the reference's visiting order: map point, then camera
@@ -447,16 +447,8 @@ class cORBmatcher:
         lv, pc = np.ascontiguousarray(lv, np.int32), np.ascontiguousarray(pc, np.int32)
         dd = np.ascontiguousarray(np.stack(dd), np.uint8)
         mm = np.ascontiguousarray(np.stack(mm), np.uint8) if self.havingMasks else None
-        keys = np.ascontiguousarray(F.mvKeys)
-        fd = np.ascontiguousarray(F.all_descriptors(), np.uint8)
-        fm = np.ascontiguousarray(F.all_masks(), np.uint8) if self.havingMasks else None
-        fc = np.ascontiguousarray(F.keypoint_to_cam, np.int32)
-        assigned = np.array([m is not None for m in F.mvpMapPoints], np.uint8)
-        w, h = np.ascontiguousarray(F.mnMaxX, np.int32), np.ascontiguousarray(F.mnMaxY, np.int32)
-        sc = np.ascontiguousarray(F.mvScaleFactors, np.float64)
         mp = ProjectionSet(np_ptr(px), np_ptr(py), np_ptr(vc), np_ptr(lv), np_ptr(pc), np_ptr(dd), np_ptr(mm), n, self.mbFeatDim)
-        fv = FrameView(np_ptr(keys), np_ptr(fd), np_ptr(fm), np_ptr(fc), np_ptr(assigned), F.totalN, self.mbFeatDim, nr, np_ptr(w), np_ptr(h), np_ptr(sc),
-                       len(sc))
+        fv, keep = _frame_view(F, self.mbFeatDim, self.havingMasks, np.array([m is not None for m in F.mvpMapPoints], np.uint8))
         match = np.full(n, -1, np.int32)
         nm = np.zeros(1, np.int32)
         check(lib().mcs_search_by_projection(self.ctx.h, C.byref(mp), C.byref(fv), float(th), self.mfNNratio, self.mbFeatDim, MEM_HOST, np_ptr(match),
@@ -467,18 +459,6 @@ class cORBmatcher:
         return int(nm[0])
 
     # ------------------------------------------------------------------ grid-window searches other than (F, mapPoints)
-    def _frame_view(self, F, assigned):
-        from ._capi import FrameView
-        keys = np.ascontiguousarray(F.mvKeys)
-        fd = np.ascontiguousarray(F.all_descriptors(), np.uint8)
-        fm = np.ascontiguousarray(F.all_masks(), np.uint8) if self.havingMasks else None
-        fc = np.ascontiguousarray(F.keypoint_to_cam, np.int32)
-        w, h = np.ascontiguousarray(F.mnMaxX, np.int32), np.ascontiguousarray(F.mnMaxY, np.int32)
-        sc = np.ascontiguousarray(F.mvScaleFactors, np.float64)
-        fv = FrameView(np_ptr(keys), np_ptr(fd), np_ptr(fm), np_ptr(fc), np_ptr(assigned), F.totalN, self.mbFeatDim, F.camSystem.GetNrCams(), np_ptr(w),
-                       np_ptr(h), np_ptr(sc), len(sc))
-        return fv, (keys, fd, fm, fc, w, h, sc, assigned)
-
     def _window_match(self, rule, x, y, r, lo, hi, cam, rows, F1, F2, assigned):
         """probes (window centre / radius / level range / camera / descriptor row of F1) against frame F2 -> (match per probe, nmatches)"""
         from ._capi import WindowProbes
@@ -493,7 +473,7 @@ class cORBmatcher:
         self.last_accepted = np.full(n, -1, np.int32)
         pr = WindowProbes(np_ptr(x), np_ptr(y), np_ptr(r), np_ptr(lo), np_ptr(hi), np_ptr(cam), np_ptr(dd), np_ptr(mm), n, self.mbFeatDim,
                           np_ptr(self.last_accepted) if rule == 3 else None)
-        fv, keep = self._frame_view(F2, assigned)
+        fv, keep = _frame_view(F2, self.mbFeatDim, self.havingMasks, assigned)
         match = np.full(n, -1, np.int32)
         nm = np.zeros(1, np.int32)
         check(lib().mcs_window_match(self.ctx.h, C.byref(pr), C.byref(fv), rule, self.mfNNratio, self.mbFeatDim, MEM_HOST, np_ptr(match), np_ptr(nm)))
@@ -515,7 +495,7 @@ class cORBmatcher:
         pr = WindowProbes(np_ptr(x), np_ptr(y), np_ptr(r), np_ptr(lo), np_ptr(hi), np_ptr(cam), np_ptr(dd), np_ptr(mm), n, self.mbFeatDim)
         if skip_taken and assigned is None:
             assigned = np.array([m is not None for m in F.mvpMapPoints] + [0] * (F.totalN == 0), np.uint8)
-        fv, keep = self._frame_view(F, assigned if skip_taken else None)
+        fv, keep = _frame_view(F, self.mbFeatDim, self.havingMasks, assigned if skip_taken else None)
         match, dist, nm = np.full(n, -1, np.int32), np.zeros(n, np.int32), np.zeros(1, np.int32)
         check(lib().mcs_window_best(self.ctx.h, C.byref(pr), C.byref(fv), int(max_dist), int(bool(skip_taken)), self.mbFeatDim, MEM_HOST, np_ptr(match),
                                     np_ptr(dist), np_ptr(nm)))
@@ -733,6 +713,46 @@ def _rig_arrays(camSystem, cams=None):
     return a
 
 
+class _Mem:
+    """where the arrays of a call live, host memory (numpy arrays) or device memory (DeviceArray copies): put / ptr / read of an array and the MEM_* kind"""
+
+    def __init__(self, device):
+        self.device, self.kind = device, MEM_DEVICE if device else MEM_HOST
+        self.put = lambda a: None if a is None else DeviceArray(a) if device else np.ascontiguousarray(a)
+        self.ptr = lambda a: None if a is None else a.ptr if device else np_ptr(a)
+        self.read = lambda a: a.read() if device else a
+
+
+_HOST, _DEVICE = _Mem(False), _Mem(True)
+
+
+def _frame_view(F, featDim, havingMasks, assigned, mem=_HOST):
+    """mcs_frame_view of a cMultiFrame in host or device memory -> (FrameView, the arrays behind it by name); `assigned` is the host call's array itself"""
+    from ._capi import FrameView
+    a = dict(keys=F.mvKeys, desc=np.asarray(F.all_descriptors(), np.uint8), mask=np.asarray(F.all_masks(), np.uint8) if havingMasks else None,
+             cam=np.asarray(F.keypoint_to_cam, np.int32), assigned=assigned, w=np.asarray(F.mnMaxX, np.int32), h=np.asarray(F.mnMaxY, np.int32),
+             sc=np.asarray(F.mvScaleFactors, np.float64))
+    a = {k: mem.put(v) for k, v in a.items()}
+    fv = FrameView(*[mem.ptr(a[k]) for k in ("keys", "desc", "mask", "cam", "assigned")], F.totalN, featDim, F.camSystem.GetNrCams(), mem.ptr(a["w"]),
+                   mem.ptr(a["h"]), mem.ptr(a["sc"]), len(F.mvScaleFactors))
+    return fv, a
+
+
+def _rig_view(camSystem, mem=_HOST, cams=None):
+    """mcs_rig_view of a cMultiCamSys_ (all cameras, or the listed ones) in host or device memory -> (RigView, keepalive)"""
+    from ._capi import RigView
+    rig = _rig_arrays(camSystem, cams)
+    if not mem.device:
+        return rig["struct"], rig
+    keep = [DeviceArray(rig["MtMc_inv"]), DeviceArray(rig["MtMc"]), DeviceArray(np.frombuffer(rig["ocs"], np.uint8).copy())]
+    mp = None
+    if all(m is not None for m in rig["masks"]):
+        md = [DeviceArray(m) for m in rig["masks"]]
+        mp = DeviceArray(np.array([m.ptr.value for m in md], np.uint64))
+        keep += md + [mp]
+    return RigView(keep[0].ptr, keep[1].ptr, keep[2].ptr, mp.ptr if mp else None, len(rig["masks"])), keep
+
+
 def SearchReferencePointsInFrustum(F, vpLocalMapPoints, th=3, nnratio=0.8, featDim=32, havingMasks=False, ctx=None):
     """int cTracking::SearchReferencePointsInFrustum() (src/cTracking.cpp:953-1012) for frame F (mCurrentFrame) and vpLocalMapPoints (mvpLocalMapPoints).
     The first loop (:957-976) runs here as written; isInFrustum for every local point in every camera, the nToMatch gate and
@@ -740,7 +760,7 @@ def SearchReferencePointsInFrustum(F, vpLocalMapPoints, th=3, nnratio=0.8, featD
     IncreaseVisible() counts are written back onto the map points, F.mvpMapPoints is filled, the reference's value is returned.  Map points:
     GetWorldPos(), GetNormal(), GetMinDistanceInvariance(), GetMaxDistanceInvariance(), isBad(), IncreaseVisible(), mnLastFrameSeen, GetDescriptor() /
     GetDescriptorMask() (numpy rows) and the per-camera lists mbTrackInView, mTrackProjX, mTrackProjY, mnTrackScaleLevel, mTrackViewCos."""
-    from ._capi import FrameView, TrackState
+    from ._capi import TrackState
     ctx = ctx or default_context()
     nr = F.camSystem.GetNrCams()
     nrMatches = 0
@@ -758,24 +778,17 @@ def SearchReferencePointsInFrustum(F, vpLocalMapPoints, th=3, nnratio=0.8, featD
     if n == 0:
         return nrMatches
     pts = _local_points(vpLocalMapPoints, F.mnId)
-    rig = _rig_arrays(F.camSystem)
+    rv, keep = _rig_view(F.camSystem)
     st = dict(in_view=np.array([[bool(v) for v in m.mbTrackInView[:nr]] for m in vpLocalMapPoints], np.uint8),
               proj_x=np.array([m.mTrackProjX[:nr] for m in vpLocalMapPoints], np.float64), proj_y=np.array([m.mTrackProjY[:nr] for m in vpLocalMapPoints], np.float64),
               level=np.array([m.mnTrackScaleLevel[:nr] for m in vpLocalMapPoints], np.int32), view_cos=np.array([m.mTrackViewCos[:nr] for m in vpLocalMapPoints], np.float64))
     ts = TrackState(*[np_ptr(st[k]) for k in ("in_view", "proj_x", "proj_y", "level", "view_cos")])
     dd = np.ascontiguousarray(np.stack([m.GetDescriptor() for m in vpLocalMapPoints]), np.uint8)
     mm = np.ascontiguousarray(np.stack([m.GetDescriptorMask() for m in vpLocalMapPoints]), np.uint8) if havingMasks else None
-    keys = np.ascontiguousarray(F.mvKeys)
-    fd = np.ascontiguousarray(F.all_descriptors(), np.uint8)
-    fm = np.ascontiguousarray(F.all_masks(), np.uint8) if havingMasks else None
-    fc = np.ascontiguousarray(F.keypoint_to_cam, np.int32)
-    assigned = np.array([m is not None for m in F.mvpMapPoints] or [0], np.uint8)
-    w, h = np.ascontiguousarray(F.mnMaxX, np.int32), np.ascontiguousarray(F.mnMaxY, np.int32)
-    sc = np.ascontiguousarray(F.mvScaleFactors, np.float64)
-    fv = FrameView(np_ptr(keys), np_ptr(fd), np_ptr(fm), np_ptr(fc), np_ptr(assigned), F.totalN, featDim, nr, np_ptr(w), np_ptr(h), np_ptr(sc), len(sc))
+    fv, fa = _frame_view(F, featDim, havingMasks, np.array([m is not None for m in F.mvpMapPoints] or [0], np.uint8))
     match, vis = np.full(n * nr, -1, np.int32), np.zeros(n, np.int32)
     nm, ntm = np.zeros(1, np.int32), np.zeros(1, np.int32)
-    check(lib().mcs_search_local_points(ctx.h, C.byref(pts["struct"]), C.byref(rig["struct"]), C.byref(ts), np_ptr(dd), np_ptr(mm), featDim, C.byref(fv), float(th),
+    check(lib().mcs_search_local_points(ctx.h, C.byref(pts["struct"]), C.byref(rv), C.byref(ts), np_ptr(dd), np_ptr(mm), featDim, C.byref(fv), float(th),
                                         float(nnratio), featDim, MEM_HOST, np_ptr(match), np_ptr(nm), np_ptr(ntm), np_ptr(vis)))
     for i, pMP in enumerate(vpLocalMapPoints):
         for _ in range(int(vis[i])):             # :995
@@ -1425,10 +1438,9 @@ class cCovisibility:
     # in device memory, nothing read back before the call has returned (the pattern of TrackLocalMapSearch) — with the same results.
     def _arrays(self, device, ins, outs):
         """-> (pointers of ins + outs, reader of the outs)"""
-        if device:
-            d = [DeviceArray(a) for a in list(ins) + list(outs)]
-            return [x.ptr for x in d], lambda: [x.read() for x in d[len(ins):]]
-        return [np_ptr(a) for a in list(ins) + list(outs)], lambda: list(outs)
+        mem = _DEVICE if device else _HOST
+        d = [mem.put(a) for a in list(ins) + list(outs)]
+        return [mem.ptr(x) for x in d], lambda: [mem.read(x) for x in d[len(ins):]]
 
     def SetOctaves(self, pKF, octaves=None, device=False):
         """octaves[i] = pKF.GetKeyPoint(i).octave (default: the keyframe's keypoints)"""
@@ -1535,7 +1547,7 @@ def TrackLocalMapSearch(F, store, points, th=3, nnratio=0.8, featDim=32, havingM
     view_cos [n][nr_cams]; the tracking state is updated in place.  The frame's first loop (:957-976) runs here on the arrays.
     -> dict(nmatches (the reference's return value), n_to_match, local_kfs, weights, dists, ref_kf, local_points, n_points, match [cap][nr_cams],
     visible_inc [n] (IncreaseVisible() calls per point id, first loop included), frame_points)"""
-    from ._capi import LP_BAD, LP_SEEN, FrameView, LocalPoints, RigView, TrackState
+    from ._capi import LP_BAD, LP_SEEN, LocalPoints, TrackState
     ctx = ctx or store.ctx
     L = lib()
     nr = F.camSystem.GetNrCams()
@@ -1574,21 +1586,10 @@ def TrackLocalMapSearch(F, store, points, th=3, nnratio=0.8, featDim=32, havingM
         g[k] = dev(np.zeros((max(cap, 1),) + a.arr.shape[1:], a.arr.dtype))
         fill = np.array([LP_BAD], np.uint8) if k == "flags" else None
         check(L.mcs_gather_rows(ctx.h, o["lp"].ptr, cap, a.ptr, row, np_ptr(fill), g[k].ptr))
-    rig = _rig_arrays(F.camSystem)
-    keep = [dev(rig["MtMc_inv"]), dev(rig["MtMc"]), dev(np.frombuffer(rig["ocs"], np.uint8).copy())]
-    mp = None
-    if all(m is not None for m in rig["masks"]):
-        md = [dev(m) for m in rig["masks"]]
-        mp = dev(np.array([m.ptr.value for m in md], np.uint64))
-        keep += md + [mp]
-    rv = RigView(keep[0].ptr, keep[1].ptr, keep[2].ptr, mp.ptr if mp else None, nr)
+    rv, keep = _rig_view(F.camSystem, _DEVICE)
     lpv = LocalPoints(g["pos"].ptr, g["normal"].ptr, g["min_dist"].ptr, g["max_dist"].ptr, g["flags"].ptr, cap)
     ts = TrackState(*[g[k].ptr for k in ("in_view", "proj_x", "proj_y", "level", "view_cos")])
-    sc = np.ascontiguousarray(F.mvScaleFactors, np.float64)
-    fa = [dev(np.ascontiguousarray(F.mvKeys)), dev(np.ascontiguousarray(F.all_descriptors(), np.uint8)),
-          dev(np.ascontiguousarray(F.all_masks(), np.uint8)) if havingMasks else None, dev(fcam), dev(assigned), dev(np.ascontiguousarray(F.mnMaxX, np.int32)),
-          dev(np.ascontiguousarray(F.mnMaxY, np.int32)), dev(sc)]
-    fv = FrameView(fa[0].ptr, fa[1].ptr, fa[2].ptr if fa[2] else None, fa[3].ptr, fa[4].ptr, F.totalN, featDim, nr, fa[5].ptr, fa[6].ptr, fa[7].ptr, len(sc))
+    fv, fa = _frame_view(F, featDim, havingMasks, assigned, _DEVICE)
     res = dict(match=dev(np.full(max(cap * nr, 1), -1, np.int32)), nm=dev(np.zeros(1, np.int32)), ntm=dev(np.zeros(1, np.int32)), vis=dev(np.zeros(max(cap, 1), np.int32)))
     check(L.mcs_search_local_points(ctx.h, C.byref(lpv), C.byref(rv), C.byref(ts), g["desc"].ptr, g["mask"].ptr if havingMasks else None, featDim, C.byref(fv),
                                     float(th), float(nnratio), featDim, MEM_DEVICE, res["match"].ptr, res["nm"].ptr, res["ntm"].ptr, res["vis"].ptr))
@@ -1618,44 +1619,25 @@ def TrackLocalMapSearch(F, store, points, th=3, nnratio=0.8, featDim=32, havingM
 # ---------------------------------------------------------------------------------------------- the frame-to-frame searches of the tracker, one device call each
 def _tracked_call(Fs, Ft, points, featDim, havingMasks, device, rig_of=None):
     """the arrays of mcs_tracked_frame (Ft: the frame whose points are carried over), mcs_point_table, mcs_frame_view (Fs: the frame searched in) and, with
-    rig_of, mcs_rig_view, in host or device memory -> (structs, arrays by name, keepalive)"""
-    from ._capi import FrameView, PointTable, RigView, TrackedFrame
-    put = (lambda a: DeviceArray(a)) if device else (lambda a: np.ascontiguousarray(a))
-    ptr = (lambda a: None if a is None else a.ptr) if device else np_ptr
-    nr = Fs.camSystem.GetNrCams()
-    a = dict(tkeys=put(np.ascontiguousarray(Ft.mvKeys)), tdesc=put(np.ascontiguousarray(Ft.all_descriptors(), np.uint8)),
-             tmask=put(np.ascontiguousarray(Ft.all_masks(), np.uint8)) if havingMasks else None, tcam=put(np.ascontiguousarray(Ft.keypoint_to_cam, np.int32)),
-             tpoints=put(_point_ids(Ft.mvpMapPoints)), toutlier=put(np.ascontiguousarray(getattr(Ft, "mvbOutlier", np.zeros(Ft.totalN)), np.uint8)),
-             pos=put(np.ascontiguousarray(points["pos"], np.float64)), flags=put(np.ascontiguousarray(points["flags"], np.uint8)),
-             keys=put(np.ascontiguousarray(Fs.mvKeys)), desc=put(np.ascontiguousarray(Fs.all_descriptors(), np.uint8)),
-             mask=put(np.ascontiguousarray(Fs.all_masks(), np.uint8)) if havingMasks else None, cam=put(np.ascontiguousarray(Fs.keypoint_to_cam, np.int32)),
-             assigned=put(np.array([m is not None for m in Fs.mvpMapPoints] or [0], np.uint8)), w=put(np.ascontiguousarray(Fs.mnMaxX, np.int32)),
-             h=put(np.ascontiguousarray(Fs.mnMaxY, np.int32)), sc=put(np.ascontiguousarray(Fs.mvScaleFactors, np.float64)))
-    nsc = len(Fs.mvScaleFactors)
-    tf = TrackedFrame(ptr(a["tkeys"]), ptr(a["tdesc"]), ptr(a["tmask"]), ptr(a["tcam"]), ptr(a["tpoints"]), ptr(a["toutlier"]), Ft.totalN, featDim)
-    tab = PointTable(ptr(a["pos"]), ptr(a["flags"]), len(points["flags"]))
-    fv = FrameView(ptr(a["keys"]), ptr(a["desc"]), ptr(a["mask"]), ptr(a["cam"]), ptr(a["assigned"]), Fs.totalN, featDim, nr, ptr(a["w"]), ptr(a["h"]), ptr(a["sc"]), nsc)
-    rv, keep = None, []
-    if rig_of is not None:
-        rig = _rig_arrays(rig_of)
-        has = all(m is not None for m in rig["masks"])
-        if device:
-            keep = [DeviceArray(rig["MtMc_inv"]), DeviceArray(rig["MtMc"]), DeviceArray(np.frombuffer(rig["ocs"], np.uint8).copy())]
-            mp = None
-            if has:
-                md = [DeviceArray(m) for m in rig["masks"]]
-                mp = DeviceArray(np.array([m.ptr.value for m in md], np.uint64))
-                keep += md + [mp]
-            rv = RigView(keep[0].ptr, keep[1].ptr, keep[2].ptr, mp.ptr if mp else None, nr)
-        else:
-            rv, keep = rig["struct"], [rig]
-    return (tf, tab, fv, rv), a, keep
+    rig_of, mcs_rig_view, in host or device memory -> (structs, arrays by name, keepalive, the memory)"""
+    from ._capi import PointTable, TrackedFrame
+    mem = _DEVICE if device else _HOST
+    a = dict(tkeys=Ft.mvKeys, tdesc=np.asarray(Ft.all_descriptors(), np.uint8), tmask=np.asarray(Ft.all_masks(), np.uint8) if havingMasks else None,
+             tcam=np.asarray(Ft.keypoint_to_cam, np.int32), tpoints=_point_ids(Ft.mvpMapPoints),
+             toutlier=np.asarray(getattr(Ft, "mvbOutlier", np.zeros(Ft.totalN)), np.uint8), pos=np.asarray(points["pos"], np.float64),
+             flags=np.asarray(points["flags"], np.uint8))
+    a = {k: mem.put(v) for k, v in a.items()}
+    tf = TrackedFrame(*[mem.ptr(a[k]) for k in ("tkeys", "tdesc", "tmask", "tcam", "tpoints", "toutlier")], Ft.totalN, featDim)
+    tab = PointTable(mem.ptr(a["pos"]), mem.ptr(a["flags"]), len(points["flags"]))
+    fv, fa = _frame_view(Fs, featDim, havingMasks, np.array([m is not None for m in Fs.mvpMapPoints] or [0], np.uint8), mem)
+    a.update(fa)
+    rv, keep = _rig_view(rig_of, mem) if rig_of is not None else (None, [])
+    return (tf, tab, fv, rv), a, keep, mem
 
 
-def _track_outputs(n, device, entry_points=None):
-    put = (lambda a: DeviceArray(a)) if device else (lambda a: a)
-    return dict(match=put(np.full(max(n, 1), -1, np.int32)), points=put(np.full(max(n, 1), -1, np.int32) if entry_points is None else entry_points),
-                nm=put(np.zeros(1, np.int32)))
+def _track_outputs(n, mem, entry_points=None):
+    return dict(match=mem.put(np.full(max(n, 1), -1, np.int32)), points=mem.put(np.full(max(n, 1), -1, np.int32) if entry_points is None else entry_points),
+                nm=mem.put(np.zeros(1, np.int32)))
 
 
 def TrackWithMotionModelSearch(Cur, Last, points, th, featDim=32, havingMasks=False, checkOrientation=False, device=False, ctx=None):
@@ -1665,18 +1647,16 @@ def TrackWithMotionModelSearch(Cur, Last, points, th, featDim=32, havingMasks=Fa
     points: the per-id tables pos [n][3] and flags [n] (LP_BAD).  Cur.mvpMapPoints receives the ids of the new matches.
     -> dict(nmatches, match_cur, cur_points, assigned)"""
     ctx = ctx or default_context()
-    (tf, tab, fv, rv), a, keep = _tracked_call(Cur, Last, points, featDim, havingMasks, device, Cur.camSystem)
+    (tf, tab, fv, rv), a, keep, mem = _tracked_call(Cur, Last, points, featDim, havingMasks, device, Cur.camSystem)
     n = Cur.totalN
-    o = _track_outputs(n, device, np.resize(_point_ids(Cur.mvpMapPoints), max(n, 1)).astype(np.int32))
-    ptr = (lambda x: x.ptr) if device else np_ptr
-    check(lib().mcs_search_last_frame(ctx.h, C.byref(tf), C.byref(tab), C.byref(rv), C.byref(fv), float(th), featDim, int(bool(checkOrientation)),
-                                      MEM_DEVICE if device else MEM_HOST, ptr(o["match"]), ptr(o["points"]), ptr(o["nm"])))
+    o = _track_outputs(n, mem, np.resize(_point_ids(Cur.mvpMapPoints), max(n, 1)).astype(np.int32))
+    check(lib().mcs_search_last_frame(ctx.h, C.byref(tf), C.byref(tab), C.byref(rv), C.byref(fv), float(th), featDim, int(bool(checkOrientation)), mem.kind,
+                                      mem.ptr(o["match"]), mem.ptr(o["points"]), mem.ptr(o["nm"])))
     # ---- only now the host looks at anything
-    rd = (lambda x: x.read()) if device else (lambda x: x)
-    match, cp, asg = rd(o["match"])[:n], rd(o["points"])[:n], rd(a["assigned"])[:n]
+    match, cp, asg = mem.read(o["match"])[:n], mem.read(o["points"])[:n], mem.read(a["assigned"])[:n]
     for j in np.flatnonzero(match >= 0):
         Cur.mvpMapPoints[int(j)] = int(cp[j])          # CurrentFrame.mvpMapPoints[bestIdx2] = pMP, :2075
-    return dict(nmatches=int(rd(o["nm"])[0]), match_cur=match, cur_points=cp, assigned=asg)
+    return dict(nmatches=int(mem.read(o["nm"])[0]), match_cur=match, cur_points=cp, assigned=asg)
 
 
 def TrackPreviousFrameWindowSearch(Last, Cur, points, windowSize, minScaleLevel=0, maxScaleLevel=2**31 - 1, nnratio=0.8, featDim=32, havingMasks=False,
@@ -1686,14 +1666,12 @@ def TrackPreviousFrameWindowSearch(Last, Cur, points, windowSize, minScaleLevel=
     matches and Last.mvbOutlier are not read, as in the reference).  Cur.mvpMapPoints becomes vpMapPointMatches2 (ids, None where unmatched), which is what
     TrackPreviousFrame assigns (src/cTracking.cpp:751).  -> dict(nmatches, match21, points2)"""
     ctx = ctx or default_context()
-    (tf, tab, fv, rv), a, keep = _tracked_call(Cur, Last, points, featDim, havingMasks, device)
+    (tf, tab, fv, rv), a, keep, mem = _tracked_call(Cur, Last, points, featDim, havingMasks, device)
     n = Cur.totalN
-    o = _track_outputs(n, device)
-    ptr = (lambda x: x.ptr) if device else np_ptr
+    o = _track_outputs(n, mem)
     check(lib().mcs_window_search_frames(ctx.h, C.byref(tf), C.byref(tab), C.byref(fv), int(windowSize), int(minScaleLevel), int(min(maxScaleLevel, 2**31 - 1)),
-                                         float(nnratio), featDim, int(bool(checkOrientation)), MEM_DEVICE if device else MEM_HOST, ptr(o["match"]), ptr(o["points"]),
-                                         ptr(o["nm"])))
-    rd = (lambda x: x.read()) if device else (lambda x: x)
-    match, p2 = rd(o["match"])[:n], rd(o["points"])[:n]
+                                         float(nnratio), featDim, int(bool(checkOrientation)), mem.kind, mem.ptr(o["match"]), mem.ptr(o["points"]),
+                                         mem.ptr(o["nm"])))
+    match, p2 = mem.read(o["match"])[:n], mem.read(o["points"])[:n]
     Cur.mvpMapPoints = [int(p) if p >= 0 else None for p in p2]
-    return dict(nmatches=int(rd(o["nm"])[0]), match21=match, points2=p2)
+    return dict(nmatches=int(mem.read(o["nm"])[0]), match21=match, points2=p2)
