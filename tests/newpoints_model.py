@@ -35,6 +35,7 @@ class KF:
         self.has_mp = np.ascontiguousarray(has_mp, bool)
         self.mp_pos = np.ascontiguousarray(mp_pos, np.float64)   # [n, 3]; rows of features without a map point are not read
         self.n, self.nr = len(keys), len(cams)
+        self.mp = None   # optional explicit (mp_pos [n_mp, 3], mp_cam [n_mp]): the map points behind the median depth, independent of the features
 
     def camera_center(self):   # GetCameraCenter = Hom2T(M_t), src/cMultiKeyFrame.cpp:156-162
         return self.M_t[:3, 3].copy()
@@ -124,10 +125,13 @@ def triangulate_matches(kf1, kf2, match12, cosThresh=COS_THRESH, maxDIST=MAX_DIS
     """the loop body src/cLocalMapping.cpp:269-361 for given matches -> dict(verdict [n1], x3D [n1, 3], idx1, idx2, acc_x3D, near [n1])"""
     n1 = kf1.n
     verdict, x3D, near = np.zeros(n1, np.int32), np.zeros((n1, 3)), np.zeros(n1, bool)
+    near_proj = np.zeros(n1, bool)   # the part of `near` that a libm call or z <= 0 stands behind: both reprojection errors and both depths
+    cosP, d1, d2 = np.full(n1, np.nan), np.full(n1, np.nan), np.full(n1, np.nan)   # per matched row, whatever its verdict; NaN where there is no match
     match12 = np.asarray(match12, np.int32)
     if skipped:
         verdict[:] = SKIPPED
-        return dict(verdict=verdict, x3D=x3D, idx1=np.zeros(0, np.int32), idx2=np.zeros(0, np.int32), acc_x3D=np.zeros((0, 3)), near=near)
+        return dict(verdict=verdict, x3D=x3D, idx1=np.zeros(0, np.int32), idx2=np.zeros(0, np.int32), acc_x3D=np.zeros((0, 3)), near=near, near_proj=near_proj,
+                    cosParallax=cosP, dist1=d1, dist2=d2)
     idx1 = np.flatnonzero(match12 >= 0)                                  # ascending idx1: src/cORBmatcher.cpp:1140-1152
     idx2 = match12[idx1]
     m = len(idx1)
@@ -155,23 +159,24 @@ def triangulate_matches(kf1, kf2, match12, cosThresh=COS_THRESH, maxDIST=MAX_DIS
         alive = v < 0
         uv1, z1 = project(kf1, xw, c1)                                   # :323
         v[alive & (z1 <= 0.0)] = BEHIND_1                                # :324-325
-        nr |= alive & _near(z1, 0.0)
+        nrp = alive & _near(z1, 0.0)
         alive = v < 0
         errX1 = uv1[:, 0] - kf1.keys["x"][idx1].astype(np.float64)       # :327-328
         errY1 = uv1[:, 1] - kf1.keys["y"][idx1].astype(np.float64)
         e1 = np.sqrt(errX1 * errX1 + errY1 * errY1)
         v[alive & (e1 > 4.0)] = REPROJ_1                                 # :329-330
-        nr |= alive & _near(e1, 4.0)
+        nrp |= alive & _near(e1, 4.0)
         alive = v < 0
         uv2, z2 = project(kf2, xw, c2)                                   # :337
         v[alive & (z2 <= 0.0)] = BEHIND_2                                # :338-339
-        nr |= alive & _near(z2, 0.0)
+        nrp |= alive & _near(z2, 0.0)
         alive = v < 0
         errX2 = uv2[:, 0] - kf2.keys["x"][idx2].astype(np.float64)       # :341-342
         errY2 = uv2[:, 1] - kf2.keys["y"][idx2].astype(np.float64)
         e2 = np.sqrt(errX2 * errX2 + errY2 * errY2)
         v[alive & (e2 > 4.0)] = REPROJ_2                                 # :343-344
-        nr |= alive & _near(e2, 4.0)
+        nrp |= alive & _near(e2, 4.0)
+        nr |= nrp
         alive = v < 0
         dist1 = norm(xw - kf1.camera_center()[None])                     # :347-348
         dist2 = norm(xw - kf2.camera_center()[None])                     # :350-351
@@ -180,26 +185,42 @@ def triangulate_matches(kf1, kf2, match12, cosThresh=COS_THRESH, maxDIST=MAX_DIS
         v[v < 0] = ACCEPTED
     verdict[idx1] = v
     near[idx1] = nr
+    near_proj[idx1] = nrp
+    cosP[idx1], d1[idx1], d2[idx1] = cosParallax, dist1, dist2
     tri = v != PARALLAX
     x3D[idx1[tri]] = xw[tri]
     acc = v == ACCEPTED
-    return dict(verdict=verdict, x3D=x3D, idx1=idx1[acc].astype(np.int32), idx2=idx2[acc].astype(np.int32), acc_x3D=xw[acc], near=near)
+    return dict(verdict=verdict, x3D=x3D, idx1=idx1[acc].astype(np.int32), idx2=idx2[acc].astype(np.int32), acc_x3D=xw[acc], near=near, near_proj=near_proj,
+                cosParallax=cosP, dist1=d1, dist2=d2)
 
 
-def scene_median_depth(kf, q=2):
-    """double cMultiKeyFrame::ComputeSceneMedianDepth(int q) (src/cMultiKeyFrame.cpp:747-778)"""
+def map_points(kf, mp=None):
+    """-> (mp_pos [n_mp, 3], mp_cam [n_mp]): the explicit arrays (the argument, else kf.mp), else those of the features that hold a map point"""
+    mp = kf.mp if mp is None else mp
+    if mp is not None:
+        return np.ascontiguousarray(mp[0], np.float64).reshape(-1, 3), np.ascontiguousarray(mp[1], np.int32)
     idx = np.flatnonzero(kf.has_mp)
-    x4 = np.concatenate([kf.mp_pos[idx], np.ones((len(idx), 1))], axis=1)      # :764-765
-    z = mv(kf.MtMc_inv[kf.cam[idx]], x4)[:, 2]                                  # :767-770
+    return kf.mp_pos[idx], kf.cam[idx]
+
+
+def scene_median_depth(kf, q=2, mp=None):
+    """double cMultiKeyFrame::ComputeSceneMedianDepth(int q) (src/cMultiKeyFrame.cpp:747-778).  Where the reference leaves the answer open, the project's
+    choice: a NaN depth takes the last ranks (np.sort puts it there), and a camera index outside the rig gives a NaN depth"""
+    pos, cam = map_points(kf, mp)
+    inside = (cam >= 0) & (cam < kf.nr)
+    x4 = np.concatenate([pos, np.ones((len(pos), 1))], axis=1)                  # :764-765
+    with np.errstate(all="ignore"):
+        z = mv(kf.MtMc_inv[np.where(inside, cam, 0)], x4)[:, 2]                 # :767-770
+    z[~inside] = np.nan
     z = np.sort(z)                                                              # :775
     return float(z[(len(z) - 1) // q])                                          # :777
 
 
-def gate(kf1, kf2):
+def gate(kf1, kf2, mp=None):
     """src/cLocalMapping.cpp:246-254 -> (baseline, median depth, skipped, near)"""
     vBaseline = kf2.camera_center() - kf1.camera_center()
     baseline = float(norm(vBaseline[None])[0])
-    med = scene_median_depth(kf2, 2)
+    med = scene_median_depth(kf2, 2, mp)
     with np.errstate(all="ignore"):
         ratio = np.float64(baseline) / np.float64(med)
     return baseline, med, bool(ratio < 0.01), bool(_near(ratio, 0.01))
@@ -263,23 +284,25 @@ def _flip(rng, d, k):
     return d
 
 
-def make_scene(seed, nr_cams=3, n_points=900, n_neigh=5, clutter=60, noise=0.3, mp_frac=0.15, dim=32, gated=None):
+def make_scene(seed, nr_cams=3, n_points=900, n_neigh=5, clutter=60, noise=0.3, mp_frac=0.15, dim=32, gated=None, cams=None):
     """A 3-D point cloud seen by a rig at known poses: the current keyframe and n_neigh neighbours.  Per keyframe every point is observed by at most one
     camera (keypoint = projection + sub-pixel noise, ray = ImgToWorld of the keypoint, one random descriptor per point with a few flipped bits per view),
     plus unmatched clutter; some features already hold map points (their positions feed the median depth).  Depths 1.5 .. 45 and baselines 0.15 .. 3 put
-    the parallax on both sides of 3 degrees and some points beyond maxDIST; neighbour `gated` has a baseline below 1 % of its median depth; a few
+    the parallax on both sides of 3 degrees and some points beyond maxDIST; neighbour `gated` has a baseline below 1 % of its median depth (a negative
+    `gated`: none has); `cams`: the rig's camera models instead of the LaFiDa calibrations; a few
     neighbours carry pairs built to land behind one of the two cameras, and a few percent of a neighbour's keypoints are displaced by 5 .. 20 px.
     -> (kf1, [neighbours])"""
     rng = np.random.default_rng(seed)
     synth = importlib.import_module("multicol-slam_amd.synth")
-    laf = synth.lafida_cameras()
+    laf = synth.lafida_cameras() if cams is None else cams
     cams = [laf[c % len(laf)] for c in range(nr_cams)]
     M_c = S.rig_poses(nr_cams)
     gated = n_neigh // 2 if gated is None else gated
     Mt1 = _small_pose(rng, 10.0, rng.normal(0, 0.5, 3))
     base = np.exp(np.linspace(math.log(0.15), math.log(3.0), n_neigh))
     rng.shuffle(base)
-    base[gated] = 0.02
+    if gated >= 0:
+        base[gated] = 0.02
     Mts = []
     for s in range(n_neigh):
         d = rng.normal(size=3)

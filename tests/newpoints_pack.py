@@ -34,17 +34,30 @@ class Mem:
         return arr.ctypes.data, (lambda: arr)
 
 
-def geom(pkg, mem, kf, with_mp):
+def ocam(pkg, cam):
+    """mcs_ocam of a camera dict.  Two keys only the hostile cases carry: "invP_pad" fills invP past invP_deg (the library must not read it),
+    "invP_deg" declares a degree other than the number of coefficients given"""
+    o = pkg.make_ocam(cam)
+    if "invP_pad" in cam:
+        for k in range(len(cam["invP"]), pkg._capi.MAX_POLY):
+            o.invP[k] = cam["invP_pad"]
+    if "invP_deg" in cam:
+        o.invP_deg = cam["invP_deg"]
+    return o
+
+
+def geom(pkg, mem, kf, with_mp, mp=None):
+    """mp: explicit (mp_pos [n_mp, 3], mp_cam [n_mp]) instead of the positions / cameras of the features that hold a map point (default: kf.mp)"""
     cap = pkg._capi
-    ocs = (cap.Ocam * kf.nr)(*[pkg.make_ocam(c) for c in kf.cams])
+    ocs = (cap.Ocam * kf.nr)(*[ocam(pkg, c) for c in kf.cams])
     g = cap.KfGeom()
     g.MtMc, g.MtMc_inv, g.M_t = mem.p(kf.MtMc.reshape(-1)), mem.p(kf.MtMc_inv.reshape(-1)), mem.p(kf.M_t.reshape(-1))
     g.cams = mem.p(np.frombuffer(ocs, np.uint8).copy())
     g.rays, g.keys, g.cam = mem.p(kf.rays), mem.p(kf.keys), mem.p(kf.cam)
     g.n, g.nr_cams = kf.n, kf.nr
     if with_mp:
-        idx = np.flatnonzero(kf.has_mp)
-        g.mp_pos, g.mp_cam, g.n_mp = mem.p(kf.mp_pos[idx]), mem.p(kf.cam[idx]), len(idx)
+        pos, cam = M.map_points(kf, mp)
+        g.mp_pos, g.mp_cam, g.n_mp = mem.p(pos), mem.p(cam), len(cam)
     return g
 
 
@@ -66,7 +79,7 @@ class Outputs:
 
     def read(self):
         ns, n1 = self.nsets, self.n1
-        r = {k: f() for k, f in self.rd.items()}
+        r = self.raw = {k: f() for k, f in self.rd.items()}   # the whole arrays, sentinels included
         out = []
         for s in range(ns):
             k = int(r["acc_count"][s])
@@ -76,8 +89,8 @@ class Outputs:
         return out
 
 
-def triangulate(pkg, ctx, G, pairs, matches, device=False, skipped=None, cosThresh=M.COS_THRESH, maxDIST=M.MAX_DIST):
-    """mcs_triangulate_matches over [(kf1, kf2)] pairs with matches [nsets][n1] -> per pair dicts"""
+def triangulate(pkg, ctx, G, pairs, matches, device=False, skipped=None, cosThresh=M.COS_THRESH, maxDIST=M.MAX_DIST, raw=False):
+    """mcs_triangulate_matches over [(kf1, kf2)] pairs with matches [nsets][n1] -> per pair dicts (raw: and the whole output arrays by name)"""
     cap = pkg._capi
     mem = Mem(G, device)
     ns, n1 = len(pairs), pairs[0][0].n
@@ -94,7 +107,8 @@ def triangulate(pkg, ctx, G, pairs, matches, device=False, skipped=None, cosThre
     pkg.check(pkg.lib().mcs_triangulate_matches(ctx.h, ns, g1, g2, m12, sk, cosThresh, maxDIST, int(device), C.byref(outs.o)))
     if device:
         ctx.synchronize()
-    return outs.read()
+    res = outs.read()
+    return (res, outs.raw) if raw else res
 
 
 def chain(pkg, ctx, G, kf1, neigh, device=False, check_ori=False, valid1=None, E=None, K=16, cosThresh=M.COS_THRESH, maxDIST=M.MAX_DIST, expect=0):

@@ -1,7 +1,11 @@
 """-m gpu: mcs_triangulate_matches and mcs_create_new_map_points (cLocalMapping::CreateNewMapPoints, src/cLocalMapping.cpp:223-381) against the
 line-by-line model of tests/newpoints_model.py: match12, verdict codes, accepted lists, final valid1 equal; x3D, baselines and median depths bit for bit
 (their whole chain is + - * / and sqrt on both sides; only the projection reaches a libm call, and no compared quantity of these scenes lies within
-1e-9 of its threshold — asserted on the model, also without a GPU in tests/test_newpoints_cpu.py)."""
+1e-9 of its threshold — asserted on the model, also without a GPU in tests/test_newpoints_cpu.py).
+
+These are well-behaved scenes.  The edge cases are in tests/test_gpu_hostile_newpoints.py (cases: tests/hostile_newpoints.py): tied, NaN and infinite depths at
+every tile size of the median kernel and the gate at exactly 0.01, rigs beyond 256 camera pairs, compaction at the wave and chunk boundaries, comparisons exactly on
+their thresholds, hostile camera models in the projection, entries outside their arrays, a repeated first keyframe and masked descriptors."""
 import importlib
 import os
 import subprocess
