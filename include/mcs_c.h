@@ -385,7 +385,9 @@ int mcs_bow_transform(mcs_vocabulary*, const uint8_t* desc, int n, int stride, i
 /* The BowVector of one frame on the device: the second half of TemplatedVocabulary::transform (TF_IDF branch, ThirdParty/DBoW2/DBoW2/
  * TemplatedVocabulary.h:1147-1163: bow[word] += weight in feature order, words of weight 0 dropped) and BowVector::normalize(L1)
  * (BowVector.cpp: |v| summed in ascending word order, one division per word), bit for bit.
- *   mcs_vocabulary_set_words  word id (-1 for inner nodes) and weight of every node of the flat tree given to mcs_vocabulary_create
+ *   mcs_vocabulary_set_words  word id (-1 for inner nodes) and weight of every node of the flat tree given to mcs_vocabulary_create.  Two nodes of
+ *                             weight > 0 with the same word id are refused (MCS_ERR_INVALID; DBoW2 gives every leaf its own word), and a refused table
+ *                             leaves the previous one in place; nodes of weight 0 may share an id
  *   mcs_bow_vector            leaf_nodes[n] = the leaf_node output of mcs_bow_transform -> word_ids_out[*nwords_out] ascending,
  *                             values_out[*nwords_out]; both outputs must hold n entries.  kind: where leaf_nodes and the outputs live
  *                             (DEVICE: nwords_out too).  Synchronous. */

@@ -62,6 +62,14 @@ int mcs_vocabulary_set_words_internal(mcs_vocabulary* v, const int32_t* word_id_
 		if (!(weight_per_node[i] >= 0.0) || std::isinf(weight_per_node[i])) return fail(MCS_ERR_INVALID, "weights must be finite and >= 0 (TF-IDF)");
 		mx = std::max(mx, (int)word_id_per_node[i]);
 	}
+	// DBoW2 gives every leaf a word id of its own.  k_bow_vector takes a word's ONE weight from whichever node reaches the histogram bin first, so two weighted
+	// nodes of one word would make the value a race.  Nodes of weight 0 never reach the histogram and may share an id.
+	std::vector<int> weighted;
+	for (int i = 0; i < v->nNodes; ++i)
+		if (weight_per_node[i] > 0.0 && word_id_per_node[i] >= 0) weighted.push_back(word_id_per_node[i]);
+	std::sort(weighted.begin(), weighted.end());
+	if (std::adjacent_find(weighted.begin(), weighted.end()) != weighted.end())
+		return fail(MCS_ERR_INVALID, "two nodes with a weight > 0 carry the same word id (every word has one leaf)");
 	HIPCHK(hipSetDevice(v->ctx->device));
 	(void)hipFree(v->wordOf); (void)hipFree(v->weightOf); (void)hipFree(v->hist);
 	v->wordOf = nullptr; v->weightOf = nullptr; v->hist = nullptr; v->nWords = 0;

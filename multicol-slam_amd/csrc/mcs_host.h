@@ -122,6 +122,9 @@ inline int ctx_join_greedy(mcs_ctx* c, hipStream_t s) {
 }
 
 inline int bad_polynomial_degree() { return fail(MCS_ERR_INVALID, "bad polynomial degree"); }   // also the rig check of the window family (mcs_window_guard.hip)
+// a BowVector CSR as the keyframe database takes it (mcs_kfdb_guard.hip): the offsets first, as a whole, then the words they delimit
+int guard_bow_offsets(const int* off, int n, const char* what);
+int guard_bow_words(const int* off, int n, const int* w, int nWords, const char* what);
 // mcs_ocam -> the kernels' camera model (fastOk / tabIdx stay 0: the extractor sets them)
 inline int ocam_to_dev(const mcs_ocam& m, mcs::OcamDev* o) {
 	if (m.p_deg < 1 || m.p_deg > MCS_MAX_POLY || m.invP_deg < 1 || m.invP_deg > MCS_MAX_POLY) return bad_polynomial_degree();

@@ -463,18 +463,6 @@ static int kfdb_sync(mcs_kfdb* db) {
 	return MCS_OK;
 }
 
-// host view of a BowVector CSR (offsets[n+1], words, values) for validation; the word / value arrays stay where they are
-static int check_bow_csr(const std::vector<int>& off, const std::vector<int>& w, int nWords, const char* what) {
-	for (size_t i = 0; i + 1 < off.size(); ++i) {
-		if (off[i + 1] < off[i]) return fail(MCS_ERR_INVALID, std::string(what) + ": offsets must be non-decreasing");
-		for (int k = off[i]; k < off[i + 1]; ++k) {
-			if (w[k] < 0 || w[k] >= nWords) return fail(MCS_ERR_INVALID, std::string(what) + ": word id out of range");
-			if (k > off[i] && w[k - 1] >= w[k]) return fail(MCS_ERR_INVALID, std::string(what) + ": word ids of a BowVector must be strictly ascending");
-		}
-	}
-	return MCS_OK;
-}
-
 int mcs_kfdb_create(mcs_ctx* c, int n_words, int capacity_hint, mcs_kfdb** out) {
 	if (!c || !out) return fail(MCS_ERR_INVALID, "null argument");
 	if (n_words < 1) return fail(MCS_ERR_INVALID, "n_words must be >= 1");
@@ -527,12 +515,11 @@ int mcs_kfdb_add(mcs_kfdb* db, int nkf, const int64_t* kf_ids, const int32_t* of
 	std::vector<int> off, w;
 	HIPCHK(fetch(ids, kf_ids, nkf, kind));
 	HIPCHK(fetch(off, offsets, (size_t)nkf + 1, kind));
-	if (off[0] != 0) return fail(MCS_ERR_INVALID, "offsets[0] must be 0");
+	if (int r = guard_bow_offsets(off.data(), nkf, "mcs_kfdb_add")) return r;   // before anything is sized by them
 	const size_t total = (size_t)off[nkf];
 	if (total && (!word_ids || !values)) return fail(MCS_ERR_INVALID, "null word / value array");
 	HIPCHK(fetch(w, word_ids, total, kind));
-	int rc = check_bow_csr(off, w, db->nWords, "mcs_kfdb_add");
-	if (rc != MCS_OK) return rc;
+	if (int r = guard_bow_words(off.data(), nkf, w.data(), db->nWords, "mcs_kfdb_add")) return r;
 	for (int i = 0; i < nkf; ++i) {
 		auto it = db->slotOf.find(ids[i]);
 		if (it != db->slotOf.end() && db->active[it->second])
@@ -603,18 +590,13 @@ static int kfdb_detect(mcs_kfdb* db, int loop, int nq, const int64_t* query_ids,
 	const bool host = kind == MCS_MEM_HOST;
 	std::vector<int> off;
 	HIPCHK(fetch(off, offsets, (size_t)nq + 1, kind));
-	if (off[0] != 0) return fail(MCS_ERR_INVALID, "offsets[0] must be 0");
-	for (int q = 0; q < nq; ++q)
-		if (off[q + 1] < off[q]) return fail(MCS_ERR_INVALID, "offsets must be non-decreasing");
+	if (int r = guard_bow_offsets(off.data(), nq, nullptr)) return r;
 	const size_t total = (size_t)off[nq];
 	if (total && (!word_ids || !values)) return fail(MCS_ERR_INVALID, "null word / value array");
 	std::vector<int64_t> qid;
 	HIPCHK(fetch(qid, query_ids, nq, kind));
-	if (host) {
-		std::vector<int> w(word_ids, word_ids + total);
-		const int rc = check_bow_csr(off, w, db->nWords, loop ? "mcs_kfdb_detect_loop" : "mcs_kfdb_detect_relocalisation");
-		if (rc != MCS_OK) return rc;
-	}
+	if (host)
+		if (int r = guard_bow_words(off.data(), nq, word_ids, db->nWords, loop ? "mcs_kfdb_detect_loop" : "mcs_kfdb_detect_relocalisation")) return r;
 	int rc = kfdb_sync(db);
 	if (rc != MCS_OK) return rc;
 	const int S = (int)db->id.size();
@@ -759,9 +741,8 @@ int mcs_kfdb_score(mcs_kfdb* db, int nw, const int32_t* word_ids, const double* 
 		slots[i] = it->second;
 	}
 	if (host) {
-		std::vector<int> off{0, nw}, w(word_ids, word_ids + nw);
-		const int rc = check_bow_csr(off, w, db->nWords, "mcs_kfdb_score");
-		if (rc != MCS_OK) return rc;
+		const int off[2] = {0, nw};
+		if (int r = guard_bow_words(off, 1, word_ids, db->nWords, "mcs_kfdb_score")) return r;
 	}
 	int rc = kfdb_sync(db);
 	if (rc != MCS_OK) return rc;
