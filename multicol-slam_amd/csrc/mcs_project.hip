@@ -19,6 +19,11 @@ namespace mcs {
 
 constexpr int kGridCols = 64, kGridRows = 48;   // FRAME_GRID_COLS / ROWS (include/cMultiFrame.h)
 
+// (int)v for an already integral v (floor / ceil / rint) as the reference's build converts it: cvttsd2si / cvtsd2si give INT_MIN for NaN and for anything
+// outside int range, where v_cvt_i32_f64 saturates and turns NaN into 0 (in C++ the conversion is undefined, so it is spelled out).  -2^31 is INT_MIN either
+// way, so one compare does.  A non-finite or huge centre / radius then leaves the window empty, and a keypoint with such a coordinate never enters a cell.
+__device__ __forceinline__ int int_x86(double v) { return fabs(v) < 2147483648.0 ? (int)v : (-2147483647 - 1); }
+
 struct Window { int minCX, maxCX, minCY, maxCY, minLevel, maxLevel; double x, y, rr, wInv, hInv; bool empty; };
 
 __device__ __forceinline__ Window make_window(const ProjArgs& a, int p) {
@@ -37,10 +42,10 @@ __device__ __forceinline__ Window make_window(const ProjArgs& a, int p) {
 	w.wInv = static_cast<double>(kGridCols) / static_cast<double>(a.width[cam] - 0);
 	w.hInv = static_cast<double>(kGridRows) / static_cast<double>(a.height[cam] - 0);
 	w.empty = false;
-	int v = (int)floor((w.x - 0 - w.rr) * w.wInv); v = max(0, v); if (v >= kGridCols) w.empty = true; w.minCX = v;
-	v = (int)ceil((w.x - 0 + w.rr) * w.wInv); v = min(kGridCols - 1, v); if (v < 0) w.empty = true; w.maxCX = v;
-	v = (int)floor((w.y - 0 - w.rr) * w.hInv); v = max(0, v); if (v >= kGridRows) w.empty = true; w.minCY = v;
-	v = (int)ceil((w.y - 0 + w.rr) * w.hInv); v = min(kGridRows - 1, v); if (v < 0) w.empty = true; w.maxCY = v;
+	int v = int_x86(floor((w.x - 0 - w.rr) * w.wInv)); v = max(0, v); if (v >= kGridCols) w.empty = true; w.minCX = v;
+	v = int_x86(ceil((w.x - 0 + w.rr) * w.wInv)); v = min(kGridCols - 1, v); if (v < 0) w.empty = true; w.maxCX = v;
+	v = int_x86(floor((w.y - 0 - w.rr) * w.hInv)); v = max(0, v); if (v >= kGridRows) w.empty = true; w.minCY = v;
+	v = int_x86(ceil((w.y - 0 + w.rr) * w.hInv)); v = min(kGridRows - 1, v); if (v < 0) w.empty = true; w.maxCY = v;
 	return w;
 }
 
@@ -48,7 +53,7 @@ __device__ __forceinline__ Window make_window(const ProjArgs& a, int p) {
 __device__ __forceinline__ unsigned long long member_key(const ProjArgs& a, const Window& w, int cam, int i) {
 	if (a.fcam[i] != cam) return ~0ull;
 	const mcs_keypoint kp = a.keys[i];
-	const int gx = __double2int_rn((kp.x - 0) * w.wInv), gy = __double2int_rn((kp.y - 0) * w.hInv);   // PosInGrid: cvRound
+	const int gx = int_x86(rint((kp.x - 0) * w.wInv)), gy = int_x86(rint((kp.y - 0) * w.hInv));   // PosInGrid: cvRound
 	if (gx < 0 || gx >= kGridCols || gy < 0 || gy >= kGridRows) return ~0ull;                            // never entered a cell
 	if (gx < w.minCX || gx > w.maxCX || gy < w.minCY || gy > w.maxCY) return ~0ull;
 	const bool checkLevels = !(w.minLevel == -1 && w.maxLevel == -1), same = checkLevels && w.minLevel == w.maxLevel;

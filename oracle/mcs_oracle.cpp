@@ -62,6 +62,9 @@ static const signed char kPattern[2048] = {
 // ---- A.0 scalars ----
 inline int cvRound_(double v) { return (int)lrint(v); }      // round-half-even in the default FP env
 inline int cvRoundf_(float v) { return (int)lrintf(v); }
+// cvRound as OpenCV compiles it on x86-64 (_mm_cvtsd_si32): INT_MIN for NaN and for a rounded value outside int range, where the (int)lrint() above keeps
+// the low 32 bits of a long.  PosInGrid bins keypoints with it, and a keypoint coordinate is whatever the caller's frame holds.
+inline int cvRound_x86_(double v) { const double r = nearbyint(v); return (r >= -2147483648.0 && r < 2147483648.0) ? (int)r : INT_MIN; }
 inline int cvFloor_(double v) { int i = (int)v; return i - (i > v); }
 inline int cvCeil_(double v) { int i = (int)v; return i + (i < v); }
 inline short sat_short(float v) { int iv = cvRoundf_(v); return (short)(iv < -32768 ? -32768 : iv > 32767 ? 32767 : iv); }
@@ -1114,8 +1117,8 @@ int orc_pos_in_grid(const orc_ocam* cam, float x, float y, int* gx, int* gy) {  
 	const int FRAME_GRID_ROWS = 48, FRAME_GRID_COLS = 64;
 	double wInv = static_cast<double>(FRAME_GRID_COLS) / static_cast<double>(cam->width - 0);
 	double hInv = static_cast<double>(FRAME_GRID_ROWS) / static_cast<double>(cam->height - 0);
-	*gx = cvRound_((x - 0) * wInv);
-	*gy = cvRound_((y - 0) * hInv);
+	*gx = cvRound_x86_((x - 0) * wInv);
+	*gy = cvRound_x86_((y - 0) * hInv);
 	if (*gx < 0 || *gx >= FRAME_GRID_COLS || *gy < 0 || *gy >= FRAME_GRID_ROWS) return 0;
 	return 1;
 }
@@ -1271,8 +1274,8 @@ int orc_search_by_projection(const double* projx, const double* projy, const dou
 	}
 	for (int i = 0; i < nfeat; ++i) {
 		const int c = fcam[i];
-		const int posX = cvRound_((keys[i].x - 0) * wInv[c]);
-		const int posY = cvRound_((keys[i].y - 0) * hInv[c]);
+		const int posX = cvRound_x86_((keys[i].x - 0) * wInv[c]);
+		const int posY = cvRound_x86_((keys[i].y - 0) * hInv[c]);
 		if (posX < 0 || posX >= FRAME_GRID_COLS || posY < 0 || posY >= FRAME_GRID_ROWS) continue;
 		grids[c][posX][posY].push_back(i);
 	}
@@ -1352,8 +1355,8 @@ struct FrameGrid {   // mGrids + GetFeaturesInArea of one cMultiFrame (src/cMult
 		}
 		for (int i = 0; i < f->n; ++i) {
 			const int c = f->cam[i];
-			const int posX = cvRound_((f->keys[i].x - 0) * wInv[c]);
-			const int posY = cvRound_((f->keys[i].y - 0) * hInv[c]);
+			const int posX = cvRound_x86_((f->keys[i].x - 0) * wInv[c]);
+			const int posY = cvRound_x86_((f->keys[i].y - 0) * hInv[c]);
 			if (posX < 0 || posX >= FRAME_GRID_COLS_ || posY < 0 || posY >= FRAME_GRID_ROWS_) continue;
 			grids[c][posX][posY].push_back(i);
 		}
