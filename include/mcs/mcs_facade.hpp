@@ -25,6 +25,7 @@
 #include <sstream>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -246,7 +247,19 @@ public:
 	std::vector<cCamModelGeneral_> camModels;
 	std::vector<Matx44d> M_c, MtMc, MtMc_inv;
 	Matx44d M_t{};
+	std::vector<std::array<double, 6>> M_c_min;   // Get_M_c_min(c): the calibration's Cayley parameters and translations (LoadMCS fills them)
+	std::array<double, 6> M_t_min{};              // GetPoseMin(): what Set_M_t_from_min was given last
 	int GetNrCams() const { return (int)camModels.size(); }
+	// src/cam_system_omni.cpp:170-183.  MtMc_ / MtMc_inv_ (nrCams x 16 doubles each): the products as a device call built them, instead of building them here.
+	void Set_M_t_from_min(const std::array<double, 6>& M_t_minRep, const double* MtMc_ = nullptr, const double* MtMc_inv_ = nullptr) {
+		M_t_min = M_t_minRep;
+		M_t = Cayley2Hom(M_t_min.data());
+		MtMc.resize(M_c.size()); MtMc_inv.resize(M_c.size());
+		for (size_t c = 0; c < M_c.size(); ++c) {
+			if (MtMc_ && MtMc_inv_) { std::memcpy(MtMc[c].data(), MtMc_ + 16 * c, 128); std::memcpy(MtMc_inv[c].data(), MtMc_inv_ + 16 * c, 128); }
+			else { MtMc[c] = MatMul(M_t, M_c[c]); MtMc_inv[c] = InvMat(MtMc[c]); }
+		}
+	}
 	cCamModelGeneral_& GetCamModelObj(int c) { return camModels[c]; }
 	void Set_M_t(const Matx44d& M) {   // src/cam_system_omni.cpp:184-198
 		M_t = M;
@@ -272,10 +285,12 @@ inline void LoadMCS(const std::string& path2calibrations, cMultiCamSys_& camSyst
 	const int nrCams = SettingI(mcs, "CameraSystem.nrCams");
 	camSystem.camModels.assign(nrCams, {});
 	camSystem.M_c.assign(nrCams, {});
+	camSystem.M_c_min.assign(nrCams, {});
 	for (int c = 0; c < nrCams; ++c) {
 		double cay[6];
 		for (int p = 1; p < 7; ++p) cay[p - 1] = SettingD(mcs, "CameraSystem.cam" + std::to_string(c + 1) + "_" + std::to_string(p));
 		camSystem.M_c[c] = Cayley2Hom(cay);
+		std::copy(cay, cay + 6, camSystem.M_c_min[c].begin());
 		const auto fs = ReadSettings(path2calibrations + "/InteriorOrientationFisheye" + std::to_string(c) + ".yaml");
 		mcs_ocam& o = camSystem.camModels[c].ocam;
 		std::memset(&o, 0, sizeof(o));
@@ -940,7 +955,7 @@ struct FlatFrame {
 // GetDescriptorRowPtr(cam, row) and, with havingMasks, GetDescriptorMaskRowPtr(cam, row).  MP: GetWorldPos(), GetNormal(), GetMinDistanceInvariance(),
 // GetMaxDistanceInvariance(), isBad(), IncreaseVisible(), mnLastFrameSeen, GetDescriptorPtr() / GetDescriptorMaskPtr() and the per-camera fields
 // mbTrackInView, mTrackProjX, mTrackProjY, mnTrackScaleLevel, mTrackViewCos (indexable by camera, at least GetNrCams() entries: include/cMapPoint.h:101-105).
-// UpdateReference, PoseOptimization and the IncreaseFound bookkeeping of TrackLocalMap stay with the caller.
+// UpdateReference and the IncreaseFound bookkeeping of TrackLocalMap stay with the caller; PoseOptimization is cOptimizer::PoseOptimization below.
 template <class FR, class MP>
 int SearchReferencePointsInFrustum(Context& ctx, FR& F, std::vector<MP*>& vpLocalMapPoints, double th = 3.0, double nnratio = 0.8, int descDim = 32,
                                    bool havingMasks = false) {
@@ -1080,6 +1095,74 @@ int WindowSearchFrames(Context& ctx, FR& F1, FR& F2, int windowSize, std::vector
 		if (match21[j] >= 0) vpMapPointMatches2[j] = F1.mvpMapPoints[(size_t)match21[j]];   // :428
 	return nmatches;
 }
+
+// ---------------------------------------------------------------------------------------------- the frame's pose
+// cOptimizer::PoseOptimization (src/cOptimizer.cpp:259-459) over mcs_pose_optimization (host kind), with the reference's signature: pFrame->mvbOutlier is
+// written, the rig's pose is set through Set_M_t_from_min with the products the device built, `inliers` receives nBad / nInitialCorrespondences (the
+// reference's out-parameter IS the outlier share) and nInitialCorrespondences - nBad is returned.  FR: camSystem (M_c_min filled, M_t_min = GetPoseMin()),
+// mvKeys, keypoint_to_cam (find(i)->second), mvpMapPoints (vector of MP*), mvbOutlier, mvInvLevelSigma2.  MP: GetWorldPos(), isBad() (not read by the
+// optimisation, as in the reference).  The batched form takes the frames of several candidates that share the rig model.
+struct cOptimizer {
+	template <class FR, class MP>
+	static std::vector<int> PoseOptimizationBatch(Context& ctx, const std::vector<FR*>& frames, std::vector<double>& inliers, const std::vector<double>& huberMultiplier,
+	                                              std::vector<mcs_pose_diag>* diag = nullptr) {
+		const size_t np = frames.size();
+		std::vector<int> ret(np, 0);
+		inliers.assign(np, 0.0);
+		if (np == 0) return ret;
+		cMultiCamSys_& cs = frames[0]->camSystem;
+		const size_t nr = (size_t)cs.GetNrCams();
+		if (cs.M_c_min.size() != nr) throw std::runtime_error("PoseOptimization: camSystem.M_c_min is not set");
+		PointIds<MP> ids;
+		std::vector<std::vector<mcs_keypoint>> keys(np);
+		std::vector<std::vector<int32_t>> cam(np), points(np);
+		std::vector<std::vector<uint8_t>> out(np);
+		std::vector<mcs_pose_frame> fr(np);
+		std::vector<uint8_t*> outs(np);
+		std::vector<double> pose(6 * np), McMin(6 * nr), MtMc(np * nr * 16), MtMcInv(np * nr * 16), share(np);
+		std::vector<mcs_ocam> oc;
+		for (size_t c = 0; c < nr; ++c) { oc.push_back(cs.camModels[c].ocam); std::copy(cs.M_c_min[c].begin(), cs.M_c_min[c].end(), McMin.begin() + 6 * c); }
+		for (size_t p = 0; p < np; ++p) {
+			FR& F = *frames[p];
+			const size_t n = F.mvpMapPoints.size();
+			keys[p].resize(n); cam[p].resize(n); out[p].assign(std::max<size_t>(n, 1), 0);
+			for (size_t i = 0; i < n; ++i) {
+				static_assert(sizeof(F.mvKeys[0]) == sizeof(mcs_keypoint), "mvKeys must hold cv::KeyPoint-layout records");
+				std::memcpy(&keys[p][i], &F.mvKeys[i], sizeof(mcs_keypoint));
+				cam[p][i] = (int32_t)F.keypoint_to_cam.find(i)->second;
+			}
+			points[p] = ids.of(F.mvpMapPoints);
+			fr[p] = mcs_pose_frame{keys[p].data(), cam[p].data(), points[p].data(), (int32_t)n};
+			outs[p] = out[p].data();
+			std::copy(F.camSystem.M_t_min.begin(), F.camSystem.M_t_min.end(), pose.begin() + 6 * p);
+		}
+		const mcs_point_table tab = ids.table();
+		const std::vector<double>& sigma = frames[0]->mvInvLevelSigma2;
+		std::vector<double> huber(huberMultiplier);
+		huber.resize(np, huber.empty() ? 1.0 : huber.back());
+		std::vector<int32_t> nin(np);
+		if (diag) diag->assign(np, mcs_pose_diag{});
+		mcs_throw(mcs_pose_optimization(ctx.h, (int)np, fr.data(), &tab, McMin.data(), oc.data(), (int)nr, sigma.data(), (int)sigma.size(), huber.data(), MCS_MEM_HOST,
+		                                pose.data(), MtMc.data(), MtMcInv.data(), outs.data(), nin.data(), share.data(), diag ? diag->data() : nullptr));
+		for (size_t p = 0; p < np; ++p) {
+			FR& F = *frames[p];
+			for (size_t i = 0; i < F.mvpMapPoints.size(); ++i) F.mvbOutlier[i] = out[p][i] != 0;
+			std::array<double, 6> m;
+			std::copy(pose.begin() + 6 * p, pose.begin() + 6 * p + 6, m.begin());
+			F.camSystem.Set_M_t_from_min(m, &MtMc[p * nr * 16], &MtMcInv[p * nr * 16]);   // :452
+			inliers[p] = share[p];
+			ret[p] = nin[p];
+		}
+		return ret;
+	}
+	template <class FR, class MP = typename std::remove_pointer<typename decltype(FR::mvpMapPoints)::value_type>::type>
+	static int PoseOptimization(Context& ctx, FR* pFrame, double& inliers, const double& huberMultiplier = 1.0) {
+		std::vector<double> share;
+		const std::vector<int> r = PoseOptimizationBatch<FR, MP>(ctx, std::vector<FR*>{pFrame}, share, std::vector<double>{huberMultiplier});
+		inliers = share[0];
+		return r[0];
+	}
+};
 
 // ---------------------------------------------------------------------------------------------- the local map and the covisibility counts
 // cTracking::UpdateReferenceKeyFrames / UpdateReferencePoints (src/cTracking.cpp:1024-1123) and the counting and ordering of cMultiKeyFrame::UpdateConnections

@@ -37,7 +37,7 @@ extern "C" {
  * 9: the keyframe database mcs_kfdb_*, mcs_vocabulary_set_words, mcs_bow_vector; 10: the Sim3 RANSAC mcs_sim3_*).  Purely additive
  * entry points leave it alone: mcs_triangulate_matches / mcs_create_new_map_points and mcs_frustum / mcs_search_local_points arrived within revision 10, as did the
  * covisibility store mcs_covis_* with mcs_gather_rows / mcs_scatter_rows and its culling calls mcs_covis_set_keyframe_octaves / _cull_keyframes / _observations / _cull_points
- * (look them up with dlsym).  mcs_abi_version() returns the value the LIBRARY was built with: compare it with MCS_ABI_VERSION after dlopen. */
+ * and mcs_pose_optimization (look them up with dlsym).  mcs_abi_version() returns the value the LIBRARY was built with: compare it with MCS_ABI_VERSION after dlopen. */
 #define MCS_ABI_VERSION 10
 
 #define MCS_MAX_POLY 16
@@ -612,6 +612,38 @@ int mcs_search_last_frame(mcs_ctx*, const mcs_tracked_frame* last, const mcs_poi
 int mcs_window_search_frames(mcs_ctx*, const mcs_tracked_frame* f1, const mcs_point_table* pts, const mcs_frame_view* f2, int window_size,
                              int min_level, int max_level, double nnratio, int dim, int check_orientation, mcs_mem_kind kind,
                              int32_t* match21 /* [f2->n] */, int32_t* points2 /* optional, [f2->n], out */, int32_t* nmatches);
+
+/* ------------------------------------------------------------------ the frame's pose, optimised on the device
+ *   int cOptimizer::PoseOptimization(cMultiFrame* pFrame, double& inliers, const double& huberMultiplier)   (src/cOptimizer.cpp:259-459), the step behind every
+ *       search of cTracking (src/cTracking.cpp:753, 775, 816, 848) and, once per surviving candidate, of Relocalisation (:1283)
+ * for a BATCH of independent problems (relocalisation candidates, several frames of a stream) over one rig and one point table, one workgroup per problem, both
+ * rounds of the reference's g2o run in one launch.  DESIGN.md 4l restates the algorithm (Levenberg-Marquardt over the 6 numbers of GetPoseMin(), Huber kernel,
+ * the terminate action with gain 1e-6, the two outlier passes) and section 7 lists what is reproduced rather than repaired.
+ *   frames[p]          keys / cam / points[n] of problem p as in mcs_tracked_frame: an edge for every feature with points[i] >= 0 — isBad() is never read (the
+ *                      table's flags are not an argument), and a point held at two features gives two edges.  cur_points of mcs_search_last_frame feeds points.
+ *   M_c_min            Get_M_c_min(c), [nr_cams][6]: 3 Cayley parameters, 3 translations.  inv_level_sigma2[nlevels] = mvInvLevelSigma2.
+ *   huber_multiplier   [nproblems]; delta = 1.345 * huber_multiplier[p].
+ *   pose_min           [nproblems][6], in: GetPoseMin(), out: the optimised pose.  MtMc / MtMc_inv (optional, [nproblems][nr_cams][16]): what Set_M_t_from_min
+ *                      (src/cam_system_omni.cpp:170-183) builds from it, in the layout mcs_rig_view reads.
+ *   outlier[p]         [frames[p].n], fully written: mvbOutlier.  n_inliers[p] = the return value (nInitialCorrespondences - nBad); outlier_share[p] = the
+ *                      `inliers` out-parameter, which is nBad / nInitialCorrespondences.  The table `outlier` itself is a host array for either kind.
+ *   diag               optional, [nproblems].  stop[r]: why round r ended — 0 its 10 iterations ran, 1 the terminate action set the stop flag, 2 solve() returned
+ *                      Terminate (10 trials or rho == 0), 3 Terminate by its nBad >= 3 rule, 4 the round did not run (the stop flag is never cleared, or no active
+ *                      edge).  trials[r][i] = Levenberg trials of iteration i; lambda = the final _currentLambda; chi2 = the terminate action's last chi2.
+ * A problem without correspondence is not optimised: pose unchanged, count 0, share 0, status 0.  A problem whose first evaluation holds a non-finite residual
+ * or Jacobian entry is not optimised either: status MCS_POSE_NONFINITE, pose unchanged, flags 0, count nInitialCorrespondences (a status, not an error, for
+ * either kind).  Guards: a point id >= table->n, a camera outside [0, nr_cams) or an octave outside [0, nlevels) is refused with MCS_ERR_INVALID in host kind
+ * before anything runs; in device kind that feature contributes no edge.  Features per problem <= 65536, nr_cams <= 32.  nproblems = 0 is a successful no-op.
+ * DEVICE: the call only enqueues on the context's stream — no host wait, no count read back; it needs no scratch.  HOST: through the staging block.  A problem's
+ * result does not depend on nproblems, on its place in the batch or on the run (sums over the edges run in a fixed order, without floating-point atomics).
+ * Refused with MCS_ERR_UNSUPPORTED while deferred searches are on (mcs_ctx_set_async_search). */
+#define MCS_POSE_OK 0
+#define MCS_POSE_NONFINITE 1
+typedef struct { const mcs_keypoint* keys; const int32_t* cam; const int32_t* points; int32_t n; } mcs_pose_frame;
+typedef struct { int32_t status, iters[2], stop[2]; int32_t trials[2][10]; int32_t pad; double lambda, chi2; } mcs_pose_diag;
+int mcs_pose_optimization(mcs_ctx*, int nproblems, const mcs_pose_frame* frames, const mcs_point_table* pts, const double* M_c_min, const mcs_ocam* cams,
+                          int nr_cams, const double* inv_level_sigma2, int nlevels, const double* huber_multiplier, mcs_mem_kind kind, double* pose_min,
+                          double* MtMc, double* MtMc_inv, uint8_t* const* outlier, int32_t* n_inliers, double* outlier_share, mcs_pose_diag* diag);
 
 /* ------------------------------------------------------------------ the local map and the covisibility counts on the device
  * cTracking::UpdateReferenceKeyFrames + UpdateReferencePoints (src/cTracking.cpp:1024-1123), the first step of TrackLocalMap, and the counting and ordering of

@@ -78,7 +78,7 @@ EXPORTS = [
     "mcs_sim3_hypotheses", "mcs_sim3_draw",
     "mcs_triangulate_matches", "mcs_create_new_map_points",
     "mcs_frustum", "mcs_search_local_points",
-    "mcs_search_last_frame", "mcs_window_search_frames",
+    "mcs_search_last_frame", "mcs_window_search_frames", "mcs_pose_optimization",
     "mcs_covis_create", "mcs_covis_destroy", "mcs_covis_clear", "mcs_covis_size", "mcs_covis_slots", "mcs_covis_set_keyframe", "mcs_covis_set_keyframe_pose",
     "mcs_covis_erase_keyframe", "mcs_covis_set_keyframe_bad", "mcs_covis_set_points_bad", "mcs_covis_update_reference", "mcs_covis_update_connections",
     "mcs_gather_rows", "mcs_scatter_rows",
@@ -147,6 +147,19 @@ class TrackedFrame(C.Structure):   # mcs_tracked_frame: the frame whose map poin
 
 class PointTable(C.Structure):   # mcs_point_table: GetWorldPos() and isBad() (LP_BAD) per map point id
     _fields_ = [("pos", C.c_void_p), ("flags", C.c_void_p), ("n", C.c_int32)]
+
+
+class PoseFrame(C.Structure):   # mcs_pose_frame: one problem of mcs_pose_optimization
+    _fields_ = [("keys", C.c_void_p), ("cam", C.c_void_p), ("points", C.c_void_p), ("n", C.c_int32)]
+
+
+class PoseDiag(C.Structure):   # mcs_pose_diag
+    _fields_ = [("status", C.c_int32), ("iters", C.c_int32 * 2), ("stop", C.c_int32 * 2), ("trials", (C.c_int32 * 10) * 2), ("pad", C.c_int32),
+                ("lam", C.c_double), ("chi2", C.c_double)]
+
+
+POSE_DIAG_DTYPE = np.dtype([("status", "<i4"), ("iters", "<i4", 2), ("stop", "<i4", 2), ("trials", "<i4", (2, 10)), ("pad", "<i4"), ("lam", "<f8"), ("chi2", "<f8")])
+POSE_OK, POSE_NONFINITE = 0, 1   # MCS_POSE_* of include/mcs_c.h
 
 
 _lib = None
@@ -254,6 +267,8 @@ def lib():
                                         C.c_int, vp, vp, vp]
     L.mcs_window_search_frames.argtypes = [vp, C.POINTER(TrackedFrame), C.POINTER(PointTable), C.POINTER(FrameView), C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
                                            C.c_int, C.c_int, vp, vp, vp]
+    L.mcs_pose_optimization.argtypes = [vp, C.c_int, C.POINTER(PoseFrame), C.POINTER(PointTable), vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp,
+                                        C.POINTER(vp), vp, vp, vp]
     L.mcs_covis_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
     L.mcs_covis_destroy.argtypes = [vp]
     L.mcs_covis_clear.argtypes = [vp]

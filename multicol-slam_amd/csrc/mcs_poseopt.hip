@@ -1,0 +1,488 @@
+// mcs_poseopt.hip — cOptimizer::PoseOptimization (src/cOptimizer.cpp:259-459) for a batch of independent problems: one workgroup per problem, both rounds of the
+// reference's g2o run in one launch, and the entry point mcs_pose_optimization (include/mcs_c.h).  DESIGN.md 4l; the statement-by-statement restatement the
+// kernel is held to is tests/poseopt_model.py.
+//
+// The edges (features with a map point) are strided over the threads: thread t owns features t, t + kPoseThreads, ... in every pass, and sums them in ascending
+// order.  A pass reduces within a wave by shuffles, then across the waves through LDS in wave order, so a problem's sums do not depend on the batch or the run.
+// Lane 0 keeps the Levenberg-Marquardt state, factorises the 6x6 and broadcasts the step and every decision through LDS; control flow is uniform.
+//
+// No edge keeps its error between passes: the terminate action recomputes the active errors before it reads them (sparse_optimizer_terminate_action.cpp:29),
+// after every iteration, so whatever reads an edge's error — the gain test, both outlier passes — reads the error of the CURRENT estimate, and a pass at that
+// estimate gives it again.  The one per-edge state is its level, which is the outlier flag of the first pass.
+//
+// The Jacobian is derived here by the chain rule (the reference's is generated code and is not used in any form): with Mct = Mt * Mc the camera-frame point is
+// p = Rc^T Rt^T (X - t) - Rc^T tc, so dp/dt = -(Rt Rc)^T and dp/dc_i = Rc^T (dRt/dc_i)^T (X - t); d(u, v)/dp differentiates WorldToImg; e = z - (u, v).
+#include "mcs_poseopt.h"
+#include <cfloat>
+
+using namespace mcs;
+
+namespace {
+
+constexpr int kWaves = kPoseThreads / 64;
+constexpr int kSums = 28;   // 21 of H (upper triangle, row-major), 6 of b, 1 of the robust chi2
+enum { STOP_ITERATIONS = 0, STOP_GAIN = 1, STOP_TRIALS = 2, STOP_NBAD = 3, STOP_NOT_RUN = 4 };
+
+struct PoseShared {
+	OcamDev cam[32];
+	double dInvP[32][MCS_MAX_POLY];   // coefficients of d rho / d theta
+	double McH[32][16];               // cayley2hom(M_c_min[c])
+	double inv[32][16];               // invMat(Mt * Mc[c]) at the current estimate
+	double A[32][3][9];               // Rc^T (dRt/dc_i)^T, build passes only
+	double red[kWaves][kSums];
+	double tot[kSums];
+	double H[21], b[6];               // of the iteration's build pass (lane 0 reads them in every trial)
+	double pose[6], backup[6], x[6];
+	int nInit, nonfinite, nBad, go, cont;
+};
+
+// include/misc.h:133-160
+__device__ void cayley2rot_dev(const double* c, double* R) {
+	const double c1 = c[0], c2 = c[1], c3 = c[2];
+	const double c1s = c1 * c1, c2s = c2 * c2, c3s = c3 * c3;
+	const double scale = 1.0 + c1s + c2s + c3s;
+	R[0] = 1 + c1s - c2s - c3s; R[1] = 2 * (c1 * c2 - c3);   R[2] = 2 * (c1 * c3 + c2);
+	R[3] = 2 * (c1 * c2 + c3);  R[4] = 1 - c1s + c2s - c3s;  R[5] = 2 * (c2 * c3 - c1);
+	R[6] = 2 * (c1 * c3 - c2);  R[7] = 2 * (c2 * c3 + c1);   R[8] = 1 - c1s - c2s + c3s;
+	const double inv = 1 / scale;
+	for (int k = 0; k < 9; ++k) R[k] = inv * R[k];
+}
+// :212-224
+__device__ void cayley2hom_dev(const double* c6, double* M) {
+	double R[9];
+	cayley2rot_dev(c6, R);
+	for (int r = 0; r < 3; ++r) { M[4 * r] = R[3 * r]; M[4 * r + 1] = R[3 * r + 1]; M[4 * r + 2] = R[3 * r + 2]; M[4 * r + 3] = c6[3 + r]; }
+	M[12] = M[13] = M[14] = 0.0; M[15] = 1.0;
+}
+// cv::Matx44d product: s = 0; s += a(i,k) * b(k,j) in increasing k
+__device__ void matx44_mul(const double* A, const double* B, double* C) {
+	for (int i = 0; i < 4; ++i)
+		for (int j = 0; j < 4; ++j) {
+			double s = 0;
+			for (int k = 0; k < 4; ++k) s += A[4 * i + k] * B[4 * k + j];
+			C[4 * i + j] = s;
+		}
+}
+// cConverter::invMat (src/cConverter.cpp:31-44): R^T and -R^T * t
+__device__ void inv_mat_dev(const double* M, double* out) {
+	for (int i = 0; i < 3; ++i) {
+		double s = 0;
+		for (int k = 0; k < 3; ++k) { out[4 * i + k] = M[4 * k + i]; s += (-M[4 * k + i]) * M[4 * k + 3]; }
+		out[4 * i + 3] = s;
+	}
+	out[12] = out[13] = out[14] = 0.0; out[15] = 1.0;
+}
+
+// Mct and its inverse of camera c at `pose` (EdgeProjectXYZ2MCS::computeError, Set_M_t_from_min); Build: also A_i = Rc^T (dRt/dc_i)^T
+template <bool Build>
+__device__ void camera_state(PoseShared& sh, int c, const double* pose, double* MtMcOut) {
+	double Mt[16], Mct[16];
+	cayley2hom_dev(pose, Mt);
+	matx44_mul(Mt, sh.McH[c], Mct);
+	inv_mat_dev(Mct, sh.inv[c]);
+	if (MtMcOut) for (int k = 0; k < 16; ++k) MtMcOut[k] = Mct[k];
+	if (Build) {
+		const double c1 = pose[0], c2 = pose[1], c3 = pose[2];
+		const double s = 1.0 + c1 * c1 + c2 * c2 + c3 * c3;
+		const double dN[3][9] = {{2 * c1, 2 * c2, 2 * c3, 2 * c2, -2 * c1, -2.0, 2 * c3, 2.0, -2 * c1},
+		                         {-2 * c2, 2 * c1, 2.0, 2 * c1, 2 * c2, 2 * c3, -2.0, 2 * c3, -2 * c2},
+		                         {-2 * c3, -2.0, 2 * c1, 2.0, -2 * c3, 2 * c2, 2 * c1, 2 * c2, 2 * c3}};
+		const double* Rc = sh.McH[c];   // rows of 4
+		for (int i = 0; i < 3; ++i) {
+			double dR[9];
+			for (int k = 0; k < 9; ++k) dR[k] = (dN[i][k] - 2.0 * pose[i] * Mt[4 * (k / 3) + k % 3]) / s;
+			for (int r = 0; r < 3; ++r)
+				for (int k = 0; k < 3; ++k) {
+					double a = 0;
+					for (int j = 0; j < 3; ++j) a += Rc[4 * j + r] * dR[3 * k + j];
+					sh.A[c][i][3 * r + k] = a;
+				}
+		}
+	}
+}
+
+__device__ __forceinline__ bool edge_of(const PoseArgs& a, const mcs_keypoint* keys, const int* cam, const int* points, int i, int& pid, int& c, int& oct) {
+	pid = points[i];
+	if (pid < 0 || pid >= a.npoints) return false;
+	c = cam[i]; oct = keys[i].octave;
+	return c >= 0 && c < a.nrCams && oct >= 0 && oct < a.nlevels;
+}
+
+// the camera-frame point of an edge: Matx44 * Vec4 in increasing k
+__device__ __forceinline__ void camera_point(const double* M, const double* X, double* p) {
+	for (int r = 0; r < 3; ++r) {
+		double s = 0;
+		s += M[4 * r] * X[0]; s += M[4 * r + 1] * X[1]; s += M[4 * r + 2] * X[2]; s += M[4 * r + 3] * 1.0;
+		p[r] = s;
+	}
+}
+
+// d(u, v) / d(x, y, z) of omni_world_to_img; the norm == 0 -> 1e-14 branch is a constant
+__device__ void d_world_to_img(const OcamDev& cam, const double* dInvP, double x, double y, double z, double D[2][3]) {
+	const double n0 = sqrt(x * x + y * y);
+	const bool constant = n0 == 0.0;
+	const double n = constant ? 1e-14 : n0;
+	const double dn[3] = {constant ? 0.0 : x / n, constant ? 0.0 : y / n, 0.0};
+	const double q = -z / n;
+	const double theta = atan(q);
+	const double dthdq = 1.0 / (1.0 + q * q);
+	const double rho = horner_fixed(cam.invP, theta), drho_dth = horner_fixed(dInvP, theta);
+	const double fx = x / n, fy = y / n;
+	for (int k = 0; k < 3; ++k) {
+		const double dq = k == 2 ? -1.0 / n : (z / (n * n)) * dn[k];
+		const double drho = drho_dth * (dthdq * dq);
+		const double dfx = -(x / (n * n)) * dn[k] + (k == 0 ? 1.0 / n : 0.0);
+		const double dfy = -(y / (n * n)) * dn[k] + (k == 1 ? 1.0 / n : 0.0);
+		const double duu = dfx * rho + fx * drho, dvv = dfy * rho + fy * drho;
+		D[0][k] = duu * cam.c + dvv * cam.d;
+		D[1][k] = duu * cam.e + dvv;
+	}
+}
+
+__device__ __forceinline__ bool finite_(double v) { return fabs(v) <= DBL_MAX; }
+
+// wave shuffles, then the waves in order: tot[0..N) on every thread after the closing barrier
+template <int N>
+__device__ void reduce_sums(PoseShared& sh, double* acc) {
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+	for (int k = 0; k < N; ++k) {
+		double v = acc[k];
+#pragma unroll
+		for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+		if (lane == 0) sh.red[wave][k] = v;
+	}
+	__syncthreads();
+	if (threadIdx.x < N) {
+		double t = sh.red[0][threadIdx.x];
+		for (int w = 1; w < kWaves; ++w) t += sh.red[w][threadIdx.x];
+		sh.tot[threadIdx.x] = t;
+	}
+	__syncthreads();
+}
+
+struct Edges { const mcs_keypoint* keys; const int* cam; const int* points; uint8_t* outlier; int n; };
+
+// One pass over the active edges at the estimate behind sh.inv (and sh.A): the robust chi2 (activeRobustChi2), Build: also H and b (constructQuadraticForm).
+// levelZero: only edges whose outlier flag is clear (initializeOptimization(0)).
+template <bool Build>
+__device__ void pass(PoseShared& sh, const PoseArgs& a, const Edges& e, bool levelZero, double delta, double dsqr) {
+	double acc[Build ? kSums : 1];
+#pragma unroll
+	for (int k = 0; k < (Build ? kSums : 1); ++k) acc[k] = 0.0;
+	bool bad = false;
+	for (int i = threadIdx.x; i < e.n; i += kPoseThreads) {
+		int pid, c, oct;
+		if (!edge_of(a, e.keys, e.cam, e.points, i, pid, c, oct)) continue;
+		if (levelZero && e.outlier[i]) continue;
+		const double X[3] = {a.pos[3 * (size_t)pid], a.pos[3 * (size_t)pid + 1], a.pos[3 * (size_t)pid + 2]};
+		double p[3], u, v;
+		camera_point(sh.inv[c], X, p);
+		omni_world_to_img(sh.cam[c], p[0], p[1], p[2], u, v);
+		const double e0 = (double)e.keys[i].x - u, e1 = (double)e.keys[i].y - v;
+		const double w = a.invSigma2[oct];
+		const double c2 = e0 * (w * e0) + e1 * (w * e1);   // _error.dot(information() * _error)
+		double rho0, rho1;                                  // RobustKernelHuber::robustify
+		if (c2 <= dsqr) { rho0 = c2; rho1 = 1.0; }
+		else { const double sq = sqrt(c2); rho0 = 2 * sq * delta - dsqr; rho1 = delta / sq; }
+		if constexpr (!Build) { (void)rho1; acc[0] += rho0; }
+		else {
+		double D[2][3], J[2][6];
+		d_world_to_img(sh.cam[c], sh.dInvP[c], p[0], p[1], p[2], D);
+		const double d[3] = {X[0] - sh.pose[3], X[1] - sh.pose[4], X[2] - sh.pose[5]};
+#pragma unroll
+		for (int k = 0; k < 6; ++k) {
+			double dp[3];
+#pragma unroll
+			for (int r = 0; r < 3; ++r)
+				dp[r] = k < 3 ? sh.A[c][k][3 * r] * d[0] + sh.A[c][k][3 * r + 1] * d[1] + sh.A[c][k][3 * r + 2] * d[2] : -sh.inv[c][4 * r + (k - 3)];
+			J[0][k] = -(D[0][0] * dp[0] + D[0][1] * dp[1] + D[0][2] * dp[2]);
+			J[1][k] = -(D[1][0] * dp[0] + D[1][1] * dp[1] + D[1][2] * dp[2]);
+			bad |= !finite_(J[0][k]) || !finite_(J[1][k]);
+		}
+		bad |= !finite_(e0) || !finite_(e1);
+		const double rw = rho1 * w;   // robustInformation = rho[1] * information; no second-order term
+		int s = 0;
+#pragma unroll
+		for (int r = 0; r < 6; ++r)
+#pragma unroll
+			for (int q = r; q < 6; ++q) acc[s++] += rw * (J[0][r] * J[0][q] + J[1][r] * J[1][q]);
+#pragma unroll
+		for (int r = 0; r < 6; ++r) acc[21 + r] += -rw * (J[0][r] * e0 + J[1][r] * e1);
+		acc[27] += rho0;
+		}
+	}
+	if (Build && bad) atomicOr(&sh.nonfinite, 1);
+	reduce_sums<Build ? kSums : 1>(sh, acc);
+}
+
+// :412-427 / :433-447: chi2 > thHuber2 of every edge still at level 0, at the estimate behind sh.inv
+__device__ void outlier_pass(PoseShared& sh, const PoseArgs& a, const Edges& e, double th2) {
+	int nbad = 0;
+	for (int i = threadIdx.x; i < e.n; i += kPoseThreads) {
+		int pid, c, oct;
+		if (!edge_of(a, e.keys, e.cam, e.points, i, pid, c, oct) || e.outlier[i]) continue;
+		const double X[3] = {a.pos[3 * (size_t)pid], a.pos[3 * (size_t)pid + 1], a.pos[3 * (size_t)pid + 2]};
+		double p[3], u, v;
+		camera_point(sh.inv[c], X, p);
+		omni_world_to_img(sh.cam[c], p[0], p[1], p[2], u, v);
+		const double e0 = (double)e.keys[i].x - u, e1 = (double)e.keys[i].y - v;
+		const double w = a.invSigma2[oct];
+		if (e0 * (w * e0) + e1 * (w * e1) > th2) { e.outlier[i] = 1; ++nbad; }
+	}
+	if (nbad) atomicAdd(&sh.nBad, nbad);
+	__syncthreads();
+}
+
+// unpivoted LDL^T of H + lambda I (H: upper triangle, row-major) and the solve; false as soon as a pivot is not > 0 (x is then left alone)
+__device__ __noinline__ bool ldlt6_solve(const double* Hu, double lambda, const double* b, double* x) {
+	double A[6][6], L[6][6], d[6], y[6];
+	int s = 0;
+#pragma unroll
+	for (int r = 0; r < 6; ++r)
+#pragma unroll
+		for (int q = r; q < 6; ++q) { A[r][q] = A[q][r] = Hu[s++]; }
+#pragma unroll
+	for (int r = 0; r < 6; ++r) A[r][r] = A[r][r] + lambda;
+#pragma unroll
+	for (int j = 0; j < 6; ++j) {
+		double t = A[j][j];
+#pragma unroll
+		for (int k = 0; k < j; ++k) t -= L[j][k] * L[j][k] * d[k];
+		if (!(t > 0.0)) return false;
+		d[j] = t;
+#pragma unroll
+		for (int i = j + 1; i < 6; ++i) {
+			double u = A[i][j];
+#pragma unroll
+			for (int k = 0; k < j; ++k) u -= L[i][k] * L[j][k] * d[k];
+			L[i][j] = u / t;
+		}
+	}
+#pragma unroll
+	for (int i = 0; i < 6; ++i) {
+		double t = b[i];
+#pragma unroll
+		for (int k = 0; k < i; ++k) t -= L[i][k] * y[k];
+		y[i] = t;
+	}
+#pragma unroll
+	for (int i = 0; i < 6; ++i) y[i] = y[i] / d[i];
+#pragma unroll
+	for (int i = 5; i >= 0; --i) {
+		double t = y[i];
+#pragma unroll
+		for (int k = i + 1; k < 6; ++k) t -= L[k][i] * x[k];
+		x[i] = t;
+	}
+	return true;
+}
+
+__global__ void __launch_bounds__(kPoseThreads) k_poseopt(PoseArgs a, PoseChunk ch, int first) {
+	__shared__ PoseShared sh;
+	const int tid = threadIdx.x, lp = blockIdx.x, gp = first + lp, nr = a.nrCams;
+	const Edges e{ch.keys[lp], ch.cam[lp], ch.points[lp], ch.outlier[lp], ch.n[lp]};
+	double* const poseOut = a.poseMin + 6 * (size_t)gp;
+
+	if (tid < nr) {
+		const mcs_ocam& m = a.cams[tid];
+		OcamDev& o = sh.cam[tid];
+		o.c = m.c; o.d = m.d; o.e = m.e; o.u0 = m.u0; o.v0 = m.v0; o.invAffine = m.c - m.d * m.e;
+		const int deg = m.invP_deg < 0 ? 0 : m.invP_deg > MCS_MAX_POLY ? MCS_MAX_POLY : m.invP_deg;
+		for (int k = 0; k < MCS_MAX_POLY; ++k) { o.p[k] = 0.0; o.invP[k] = k < deg ? m.invP[k] : 0.0; }
+		for (int k = 0; k < MCS_MAX_POLY; ++k) sh.dInvP[tid][k] = k + 1 < deg ? m.invP[k + 1] * (double)(k + 1) : 0.0;
+		o.p_deg = 0; o.invP_deg = deg; o.fastOk = 0; o.tabIdx = 0;
+		cayley2hom_dev(a.McMin + 6 * tid, sh.McH[tid]);
+	}
+	if (tid == 0) {
+		for (int k = 0; k < 6; ++k) { sh.pose[k] = poseOut[k]; sh.x[k] = 0.0; }
+		sh.nInit = 0; sh.nonfinite = 0; sh.nBad = 0;
+	}
+	int mine = 0;
+	for (int i = tid; i < e.n; i += kPoseThreads) {
+		int pid, c, oct;
+		e.outlier[i] = 0;   // :351
+		mine += edge_of(a, e.keys, e.cam, e.points, i, pid, c, oct) ? 1 : 0;
+	}
+	__syncthreads();
+	if (mine) atomicAdd(&sh.nInit, mine);
+	__syncthreads();
+	const int nInit = sh.nInit;
+
+	const double delta = 1.345 * a.huber[gp], dsqr = delta * delta, th2 = delta * delta;
+	// lane 0's state
+	int status = MCS_POSE_OK, iters[2] = {0, 0}, stop[2] = {STOP_NOT_RUN, STOP_NOT_RUN}, trials[2][10] = {};
+	double lambda = -1.0, ni = 2.0, lastChi = 0.0;
+	bool stopFlag = false;
+
+	if (nInit > 0) {   // uniform
+		for (int rnd = 0; rnd < 2; ++rnd) {
+			const int nAct = nInit - sh.nBad;   // round 1: the edges the first outlier pass left at level 0
+			bool resultOk = true;
+			int it = 0, lmBad = 0, why = stopFlag || nAct == 0 ? STOP_NOT_RUN : STOP_ITERATIONS;
+			if (tid == 0) for (int k = 0; k < 6; ++k) sh.x[k] = 0.0;   // Solver::resize: zeros
+			while (true) {
+				if (tid == 0) sh.go = it < 10 && !stopFlag && resultOk && nAct > 0;
+				__syncthreads();
+				if (!sh.go) break;
+				// ---- OptimizationAlgorithmLevenberg::solve(it)
+				if (tid < nr) camera_state<true>(sh, tid, sh.pose, nullptr);
+				__syncthreads();
+				pass<true>(sh, a, e, rnd == 1, delta, dsqr);
+				if (rnd == 0 && it == 0 && sh.nonfinite) { status = MCS_POSE_NONFINITE; break; }   // uniform: not optimised
+				double currentChi = 0, iniChi = 0, rho = 0, postChi = 0;
+				int qmax = 0;
+				if (tid == 0) {
+					for (int k = 0; k < 21; ++k) sh.H[k] = sh.tot[k];
+					for (int k = 0; k < 6; ++k) sh.b[k] = sh.tot[21 + k];
+					currentChi = iniChi = postChi = sh.tot[27];
+					if (it == 0) {   // computeLambdaInit: tau * max |H_jj|
+						double m = 0.0;
+						int s = 0;
+						for (int r = 0; r < 6; ++r) { m = fmax(fabs(sh.H[s]), m); s += 6 - r; }
+						lambda = 1e-5 * m; ni = 2.0; lmBad = 0;
+					}
+				}
+				while (true) {
+					bool ok2 = true;
+					if (tid == 0) {
+						double x[6];
+						for (int k = 0; k < 6; ++k) { x[k] = sh.x[k]; sh.backup[k] = sh.pose[k]; }   // push
+						ok2 = ldlt6_solve(sh.H, lambda, sh.b, x);
+						for (int k = 0; k < 6; ++k) { sh.x[k] = x[k]; sh.pose[k] = sh.pose[k] + x[k]; }   // oplus, with the stale x after a failed solve
+					}
+					__syncthreads();
+					if (tid < nr) camera_state<false>(sh, tid, sh.pose, nullptr);
+					__syncthreads();
+					pass<false>(sh, a, e, rnd == 1, delta, dsqr);
+					if (tid == 0) {
+						const double rawChi = sh.tot[0];
+						double tempChi = ok2 ? rawChi : DBL_MAX;
+						rho = currentChi - tempChi;
+						double scale = 0.0;
+						for (int j = 0; j < 6; ++j) scale += sh.x[j] * (lambda * sh.x[j] + sh.b[j]);
+						scale += 1e-3;
+						rho /= scale;
+						if (rho > 0 && finite_(tempChi)) {
+							double alpha = 1. - pow(2 * rho - 1, 3.0);
+							alpha = fmin(alpha, 2. / 3.);
+							lambda *= fmax(1. / 3., alpha);
+							ni = 2;
+							currentChi = tempChi;
+							postChi = rawChi;
+						} else {
+							lambda *= ni;
+							ni *= 2;
+							for (int k = 0; k < 6; ++k) sh.pose[k] = sh.backup[k];   // pop
+						}
+						++qmax;
+						sh.cont = rho < 0 && qmax < 10 && !stopFlag;
+					}
+					__syncthreads();
+					if (!sh.cont) break;
+				}
+				if (tid == 0) {
+					trials[rnd][it] = qmax;
+					if (qmax == 10 || rho == 0) { resultOk = false; why = STOP_TRIALS; }
+					else {
+						lmBad = (iniChi - currentChi) * 1e3 < iniChi ? lmBad + 1 : 0;
+						if (lmBad >= 3) { resultOk = false; why = STOP_NBAD; }
+					}
+					// ---- postIteration(it): the terminate action, on the errors of the current estimate (postChi: the chi2 of the pass that evaluated it)
+					if (it == 0) lastChi = postChi;
+					else {
+						const double gain = (lastChi - postChi) / postChi;
+						lastChi = postChi;
+						if (gain >= 0 && gain < 1e-6) { stopFlag = true; if (resultOk) why = STOP_GAIN; }   // never cleared: this g2o has no iteration -1 call
+					}
+				}
+				++it;
+			}
+			if (status != MCS_POSE_OK) break;
+			iters[rnd] = it; stop[rnd] = why;
+			// ---- the outlier pass behind this round, at the current estimate
+			__syncthreads();
+			if (tid < nr) camera_state<false>(sh, tid, sh.pose, nullptr);
+			__syncthreads();
+			outlier_pass(sh, a, e, th2);
+		}
+	}
+	__syncthreads();
+	if (status == MCS_POSE_NONFINITE && tid == 0) for (int k = 0; k < 6; ++k) sh.pose[k] = poseOut[k];   // nothing was applied yet; for the matrices below
+	__syncthreads();
+	// Set_M_t_from_min (src/cam_system_omni.cpp:170-183)
+	if (tid < nr) {
+		double MtMc[16];
+		camera_state<false>(sh, tid, sh.pose, MtMc);
+		const size_t at = ((size_t)gp * nr + tid) * 16;
+		if (a.MtMc) for (int k = 0; k < 16; ++k) a.MtMc[at + k] = MtMc[k];
+		if (a.MtMcInv) for (int k = 0; k < 16; ++k) a.MtMcInv[at + k] = sh.inv[tid][k];
+	}
+	if (tid == 0) {
+		const int nBad = status == MCS_POSE_OK ? sh.nBad : 0;
+		for (int k = 0; k < 6; ++k) poseOut[k] = sh.pose[k];
+		a.nInliers[gp] = nInit - nBad;
+		a.share[gp] = nInit > 0 ? (double)nBad / (double)nInit : 0.0;   // the `inliers` out-parameter (:454-456)
+		if (a.diag) {
+			mcs_pose_diag& g = a.diag[gp];
+			g.status = status; g.pad = 0;
+			for (int r = 0; r < 2; ++r) { g.iters[r] = iters[r]; g.stop[r] = stop[r]; for (int k = 0; k < 10; ++k) g.trials[r][k] = trials[r][k]; }
+			g.lambda = nInit > 0 && status == MCS_POSE_OK ? lambda : 0.0; g.chi2 = status == MCS_POSE_OK ? lastChi : 0.0;
+		}
+	}
+}
+
+}  // namespace
+
+namespace mcs {
+void launch_poseopt(const PoseArgs& a, const PoseChunk& ch, int first, int count, hipStream_t s) {
+	hipLaunchKernelGGL(k_poseopt, dim3(count), dim3(kPoseThreads), 0, s, a, ch, first);
+}
+}  // namespace mcs
+
+// ---------------------------------------------------------------------------------------------- cOptimizer::PoseOptimization
+int mcs_pose_optimization(mcs_ctx* c, int nproblems, const mcs_pose_frame* frames, const mcs_point_table* pts, const double* M_c_min, const mcs_ocam* cams,
+                          int nr_cams, const double* inv_level_sigma2, int nlevels, const double* huber_multiplier, mcs_mem_kind kind, double* pose_min,
+                          double* MtMc, double* MtMc_inv, uint8_t* const* outlier, int32_t* n_inliers, double* outlier_share, mcs_pose_diag* diag) {
+	const PoseCall q{nproblems, frames, pts, M_c_min, cams, nr_cams, inv_level_sigma2, nlevels, huber_multiplier, kind,
+	                 pose_min, MtMc, MtMc_inv, outlier, n_inliers, outlier_share, diag};
+	if (int r = guard_pose(c, q, c && c->asyncSearch)) return r;
+	if (nproblems == 0) return MCS_OK;
+	const bool host = kind == MCS_MEM_HOST;
+	if (host)
+		if (int r = guard_pose_content(q)) return r;
+	HIPCHK(hipSetDevice(c->device));
+	hipStream_t s = c->stream;
+	if (int r = ctx_join_greedy(c, s)) return r;   // the points may come from a search whose greedy pass runs on the side stream
+	const size_t np = nproblems, nr = nr_cams;
+	PoseArgs a{};
+	a.npoints = pts->n; a.nrCams = nr_cams; a.nlevels = nlevels;
+	std::vector<const mcs_keypoint*> keys(np); std::vector<const int*> cam(np), points(np); std::vector<uint8_t*> out(np);
+	Staging st(c, host);
+	st.in(&a.pos, pts->pos, (size_t)pts->n * 24); st.in(&a.McMin, M_c_min, nr * 48); st.in(&a.cams, cams, nr * sizeof(mcs_ocam));
+	st.in(&a.invSigma2, inv_level_sigma2, (size_t)nlevels * 8); st.in(&a.huber, huber_multiplier, np * 8);
+	st.inout(&a.poseMin, pose_min, np * 48);
+	if (MtMc) st.out(&a.MtMc, MtMc, np * nr * 128);
+	if (MtMc_inv) st.out(&a.MtMcInv, MtMc_inv, np * nr * 128);
+	st.out(&a.nInliers, n_inliers, np * 4); st.out(&a.share, outlier_share, np * 8);
+	if (diag) st.out(&a.diag, diag, np * sizeof(mcs_pose_diag));
+	for (size_t p = 0; p < np; ++p) {
+		const size_t n = frames[p].n;
+		st.in(&keys[p], frames[p].keys, n * sizeof(mcs_keypoint)); st.in(&cam[p], frames[p].cam, n * 4); st.in(&points[p], frames[p].points, n * 4);
+		if (n) st.out(&out[p], outlier[p], n); else out[p] = nullptr;
+	}
+	if (int r = st.commit()) return r;
+	c->tic("pose_optimization");
+	for (int first = 0; first < nproblems; first += kPoseBatch) {
+		const int count = std::min(kPoseBatch, nproblems - first);
+		PoseChunk ch{};
+		for (int k = 0; k < count; ++k) {
+			ch.keys[k] = keys[first + k]; ch.cam[k] = cam[first + k]; ch.points[k] = points[first + k]; ch.outlier[k] = out[first + k]; ch.n[k] = frames[first + k].n;
+		}
+		launch_poseopt(a, ch, first, count, s);
+	}
+	c->toc("pose_optimization");
+	c->lastResultStream = s;   // every output is complete on the context's stream
+	HIPCHK(hipGetLastError());
+	return st.finish(MCS_OK);
+}

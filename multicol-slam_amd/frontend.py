@@ -11,6 +11,7 @@
   CreateNewMapPoints                   src/cLocalMapping.cpp:223-381 (the mapping thread's neighbour loop: search, triangulation and checks in one call)
   cMultiFrame.isInFrustum, SearchReferencePointsInFrustum   src/cMultiFrame.cpp:218-270, src/cTracking.cpp:953-1012 (the search step of TrackLocalMap in one call)
   cCovisibility, TrackLocalMapSearch   src/cTracking.cpp:1024-1123, src/cMultiKeyFrame.cpp:406-500 (local map and covisibility counts from a device-resident store)
+  PoseOptimization[Batch]              src/cOptimizer.cpp:259-459 (the frame's pose, both g2o rounds in one call, a batch of frames per call)
 
 Everything numeric runs in libmcs_hip.so on the GPU; this file only shapes inputs/outputs (numpy stands in for cv::Mat).
 """
@@ -81,6 +82,13 @@ def _inv_mat(M):
     return out
 
 
+def _hom2cayley(M):   # include/misc.h:171-202
+    M = np.asarray(M, np.float64)
+    R = M[:3, :3]
+    Cm = (R - np.eye(3)) @ np.linalg.inv(R + np.eye(3))
+    return np.array([-Cm[1, 2], Cm[0, 2], -Cm[0, 1], M[0, 3], M[1, 3], M[2, 3]])
+
+
 class cMultiCamSys_:
     """Calibrations + poses of the rig (include/cam_system_omni.h): M_t = rig pose, M_c[c] = camera c in the rig frame."""
 
@@ -94,6 +102,26 @@ class cMultiCamSys_:
         self.M_t_inv = _inv_mat(self.M_t)
         self.MtMc = [_matx_mul(self.M_t, mc) for mc in self.M_c]
         self.MtMc_inv = [_inv_mat(m) for m in self.MtMc]
+
+    def Get_M_c_min(self, c):   # the calibration's 6-vector where the rig was built from one (M_c_min), else hom2cayley(M_c[c]) (include/misc.h:171-202)
+        if getattr(self, "M_c_min", None) is not None:
+            return np.asarray(self.M_c_min[c], np.float64)
+        return _hom2cayley(self.M_c[c])
+
+    def GetPoseMin(self):
+        return self.M_t_min.copy() if getattr(self, "M_t_min", None) is not None else _hom2cayley(self.M_t)
+
+    def Set_M_t_from_min(self, M_t_minRep, MtMc=None, MtMc_inv=None):   # src/cam_system_omni.cpp:170-183; MtMc / MtMc_inv: as a device call built them
+        from .io import cayley2hom
+        self.M_t_min = np.asarray(M_t_minRep, np.float64).reshape(6).copy()
+        self.M_t = cayley2hom(self.M_t_min)
+        self.M_t_inv = _inv_mat(self.M_t)
+        if MtMc is None:
+            M_c = [cayley2hom(self.Get_M_c_min(c)) for c in range(len(self.cams))] if getattr(self, "M_c_min", None) is not None else self.M_c
+            MtMc = [_matx_mul(self.M_t, mc) for mc in M_c]
+            MtMc_inv = [_inv_mat(m) for m in MtMc]
+        self.MtMc = [np.asarray(m, np.float64).reshape(4, 4).copy() for m in MtMc]
+        self.MtMc_inv = [np.asarray(m, np.float64).reshape(4, 4).copy() for m in MtMc_inv]
 
     def world_to_cam(self, pts3, cam_idx, ctx=None):
         """Batched WorldToCamHom_fast + isPointInMirrorMask(u, v, 0) on the GPU -> (uv [n,2] float64, flags [n] uint8; bit0 = in mask,
@@ -1675,3 +1703,51 @@ def TrackPreviousFrameWindowSearch(Last, Cur, points, windowSize, minScaleLevel=
     match, p2 = mem.read(o["match"])[:n], mem.read(o["points"])[:n]
     Cur.mvpMapPoints = [int(p) if p >= 0 else None for p in p2]
     return dict(nmatches=int(mem.read(o["nm"])[0]), match21=match, points2=p2)
+
+
+# ---------------------------------------------------------------------------------------------- the frame's pose (mcs_pose_optimization)
+def PoseOptimizationBatch(frames, points, huberMultiplier=1.0, device=False, ctx=None, diag=False):
+    """cOptimizer::PoseOptimization (src/cOptimizer.cpp:259-459) for a list of frames that share one rig model (cameras, M_c) and one point table, as ONE call
+    (mcs_pose_optimization).  Every frame: mvKeys, keypoint_to_cam, mvpMapPoints (ids, objects with mnId, or None), mvInvLevelSigma2, camSystem (GetPoseMin,
+    Get_M_c_min).  points: dict(pos [n][3]).  huberMultiplier: one value or one per frame.  device=True: every array in device memory, nothing read back before
+    the call has returned.  Sets F.mvbOutlier and the frame's rig through Set_M_t_from_min, with MtMc / MtMc_inv as the device built them.
+    -> [(nInliers, outlierShare)] per frame; diag=True: (that list, the mcs_pose_diag records)"""
+    from ._capi import POSE_DIAG_DTYPE, PointTable, PoseFrame
+    ctx = ctx or default_context()
+    npb = len(frames)
+    if npb == 0:
+        check(lib().mcs_pose_optimization(ctx.h, 0, None, None, None, None, 0, None, 0, None, MEM_HOST, None, None, None, None, None, None, None))
+        return ([], np.zeros(0, POSE_DIAG_DTYPE)) if diag else []
+    mem = _DEVICE if device else _HOST
+    rig = frames[0].camSystem
+    nr = rig.GetNrCams()
+    ocs = (type(rig.cams[0].ocam) * nr)(*[cm.ocam for cm in rig.cams])
+    sig = np.asarray(frames[0].mvInvLevelSigma2, np.float64)
+    hub = np.resize(np.asarray(huberMultiplier, np.float64), npb).astype(np.float64)
+    pos = np.ascontiguousarray(points["pos"], np.float64).reshape(-1, 3)
+    g = dict(pos=pos, Mc=np.ascontiguousarray([rig.Get_M_c_min(c) for c in range(nr)], np.float64), ocs=np.frombuffer(ocs, np.uint8).copy(), sig=sig, hub=hub,
+             pose=np.ascontiguousarray([F.camSystem.GetPoseMin() for F in frames], np.float64), MtMc=np.zeros((npb, nr, 16)), inv=np.zeros((npb, nr, 16)),
+             nin=np.zeros(npb, np.int32), share=np.zeros(npb), diag=np.zeros(npb, POSE_DIAG_DTYPE))
+    g = {k: mem.put(v) for k, v in g.items()}
+    per = [dict(keys=mem.put(F.mvKeys), cam=mem.put(np.asarray(F.keypoint_to_cam, np.int32)), points=mem.put(_point_ids(F.mvpMapPoints)),
+                out=mem.put(np.zeros(max(len(F.mvpMapPoints), 1), np.uint8))) for F in frames]
+    fr = (PoseFrame * npb)(*[PoseFrame(mem.ptr(q["keys"]), mem.ptr(q["cam"]), mem.ptr(q["points"]), len(F.mvpMapPoints)) for q, F in zip(per, frames)])
+    outs = (C.c_void_p * npb)(*[mem.ptr(q["out"]) for q in per])
+    tab = PointTable(mem.ptr(g["pos"]), None, len(pos))
+    check(lib().mcs_pose_optimization(ctx.h, npb, fr, C.byref(tab), mem.ptr(g["Mc"]), mem.ptr(g["ocs"]), nr, mem.ptr(g["sig"]), len(sig), mem.ptr(g["hub"]), mem.kind,
+                                      mem.ptr(g["pose"]), mem.ptr(g["MtMc"]), mem.ptr(g["inv"]), outs, mem.ptr(g["nin"]), mem.ptr(g["share"]), mem.ptr(g["diag"])))
+    # ---- only now the host looks at anything
+    pose, MtMc, inv, nin, share = (mem.read(g[k]) for k in ("pose", "MtMc", "inv", "nin", "share"))
+    res = []
+    for p, (F, q) in enumerate(zip(frames, per)):
+        n = len(F.mvpMapPoints)
+        F.mvbOutlier = [bool(v) for v in mem.read(q["out"])[:n]]
+        F.camSystem.Set_M_t_from_min(pose[p], MtMc[p], inv[p])
+        res.append((int(nin[p]), float(share[p])))
+    return (res, mem.read(g["diag"])) if diag else res
+
+
+def PoseOptimization(F, points, huberMultiplier=1.0, device=False, ctx=None):
+    """int cOptimizer::PoseOptimization(cMultiFrame* pFrame, double& inliers, const double& huberMultiplier) -> (the return value, `inliers`): the second is the
+    reference's out-parameter, which is the OUTLIER share nBad / nInitialCorrespondences (src/cOptimizer.cpp:454-456)."""
+    return PoseOptimizationBatch([F], points, huberMultiplier, device, ctx)[0]
