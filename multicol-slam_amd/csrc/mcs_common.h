@@ -274,47 +274,6 @@ struct WorldToCamArgs {   // cMultiCamSys_::WorldToCamHom_fast + isPointInMirror
 };
 void launch_world_to_cam(const WorldToCamArgs& a, hipStream_t s);
 
-// include/misc.h:115-122 (zero-padded fixed-length form, see mcs_describe.hip)
-__device__ __forceinline__ double horner_fixed(const double* coeffs, double x) {
-	double res = 0.0;
-#pragma unroll
-	for (int i = MCS_MAX_POLY - 1; i >= 0; i--) res = res * x + coeffs[i];
-	return res;
-}
-
-// cCamModelGeneral_::WorldToImg (src/cam_model_omni.cpp:146-161): the one statement of the omni projection, for k_world_to_cam (mcs_project.hip)
-// and the Sim3 inlier test (mcs_sim3.hip)
-__device__ __forceinline__ void omni_world_to_img(const OcamDev& cam, double x, double y, double z, double& u, double& v) {
-	double norm = sqrt(x * x + y * y);
-	if (norm == 0.0) norm = 1e-14;
-	const double theta = atan(-z / norm);
-	const double rho = horner_fixed(cam.invP, theta);
-	const double uu = x / norm * rho;
-	const double vv = y / norm * rho;
-	u = uu * cam.c + vv * cam.d + cam.u0;
-	v = uu * cam.e + vv + cam.v0;
-}
-
-// cCamModelGeneral_::isPointInMirrorMask(u, v, 0) (src/cam_model_omni.cpp:163-178): cvRound, the open bounds test, then the level-0 mask (nullptr: bounds only).
-// The one statement for k_world_to_cam (mcs_project.hip) and k_frustum (mcs_frustum.hip).
-__device__ __forceinline__ bool in_mirror_mask(double u, double v, int W, int H, const uint8_t* m) {
-	const int ur = __double2int_rn(u), vr = __double2int_rn(v);
-	if (ur >= W || ur <= 0 || vr >= H || vr <= 0) return false;
-	return !m || m[(size_t)vr * W + ur] > 0;
-}
-
-// ptRot = M * (P, 1) as cv::Matx multiplies: s = 0; s += a(i,k) * b(k) in increasing k (WorldToCamHom_fast, src/cam_system_omni.cpp:114-133)
-__device__ __forceinline__ void matx44_point(const double* M, double x, double y, double z, double r[4]) {
-	const double pt4[4] = {x, y, z, 1.0};
-#pragma unroll
-	for (int row = 0; row < 4; ++row) {
-		double s = 0;
-#pragma unroll
-		for (int k = 0; k < 4; ++k) s += M[4 * row + k] * pt4[k];
-		r[row] = s;
-	}
-}
-
 // cMultiFrame::isInFrustum for every (local map point, camera) slot + the bookkeeping of cTracking::SearchReferencePointsInFrustum (mcs_frustum.hip)
 struct FrustumArgs {
 	const double* pos; const double* normal; const double* minDist; const double* maxDist; const uint8_t* flags; int npoints;   // flags bit0 isBad(), bit1 seen in this frame

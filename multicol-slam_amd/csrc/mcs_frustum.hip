@@ -4,7 +4,7 @@
 // One thread per (map point i, camera c) slot p = i * nrCams + c, which is the visiting order of cORBmatcher::SearchByProjection(F, mapPoints, th)
 // (src/cORBmatcher.cpp:75-85: map point, then camera).  The search therefore runs on the slots as they lie (mcs_project.hip: ProjArgs.active / rowDiv):
 // nothing is compacted and no count leaves the device.  FP64, no contraction; the statements are the reference's, its quirks included.
-#include "mcs_common.h"
+#include "mcs_geom.h"
 
 namespace mcs {
 
@@ -31,26 +31,16 @@ __global__ __launch_bounds__(256) void k_frustum(FrustumArgs a) {
 		// :985-988: a point seen in this frame or bad is not projected; its slots keep whatever earlier frames left there
 		if (a.flags[i] == 0) {
 			const double P0 = a.pos[3 * (size_t)i], P1 = a.pos[3 * (size_t)i + 1], P2 = a.pos[3 * (size_t)i + 2];
-			double r[4];
-			matx44_point(a.MtMcInv + 16 * (size_t)c, P0, P1, P2, r);   // WorldToCamHom_fast; the bool it returns (ptRot.z <= 0) is ignored, :228
 			const mcs_ocam& m = a.cams[c];
-			OcamDev o;
-			o.c = m.c; o.d = m.d; o.e = m.e; o.u0 = m.u0; o.v0 = m.v0;
-			const int deg = m.invP_deg;
-			for (int k = 0; k < MCS_MAX_POLY; ++k) o.invP[k] = k < deg ? m.invP[k] : 0.0;
 			double u, v;
-			omni_world_to_img(o, r[0], r[1], r[2], u, v);
+			(void)world_to_cam_hom_fast(a.MtMcInv + 16 * (size_t)c, ocam_dev_of(m), P0, P1, P2, u, v);   // the bool it returns (ptRot.z <= 0) is ignored, :228
 			if (in_mirror_mask(u, v, m.width, m.height, a.masks ? a.masks[c] : nullptr)) {   // :230
 				const double* T = a.MtMc + 16 * (size_t)c;
-				const double PO0 = P0 - T[3], PO1 = P1 - T[7], PO2 = P2 - T[11];                 // :238
-				double s = 0;
-				s += PO0 * PO0; s += PO1 * PO1; s += PO2 * PO2;
-				const double dist = sqrt(s);                                                     // cv::norm, :239
+				const double PO[3] = {P0 - T[3], P1 - T[7], P2 - T[11]};                         // :238
+				const double dist = norm3(PO);                                                   // :239
 				const double minD = a.minDist[i], maxD = a.maxDist[i];
 				if (!(dist < minD || dist > maxD)) {                                             // :241 (a NaN passes)
-					double d = 0;
-					d += PO0 * a.normal[3 * (size_t)i]; d += PO1 * a.normal[3 * (size_t)i + 1]; d += PO2 * a.normal[3 * (size_t)i + 2];
-					const double viewCos = d / dist;                                             // :247; viewingCosLimit is never applied (:249-250)
+					const double viewCos = dot3(PO, a.normal + 3 * (size_t)i) / dist;            // :247; viewingCosLimit is never applied (:249-250)
 					const double ratio = dist / minD;                                            // :253
 					int lvl = lower_bound_index(a.scales, a.nlevels, ratio);                     // :255-257
 					if (lvl >= a.nlevels) lvl = a.nlevels - 1;                                   // :259-260

@@ -4,8 +4,8 @@
 // One slot per feature of the tracked frame, in feature order, which is the reference's visiting order.  k_track_probes decides which slots the reference
 // would search and writes their windows; the window matcher of mcs_project.hip then runs on the slots as they lie (ProjArgs.active), as it does for the
 // local map (mcs_frustum.hip): nothing is compacted and no count leaves the device.  The tail turns feature-per-slot into slot-per-feature, which is what
-// the rotation filter and the caller read.  FP64, no contraction; the projection is k_world_to_cam's / k_frustum's, statement for statement.
-#include "mcs_common.h"
+// the rotation filter and the caller read.  FP64, no contraction; the projection is mcs_geom.h's world_to_cam_hom_fast.
+#include "mcs_geom.h"
 
 namespace mcs {
 
@@ -21,15 +21,9 @@ __global__ __launch_bounds__(256) void k_track_probes(TrackArgs t) {
 		if (t.project) {
 			if (!(t.outlier && t.outlier[i]) && (unsigned)kp.octave < (unsigned)t.nlevels) {     // :2014; the octave indexes mvScaleFactors (:2028)
 				const double P0 = t.pos[3 * (size_t)id], P1 = t.pos[3 * (size_t)id + 1], P2 = t.pos[3 * (size_t)id + 2];
-				double r[4];
-				matx44_point(t.MtMcInv + 16 * (size_t)c, P0, P1, P2, r);   // WorldToCamHom_fast; the bool it returns (ptRot.z <= 0) is ignored, :2020
 				const mcs_ocam& m = t.cams[c];
-				OcamDev o;
-				o.c = m.c; o.d = m.d; o.e = m.e; o.u0 = m.u0; o.v0 = m.v0;
-				const int deg = m.invP_deg;
-				for (int k = 0; k < MCS_MAX_POLY; ++k) o.invP[k] = k < deg ? m.invP[k] : 0.0;
 				double u, v;
-				omni_world_to_img(o, r[0], r[1], r[2], u, v);
+				(void)world_to_cam_hom_fast(t.MtMcInv + 16 * (size_t)c, ocam_dev_of(m), P0, P1, P2, u, v);   // the bool it returns (ptRot.z <= 0) is ignored, :2020
 				if (in_mirror_mask(u, v, m.width, m.height, t.masks ? t.masks[c] : nullptr)) {   // :2022
 					t.px[i] = u; t.py[i] = v;
 					t.rad[i] = t.th * t.scales[kp.octave];                                   // :2028

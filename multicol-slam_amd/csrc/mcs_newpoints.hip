@@ -13,6 +13,7 @@
 // behind them on the context's stream.  FP64 throughout, no contraction (-ffp-contract=off): every product and sum is the reference's, in its order; the OpenCV
 // pieces are restated as DESIGN.md section 7 lists them.
 #include "mcs_host.h"
+#include "mcs_geom.h"
 #include <algorithm>
 #include <cstddef>
 
@@ -43,47 +44,17 @@ struct NpTriArgs {
 	int* verdict; double* x3D;
 };
 
-// cv::norm(Vec3d): sqrt(((0 + a0^2) + a1^2) + a2^2)
-__device__ __forceinline__ double np_norm3(const double* v) {
-	double s = 0;
-	for (int k = 0; k < 3; ++k) s += v[k] * v[k];
-	return sqrt(s);
-}
-// Matx::dot / Vec::dot: s = 0; s += a(k) * b(k)
-__device__ __forceinline__ double np_dot3(const double* a, const double* b) {
-	double s = 0;
-	for (int k = 0; k < 3; ++k) s += a[k] * b[k];
-	return s;
-}
-// top-left 3x3 of a row-major 4x4 (or a 3x3 with ld = 3) times a 3-vector: s = 0; s += a(i,k) * b(k)
-__device__ __forceinline__ void np_mat3_vec3(const double* M, int ld, const double* p, double* r) {
-	for (int i = 0; i < 3; ++i) {
-		double s = 0;
-		for (int k = 0; k < 3; ++k) s += M[ld * i + k] * p[k];
-		r[i] = s;
-	}
-}
-__device__ __forceinline__ void np_mat4_vec4(const double* M, const double* p, double* r) {
-	for (int i = 0; i < 4; ++i) {
-		double s = 0;
-		for (int k = 0; k < 4; ++k) s += M[4 * i + k] * p[k];
-		r[i] = s;
-	}
-}
-
 // cv::Matx33d ComputeE(const cv::Matx44d& T1, const cv::Matx44d& T2) (src/misc.cpp:71-85)
 __device__ void np_compute_E(const double* T1, const double* T2, double* E) {
 	double R12[9], N[9], t12[3];
-	for (int i = 0; i < 3; ++i)
-		for (int j = 0; j < 3; ++j) {   // R1w * R2w.t() and (-R1w) * R2w.t()
-			double s = 0, sn = 0;
-			for (int k = 0; k < 3; ++k) { s += T1[4 * i + k] * T2[4 * j + k]; sn += (-T1[4 * i + k]) * T2[4 * j + k]; }
-			R12[3 * i + j] = s; N[3 * i + j] = sn;
-		}
+	for (int i = 0; i < 3; ++i) {   // R1w * R2w.t() and (-R1w) * R2w.t()
+		const double neg[3] = {-T1[4 * i], -T1[4 * i + 1], -T1[4 * i + 2]};
+		for (int j = 0; j < 3; ++j) { R12[3 * i + j] = dot3(T1 + 4 * i, T2 + 4 * j); N[3 * i + j] = dot3(neg, T2 + 4 * j); }
+	}
 	const double t1w[3] = {T1[3], T1[7], T1[11]}, t2w[3] = {T2[3], T2[7], T2[11]};
-	np_mat3_vec3(N, 3, t2w, t12);
+	mat3_vec3(N, 3, t2w, t12);
 	for (int i = 0; i < 3; ++i) t12[i] = t12[i] + t1w[i];
-	const double ialpha = 1. / np_norm3(t12);   // Vec operator/=(double) of OpenCV 3.x: a multiplication by 1./alpha
+	const double ialpha = 1. / norm3(t12);   // Vec operator/=(double) of OpenCV 3.x: a multiplication by 1./alpha
 	for (int i = 0; i < 3; ++i) t12[i] = t12[i] * ialpha;
 	const double S[9] = {0.0, -t12[2], t12[1], t12[2], 0.0, -t12[0], -t12[1], t12[0], 0.0};   // Skew (include/misc.h:58-64)
 	for (int i = 0; i < 3; ++i)
@@ -100,9 +71,8 @@ __global__ __launch_bounds__(256) void k_np_setup(NpSetupArgs a) {
 		const int c = a.mpCam[g];
 		double z = __longlong_as_double(0x7FF8000000000000ll);   // a camera index outside the rig: no depth
 		if (c >= 0 && c < a.k2.nrCams) {
-			const double x4[4] = {a.mpPos[3 * (size_t)g], a.mpPos[3 * (size_t)g + 1], a.mpPos[3 * (size_t)g + 2], 1.0};
-			double r[4];
-			np_mat4_vec4(a.k2.MtMcInv + 16 * (size_t)c, x4, r);
+			double r[3];
+			matx44_point<3>(a.k2.MtMcInv + 16 * (size_t)c, a.mpPos + 3 * (size_t)g, r);
 			z = r[2];
 		}
 		a.z[g] = z;
@@ -116,7 +86,7 @@ __global__ __launch_bounds__(256) void k_np_setup(NpSetupArgs a) {
 	if (threadIdx.x == 0) {   // src/cLocalMapping.cpp:230, 246-248; GetCameraCenter = Hom2T(M_t)
 		double vb[3];
 		for (int k = 0; k < 3; ++k) vb[k] = a.k2.Mt[4 * k + 3] - a.k1.Mt[4 * k + 3];
-		*a.baseline = np_norm3(vb);
+		*a.baseline = norm3(vb);
 		*a.median = __longlong_as_double(0x7FF8000000000000ll);   // stays NaN only when no depth has the wanted rank (a NaN depth: the reference's sort is undefined then)
 		*a.skip = 0;
 	}
@@ -142,17 +112,9 @@ __global__ __launch_bounds__(256) void k_np_median(const double* __restrict__ z,
 	}
 }
 
-// bool cMultiCamSys_::WorldToCamHom_fast(int c, cv::Vec4d&, cv::Vec2d&) (src/cam_system_omni.cpp:92-112, the flagMcMt branch)
+// the Vec4d overload of WorldToCamHom_fast (src/cam_system_omni.cpp:92-112); one body for both reprojections
 __device__ __noinline__ bool np_world_to_cam(const NpKf& kf, int c, const double* pt4, double& u, double& v) {
-	double r[4];
-	np_mat4_vec4(kf.MtMcInv + 16 * (size_t)c, pt4, r);
-	const mcs_ocam& m = kf.cams[c];
-	OcamDev o;
-	o.c = m.c; o.d = m.d; o.e = m.e; o.u0 = m.u0; o.v0 = m.v0;
-	const int deg = m.invP_deg;
-	for (int k = 0; k < MCS_MAX_POLY; ++k) o.invP[k] = k < deg ? m.invP[k] : 0.0;
-	omni_world_to_img(o, r[0], r[1], r[2], u, v);
-	return r[2] <= 0.0;
+	return world_to_cam_hom_fast(kf.MtMcInv + 16 * (size_t)c, ocam_dev_of(kf.cams[c]), pt4[0], pt4[1], pt4[2], u, v, pt4[3]);
 }
 
 enum { NP_NONE = 0, NP_ACCEPTED = 1, NP_PARALLAX = 2, NP_BEHIND1 = 3, NP_REPROJ1 = 4, NP_BEHIND2 = 5, NP_REPROJ2 = 6, NP_DISTANCE = 7, NP_SKIPPED = 8 };
@@ -177,22 +139,18 @@ __global__ __launch_bounds__(128) void k_np_triangulate(NpTriArgs a) {
 	double ray1[3], ray2[3];
 	for (int k = 0; k < 3; ++k) { ray1[k] = a.k1.rays[3 * (size_t)i + k]; ray2[k] = a.k2.rays[3 * (size_t)idx2 + k]; }
 	double rayRot1[3], rayRot2[3];
-	np_mat3_vec3(Tcw1, 4, ray1, rayRot1);   // :297-298
-	np_mat3_vec3(Tcw2, 4, ray2, rayRot2);
-	const double cosParallax = np_dot3(rayRot1, rayRot2) / (np_norm3(rayRot1) * np_norm3(rayRot2));   // :300-301
+	mat3_vec3(Tcw1, 4, ray1, rayRot1);   // :297-298
+	mat3_vec3(Tcw2, 4, ray2, rayRot2);
+	const double cosParallax = dot3(rayRot1, rayRot2) / (norm3(rayRot1) * norm3(rayRot2));   // :300-301
 	if (cosParallax < 0 || cosParallax > a.cosThresh) { a.verdict[i] = NP_PARALLAX; return; }         // :303
-	double R12[9], t12[3];   // relOri = Tcw1inv * Tcw2 (:306), Hom2T / Hom2R (:307-308)
-	for (int r = 0; r < 3; ++r)
-		for (int j = 0; j < 4; ++j) {
-			double s = 0;
-			for (int k = 0; k < 4; ++k) s += Tcw1inv[4 * r + k] * Tcw2[4 * k + j];
-			if (j < 3) R12[3 * r + j] = s; else t12[r] = s;
-		}
+	double relOri[16], R12[9], t12[3];   // relOri = Tcw1inv * Tcw2 (:306), Hom2T / Hom2R (:307-308)
+	matx44_mul(Tcw1inv, Tcw2, relOri);
+	for (int r = 0; r < 3; ++r) { R12[3 * r] = relOri[4 * r]; R12[3 * r + 1] = relOri[4 * r + 1]; R12[3 * r + 2] = relOri[4 * r + 2]; t12[r] = relOri[4 * r + 3]; }
 	// triangulate_point(t12, R12, ray1, ray2) (src/misc.cpp:25-50)
 	double f2[3];
-	np_mat3_vec3(R12, 3, ray2, f2);
-	const double b0 = np_dot3(t12, ray1), b1 = np_dot3(t12, f2);
-	const double a00 = np_dot3(ray1, ray1), a10 = np_dot3(ray1, f2), a01 = -a10, a11 = -np_dot3(f2, f2);
+	mat3_vec3(R12, 3, ray2, f2);
+	const double b0 = dot3(t12, ray1), b1 = dot3(t12, f2);
+	const double a00 = dot3(ray1, ray1), a10 = dot3(ray1, f2), a01 = -a10, a11 = -dot3(f2, f2);
 	double i00 = 0.0, i01 = 0.0, i10 = 0.0, i11 = 0.0;   // Matx22d::inv(), OpenCV 3.x's closed form: a zero determinant gives the zero matrix
 	double d = a00 * a11 - a01 * a10;
 	if (d != 0) {
@@ -208,9 +166,8 @@ __global__ __launch_bounds__(128) void k_np_triangulate(NpTriArgs a) {
 		const double xn = t12[k] + l1 * f2[k];
 		x3[k] = (xm + xn) / 2.0;
 	}
-	const double p4[4] = {x3[0], x3[1], x3[2], 1.0};
 	double x3D4[4];
-	np_mat4_vec4(Tcw1, p4, x3D4);   // :312-314
+	matx44_point<4>(Tcw1, x3, x3D4);   // :312-314
 	X[0] = x3D4[0]; X[1] = x3D4[1]; X[2] = x3D4[2];
 	double u, v;
 	if (np_world_to_cam(a.k1, camIdx1, x3D4, u, v)) { a.verdict[i] = NP_BEHIND1; return; }   // :323-325
@@ -225,7 +182,7 @@ __global__ __launch_bounds__(128) void k_np_triangulate(NpTriArgs a) {
 	}
 	double normal1[3], normal2[3];   // :347-351
 	for (int k = 0; k < 3; ++k) { normal1[k] = x3D4[k] - a.k1.Mt[4 * k + 3]; normal2[k] = x3D4[k] - a.k2.Mt[4 * k + 3]; }
-	const double dist1 = np_norm3(normal1), dist2 = np_norm3(normal2);
+	const double dist1 = norm3(normal1), dist2 = norm3(normal2);
 	if (dist1 == 0 || dist2 == 0 || dist1 > a.maxDist || dist2 > a.maxDist) { a.verdict[i] = NP_DISTANCE; return; }   // :359-361
 	a.verdict[i] = NP_ACCEPTED;
 	if (a.valid1) a.valid1[i] = 0;   // mpCurrentMultiKeyFrame->AddMapPoint(pMP, idx1), :367

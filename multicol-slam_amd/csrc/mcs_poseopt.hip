@@ -13,6 +13,7 @@
 // The Jacobian is derived here by the chain rule (the reference's is generated code and is not used in any form): with Mct = Mt * Mc the camera-frame point is
 // p = Rc^T Rt^T (X - t) - Rc^T tc, so dp/dt = -(Rt Rc)^T and dp/dc_i = Rc^T (dRt/dc_i)^T (X - t); d(u, v)/dp differentiates WorldToImg; e = z - (u, v).
 #include "mcs_poseopt.h"
+#include "mcs_geom.h"
 #include <cfloat>
 
 using namespace mcs;
@@ -36,50 +37,13 @@ struct PoseShared {
 	int nInit, nonfinite, nBad, go, cont;
 };
 
-// include/misc.h:133-160
-__device__ void cayley2rot_dev(const double* c, double* R) {
-	const double c1 = c[0], c2 = c[1], c3 = c[2];
-	const double c1s = c1 * c1, c2s = c2 * c2, c3s = c3 * c3;
-	const double scale = 1.0 + c1s + c2s + c3s;
-	R[0] = 1 + c1s - c2s - c3s; R[1] = 2 * (c1 * c2 - c3);   R[2] = 2 * (c1 * c3 + c2);
-	R[3] = 2 * (c1 * c2 + c3);  R[4] = 1 - c1s + c2s - c3s;  R[5] = 2 * (c2 * c3 - c1);
-	R[6] = 2 * (c1 * c3 - c2);  R[7] = 2 * (c2 * c3 + c1);   R[8] = 1 - c1s - c2s + c3s;
-	const double inv = 1 / scale;
-	for (int k = 0; k < 9; ++k) R[k] = inv * R[k];
-}
-// :212-224
-__device__ void cayley2hom_dev(const double* c6, double* M) {
-	double R[9];
-	cayley2rot_dev(c6, R);
-	for (int r = 0; r < 3; ++r) { M[4 * r] = R[3 * r]; M[4 * r + 1] = R[3 * r + 1]; M[4 * r + 2] = R[3 * r + 2]; M[4 * r + 3] = c6[3 + r]; }
-	M[12] = M[13] = M[14] = 0.0; M[15] = 1.0;
-}
-// cv::Matx44d product: s = 0; s += a(i,k) * b(k,j) in increasing k
-__device__ void matx44_mul(const double* A, const double* B, double* C) {
-	for (int i = 0; i < 4; ++i)
-		for (int j = 0; j < 4; ++j) {
-			double s = 0;
-			for (int k = 0; k < 4; ++k) s += A[4 * i + k] * B[4 * k + j];
-			C[4 * i + j] = s;
-		}
-}
-// cConverter::invMat (src/cConverter.cpp:31-44): R^T and -R^T * t
-__device__ void inv_mat_dev(const double* M, double* out) {
-	for (int i = 0; i < 3; ++i) {
-		double s = 0;
-		for (int k = 0; k < 3; ++k) { out[4 * i + k] = M[4 * k + i]; s += (-M[4 * k + i]) * M[4 * k + 3]; }
-		out[4 * i + 3] = s;
-	}
-	out[12] = out[13] = out[14] = 0.0; out[15] = 1.0;
-}
-
 // Mct and its inverse of camera c at `pose` (EdgeProjectXYZ2MCS::computeError, Set_M_t_from_min); Build: also A_i = Rc^T (dRt/dc_i)^T
 template <bool Build>
 __device__ void camera_state(PoseShared& sh, int c, const double* pose, double* MtMcOut) {
 	double Mt[16], Mct[16];
-	cayley2hom_dev(pose, Mt);
+	cayley2hom(pose, Mt);
 	matx44_mul(Mt, sh.McH[c], Mct);
-	inv_mat_dev(Mct, sh.inv[c]);
+	inv_mat(Mct, sh.inv[c]);
 	if (MtMcOut) for (int k = 0; k < 16; ++k) MtMcOut[k] = Mct[k];
 	if (Build) {
 		const double c1 = pose[0], c2 = pose[1], c3 = pose[2];
@@ -106,15 +70,6 @@ __device__ __forceinline__ bool edge_of(const PoseArgs& a, const mcs_keypoint* k
 	if (pid < 0 || pid >= a.npoints) return false;
 	c = cam[i]; oct = keys[i].octave;
 	return c >= 0 && c < a.nrCams && oct >= 0 && oct < a.nlevels;
-}
-
-// the camera-frame point of an edge: Matx44 * Vec4 in increasing k
-__device__ __forceinline__ void camera_point(const double* M, const double* X, double* p) {
-	for (int r = 0; r < 3; ++r) {
-		double s = 0;
-		s += M[4 * r] * X[0]; s += M[4 * r + 1] * X[1]; s += M[4 * r + 2] * X[2]; s += M[4 * r + 3] * 1.0;
-		p[r] = s;
-	}
 }
 
 // d(u, v) / d(x, y, z) of omni_world_to_img; the norm == 0 -> 1e-14 branch is a constant
@@ -177,7 +132,7 @@ __device__ void pass(PoseShared& sh, const PoseArgs& a, const Edges& e, bool lev
 		if (levelZero && e.outlier[i]) continue;
 		const double X[3] = {a.pos[3 * (size_t)pid], a.pos[3 * (size_t)pid + 1], a.pos[3 * (size_t)pid + 2]};
 		double p[3], u, v;
-		camera_point(sh.inv[c], X, p);
+		matx44_point<3>(sh.inv[c], X, p);   // the camera-frame point of the edge
 		omni_world_to_img(sh.cam[c], p[0], p[1], p[2], u, v);
 		const double e0 = (double)e.keys[i].x - u, e1 = (double)e.keys[i].y - v;
 		const double w = a.invSigma2[oct];
@@ -224,7 +179,7 @@ __device__ void outlier_pass(PoseShared& sh, const PoseArgs& a, const Edges& e, 
 		if (!edge_of(a, e.keys, e.cam, e.points, i, pid, c, oct) || e.outlier[i]) continue;
 		const double X[3] = {a.pos[3 * (size_t)pid], a.pos[3 * (size_t)pid + 1], a.pos[3 * (size_t)pid + 2]};
 		double p[3], u, v;
-		camera_point(sh.inv[c], X, p);
+		matx44_point<3>(sh.inv[c], X, p);   // the camera-frame point of the edge
 		omni_world_to_img(sh.cam[c], p[0], p[1], p[2], u, v);
 		const double e0 = (double)e.keys[i].x - u, e1 = (double)e.keys[i].y - v;
 		const double w = a.invSigma2[oct];
@@ -286,13 +241,10 @@ __global__ void __launch_bounds__(kPoseThreads) k_poseopt(PoseArgs a, PoseChunk 
 
 	if (tid < nr) {
 		const mcs_ocam& m = a.cams[tid];
-		OcamDev& o = sh.cam[tid];
-		o.c = m.c; o.d = m.d; o.e = m.e; o.u0 = m.u0; o.v0 = m.v0; o.invAffine = m.c - m.d * m.e;
-		const int deg = m.invP_deg < 0 ? 0 : m.invP_deg > MCS_MAX_POLY ? MCS_MAX_POLY : m.invP_deg;
-		for (int k = 0; k < MCS_MAX_POLY; ++k) { o.p[k] = 0.0; o.invP[k] = k < deg ? m.invP[k] : 0.0; }
-		for (int k = 0; k < MCS_MAX_POLY; ++k) sh.dInvP[tid][k] = k + 1 < deg ? m.invP[k + 1] * (double)(k + 1) : 0.0;
-		o.p_deg = 0; o.invP_deg = deg; o.fastOk = 0; o.tabIdx = 0;
-		cayley2hom_dev(a.McMin + 6 * tid, sh.McH[tid]);
+		const OcamDev o = ocam_dev_of(m);
+		sh.cam[tid] = o;
+		for (int k = 0; k < MCS_MAX_POLY; ++k) sh.dInvP[tid][k] = k + 1 < o.invP_deg ? m.invP[k + 1] * (double)(k + 1) : 0.0;
+		cayley2hom(a.McMin + 6 * tid, sh.McH[tid]);
 	}
 	if (tid == 0) {
 		for (int k = 0; k < 6; ++k) { sh.pose[k] = poseOut[k]; sh.x[k] = 0.0; }

@@ -13,7 +13,7 @@
 // members' smallest keys  dist<<42 | cell<<20 | index  (k_proj_candidates, one wave per projection, fully parallel), and the greedy
 // part — a feature taken by an earlier projection is skipped by all later ones — runs as the same speculative wave-parallel
 // commit as the brute-force searches (k_proj_greedy).  Pure integer + IEEE double arithmetic: bit-exact.
-#include "mcs_common.h"
+#include "mcs_geom.h"
 
 namespace mcs {
 
@@ -277,14 +277,12 @@ __global__ __launch_bounds__(64) void k_world_to_cam(WorldToCamArgs a) {
 	const int i = blockIdx.x * 64 + threadIdx.x;
 	if (i >= a.n) return;
 	const int c = a.pcam[i];
-	double r[4];
-	matx44_point(a.M + 16 * (size_t)c, a.pts[3 * (size_t)i], a.pts[3 * (size_t)i + 1], a.pts[3 * (size_t)i + 2], r);
 	double u, v;
-	omni_world_to_img(a.cams[c], r[0], r[1], r[2], u, v);
+	const bool behind = world_to_cam_hom_fast(a.M + 16 * (size_t)c, a.cams[c], a.pts[3 * (size_t)i], a.pts[3 * (size_t)i + 1], a.pts[3 * (size_t)i + 2], u, v);
 	a.uv[2 * (size_t)i] = u; a.uv[2 * (size_t)i + 1] = v;
 	unsigned fl = 0;
 	if (in_mirror_mask(u, v, a.width[c], a.height[c], a.masks ? a.masks[c] : nullptr)) fl |= 1u;
-	if (r[2] <= 0.0) fl |= 2u;
+	if (behind) fl |= 2u;
 	a.flags[i] = (uint8_t)fl;
 }
 

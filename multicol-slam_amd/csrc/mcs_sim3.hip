@@ -13,6 +13,7 @@
 // (seed or caller draws, solver, iteration) alone, so the outputs do not depend on how the iterations are split into calls.
 // FP64 throughout, no contraction (-ffp-contract=off): every product and sum is the reference's, in the reference's order.
 #include "mcs_host.h"
+#include "mcs_geom.h"
 #include <algorithm>
 #include <cfloat>
 #include <climits>
@@ -59,48 +60,21 @@ struct Sim3SetupArgs {
 	Sim3Corr* corr;
 };
 
-// cv::Matx product, s = 0; s += a(i,k) * b(k) in increasing k
-__device__ __forceinline__ void mat4_vec4(const double* M, const double* p, double* r, int rows) {
-	for (int i = 0; i < rows; ++i) {
-		double s = 0;
-		for (int k = 0; k < 4; ++k) s += M[4 * i + k] * p[k];
-		r[i] = s;
-	}
-}
-
-// cConverter::invMat (src/cConverter.cpp:31-44): R^T, t = -R^T t
-__device__ __forceinline__ void inv_mat(const double* M, double* o) {
-	for (int i = 0; i < 3; ++i)
-		for (int j = 0; j < 3; ++j) o[4 * i + j] = M[4 * j + i];
-	for (int i = 0; i < 3; ++i) {
-		double s = 0;
-		for (int k = 0; k < 3; ++k) s += -o[4 * i + k] * M[4 * k + 3];
-		o[4 * i + 3] = s;
-	}
-	o[12] = 0.0; o[13] = 0.0; o[14] = 0.0; o[15] = 1.0;
-}
-
 __global__ __launch_bounds__(64) void k_sim3_setup(Sim3SetupArgs a) {
 	const int g = blockIdx.x * 64 + threadIdx.x;
 	if (g < a.nrCams) inv_mat(a.Mc + 16 * (size_t)g, a.McInv + 16 * (size_t)g);
 	if (g >= a.nc) return;
 	const int s = a.corrSolver[g];
 	Sim3Corr c;
+#pragma unroll
 	for (int side = 0; side < 2; ++side) {
 		const double* X = a.Xw + 6 * (size_t)g + 3 * side;
 		const double* hom = a.Mtinv + 32 * (size_t)s + 16 * side;
 		const int cam = a.cam[2 * (size_t)g + side];
 		double* Xc = side ? c.X2c : c.X1c;
-		for (int i = 0; i < 3; ++i) {   // Hom2R(hom) * X + Hom2T(hom)
-			double acc = 0;
-			for (int k = 0; k < 3; ++k) acc += hom[4 * i + k] * X[k];
-			Xc[i] = acc + hom[4 * i + 3];
-		}
-		const double pt4[4] = {X[0], X[1], X[2], 1.0};   // WorldToCamHom_fast(cam, Xw, proj): MtMc_inv[cam] * (Xw, 1), then WorldToImg
-		double r[3];
-		mat4_vec4(a.MtMcInv + ((size_t)s * 2 + side) * a.nrCams * 16 + 16 * (size_t)cam, pt4, r, 3);
+		matx44_point<3>(hom, X, Xc);   // Hom2R(hom) * X + Hom2T(hom): the same sums, the last term being hom(i,3) * 1.0
 		double* p = side ? c.p2 : c.p1;
-		omni_world_to_img(a.cams[cam], r[0], r[1], r[2], p[0], p[1]);
+		(void)world_to_cam_hom_fast(a.MtMcInv + ((size_t)s * 2 + side) * a.nrCams * 16 + 16 * (size_t)cam, a.cams[cam], X[0], X[1], X[2], p[0], p[1]);
 		const double e = 9.210 * a.sigma2[2 * (size_t)g + side];   // mvnMaxError is a std::vector<size_t>: the product is truncated
 		const double et = (double)(unsigned long long)e;
 		if (side) { c.e2 = et; c.c2 = cam; } else { c.e1 = et; c.c1 = cam; }
@@ -367,10 +341,10 @@ __global__ __launch_bounds__(256) void k_sim3_score(Sim3ScoreArgs a) {
 			const Sim3Corr c = corr[i];
 			const double x2[4] = {c.X2c[0], c.X2c[1], c.X2c[2], 1.0}, x1[4] = {c.X1c[0], c.X1c[1], c.X1c[2], 1.0};
 			double p21[4], p12[4], r1[3], r2[3];
-			mat4_vec4(A, x2, p21, 4);   // mT12i * (X3Dc2, 1)
-			mat4_vec4(B, x1, p12, 4);   // mT21i * (X3Dc1, 1)
-			mat4_vec4(sM + 12 * c.c1, p21, r1, 3);   // invMat(M_c(camIdx1)) * pt2_in_1
-			mat4_vec4(sM + 12 * c.c2, p12, r2, 3);   // invMat(M_c(camIdx2)) * pt1_in_2
+			matx44_vec4<4>(A, x2, p21);   // mT12i * (X3Dc2, 1)
+			matx44_vec4<4>(B, x1, p12);   // mT21i * (X3Dc1, 1)
+			matx44_vec4<3>(sM + 12 * c.c1, p21, r1);   // invMat(M_c(camIdx1)) * pt2_in_1
+			matx44_vec4<3>(sM + 12 * c.c2, p12, r2);   // invMat(M_c(camIdx2)) * pt1_in_2
 			double u1, v1, u2, v2;
 			omni_world_to_img(sCam[c.c1], r1[0], r1[1], r1[2], u1, v1);
 			omni_world_to_img(sCam[c.c2], r2[0], r2[1], r2[2], u2, v2);

@@ -1,6 +1,6 @@
 """The extractor's plan (csrc/mcs_plan.hip: level geometry, FAST cells, slot / dense / selection ranges, oct-tree roots, resize taps, mask maps) on its own,
 without a GPU, through tests/cpp/plan_driver.cpp.  The driver and the plan's translation unit are compiled by hipcc in host-only mode with the library's
-floating-point flags (plain g++ cannot read csrc/mcs_common.h: its inline device helpers call HIP device intrinsics); the program makes no HIP call.
+floating-point flags (plain g++ cannot read csrc/mcs_common.h: its structs hold HIP streams and events and carry __host__ __device__ members); the program makes no HIP call.
 
 Shapes: 754x480 (Lafida), 160x120, 400x300 and a portrait 120x400 at scale 1.2, 160x120 at 2.0 and 2.5, 345x532 at 1.5 (only its top levels lack an oct-tree
 root), AGAST types 0-3.  Each asks for 8 levels; where the geometry does not hold 8 (160x120 at 1.2: level 6 would be 40 rows, below the 44-px border) the plan is
