@@ -630,8 +630,9 @@ int mcs_window_search_frames(mcs_ctx*, const mcs_tracked_frame* f1, const mcs_po
  *   diag               optional, [nproblems].  stop[r]: why round r ended — 0 its 10 iterations ran, 1 the terminate action set the stop flag, 2 solve() returned
  *                      Terminate (10 trials or rho == 0), 3 Terminate by its nBad >= 3 rule, 4 the round did not run (the stop flag is never cleared, or no active
  *                      edge).  trials[r][i] = Levenberg trials of iteration i; lambda = the final _currentLambda; chi2 = the terminate action's last chi2.
- * A problem without correspondence is not optimised: pose unchanged, count 0, share 0, status 0.  A problem whose first evaluation holds a non-finite residual
- * or Jacobian entry is not optimised either: status MCS_POSE_NONFINITE, pose unchanged, flags 0, count nInitialCorrespondences (a status, not an error, for
+ * A problem without correspondence is not optimised: pose unchanged, count 0, share 0, status 0.  A problem whose first evaluation holds a non-finite residual,
+ * Jacobian entry, edge weight, Huber delta or delta^2 (a multiplier of 1e200 overflows it), or a non-finite sum of H, b or chi2 (a weight of 1e308 does
+ * that) is not optimised either: status MCS_POSE_NONFINITE, pose unchanged, flags 0, count nInitialCorrespondences (a status, not an error, for
  * either kind).  Guards: a point id >= table->n, a camera outside [0, nr_cams) or an octave outside [0, nlevels) is refused with MCS_ERR_INVALID in host kind
  * before anything runs; in device kind that feature contributes no edge.  Features per problem <= 65536, nr_cams <= 32.  nproblems = 0 is a successful no-op.
  * DEVICE: the call only enqueues on the context's stream — no host wait, no count read back; it needs no scratch.  HOST: through the staging block.  A problem's

@@ -155,7 +155,7 @@ __device__ void pass(PoseShared& sh, const PoseArgs& a, const Edges& e, bool lev
 			J[1][k] = -(D[1][0] * dp[0] + D[1][1] * dp[1] + D[1][2] * dp[2]);
 			bad |= !finite_(J[0][k]) || !finite_(J[1][k]);
 		}
-		bad |= !finite_(e0) || !finite_(e1);
+		bad |= !finite_(e0) || !finite_(e1) || !finite_(w);
 		const double rw = rho1 * w;   // robustInformation = rho[1] * information; no second-order term
 		int s = 0;
 #pragma unroll
@@ -281,7 +281,11 @@ __global__ void __launch_bounds__(kPoseThreads) k_poseopt(PoseArgs a, PoseChunk 
 				if (tid < nr) camera_state<true>(sh, tid, sh.pose, nullptr);
 				__syncthreads();
 				pass<true>(sh, a, e, rnd == 1, delta, dsqr);
-				if (rnd == 0 && it == 0 && sh.nonfinite) { status = MCS_POSE_NONFINITE; break; }   // uniform: not optimised
+				if (rnd == 0 && it == 0) {   // the screen of the first evaluation: every edge's residual, Jacobian and weight, the Huber pair, the sums
+					bool nf = sh.nonfinite || !finite_(delta) || !finite_(dsqr);
+					for (int k = 0; k < kSums; ++k) nf |= !finite_(sh.tot[k]);
+					if (nf) { status = MCS_POSE_NONFINITE; break; }   // uniform: not optimised
+				}
 				double currentChi = 0, iniChi = 0, rho = 0, postChi = 0;
 				int qmax = 0;
 				if (tid == 0) {

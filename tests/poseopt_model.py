@@ -239,6 +239,27 @@ class Result:
     pass
 
 
+def sum_margin(a, b):
+    """relative distance of two chi2 sums, scaled by 1e3 (DECISION MARGINS).  An infinite sum is infinitely far from a finite one; a NaN sum decides by being
+    NaN, which nothing here can vouch for: distance 0."""
+    if math.isnan(a) or math.isnan(b):
+        return 0.0
+    if math.isinf(a) or math.isinf(b):
+        return 0.0 if a == b else math.inf
+    return abs(a - b) / max(abs(a), abs(b), 1e-300) * 1e3
+
+
+def threshold_margin(c2, t):
+    """smallest distance of the values c2 from the threshold t >= 0 they are compared with, relative to t.  Against an infinite threshold a finite value is
+    infinitely far from its edge; against t == 0 there is nothing to be relative to and the distance is the value itself."""
+    c2 = np.asarray(c2, np.float64)
+    if math.isinf(t):
+        return float(np.min(np.where(c2 == t, 0.0, math.inf)))
+    if t == 0.0:
+        return float(np.min(np.abs(c2)))
+    return float(np.min(np.abs(c2 - t) / t))
+
+
 def optimize(pr, reverse=False, fix=(), guard=True):
     with np.errstate(all="ignore"):
         return _optimize(pr, reverse, fix, guard)
@@ -266,6 +287,10 @@ def _optimize(pr, reverse, fix, guard):
     res.iters, res.stop, res.trials = [0, 0], [STOP_NOT_RUN, STOP_NOT_RUN], np.zeros((2, 10), np.int32)
     res.lam, res.chi2, res.n_inliers, res.share, res.margin = 0.0, 0.0, 0, 0.0, math.inf
     res.nInitial = nInitial
+    # what the tests of the hostile scenes ask about a run: failed 6x6 solves, active edges at the start of each round, the [build, trial] passes behind the
+    # first evaluation that held a non-finite sum
+    res.failed_solves, res.n_active, res.late_nonfinite, res.flag_margin = 0, [nInitial, 0], [0, 0], math.inf   # flag_margin: of the two outlier passes alone
+    res.accepted_failed = 0
     if nInitial == 0:   # quirk 6: nothing is optimised
         res.MtMc, res.MtMc_inv = rig_from_min(res.pose, pr.Mc_min)
         return res
@@ -275,6 +300,12 @@ def _optimize(pr, reverse, fix, guard):
     omega = pr.inv_sigma2[pr.octave[idx_all]]
     level = np.zeros(nInitial, np.int32)
     margins = []
+
+    def not_optimised():   # the project's choice: pose unchanged, no flag, every edge counted
+        res.status = POSE_NONFINITE
+        res.n_inliers, res.share = nInitial, 0.0
+        res.MtMc, res.MtMc_inv = rig_from_min(res.pose, pr.Mc_min)
+        return res
 
     def ssum(a):   # one ordered chain over the edges
         a = a[::-1] if reverse else a
@@ -286,7 +317,7 @@ def _optimize(pr, reverse, fix, guard):
     def robust(c2, track=True):   # robustify: rho[0], rho[1]
         inl = c2 <= dsqr
         if track and len(c2):
-            margins.append(float(np.min(np.abs(c2 - dsqr) / dsqr)))
+            margins.append(threshold_margin(c2, dsqr))
         sq = np.sqrt(np.where(inl, 1.0, c2))
         return np.where(inl, c2, 2 * sq * delta - dsqr), np.where(inl, 1.0, delta / sq)
 
@@ -313,6 +344,7 @@ def _optimize(pr, reverse, fix, guard):
             act = np.ones(nInitial, bool)
         if rnd == 1 and "clear_stop" in fix:
             stop_flag = False
+        res.n_active[rnd] = int(act.sum())
         x = np.zeros(6)           # buildStructure -> Solver::resize: zeros
         result_ok = True
         it = 0
@@ -321,11 +353,11 @@ def _optimize(pr, reverse, fix, guard):
         while it < 10 and not stop_flag and result_ok and act.any():
             # ---- OptimizationAlgorithmLevenberg::solve(it)
             active_errors(act)
-            if rnd == 0 and it == 0 and not (np.isfinite(state["err"]).all() and np.isfinite(jacobian(pr, pose, idx_all)).all()):
-                res.status = POSE_NONFINITE   # the project's choice: not optimised
-                res.n_inliers, res.share = nInitial, 0.0
-                res.MtMc, res.MtMc_inv = rig_from_min(res.pose, pr.Mc_min)
-                return res
+            first = rnd == 0 and it == 0
+            # the screen of the first evaluation: every edge's residual, Jacobian and weight, the Huber pair (delta, delta^2) ...
+            if first and not (np.isfinite(state["err"]).all() and np.isfinite(jacobian(pr, pose, idx_all)).all() and np.isfinite(omega).all()
+                              and math.isfinite(delta) and math.isfinite(dsqr)):
+                return not_optimised()
             currentChi = active_robust_chi2(act)
             iniChi = currentChi
             e = state["err"][act]
@@ -338,6 +370,9 @@ def _optimize(pr, reverse, fix, guard):
                 for c in range(a, 6):
                     H[a, c] = H[c, a] = ssum(rw * (J[:, 0, a] * J[:, 0, c] + J[:, 1, a] * J[:, 1, c]))
             b = np.array([ssum(-rw * (J[:, 0, a] * e[:, 0] + J[:, 1, a] * e[:, 1])) for a in range(6)])
+            if first and not (np.isfinite(H).all() and np.isfinite(b).all() and math.isfinite(currentChi)):   # ... and the sums it reduces to
+                return not_optimised()
+            res.late_nonfinite[0] += not (np.isfinite(H).all() and np.isfinite(b).all() and math.isfinite(currentChi))
             if it == 0:
                 lam, ni, lm_bad = 1e-5 * float(np.max(np.abs(np.diag(H)))), 2.0, 0
             rho, qmax = 0.0, 0
@@ -346,9 +381,12 @@ def _optimize(pr, reverse, fix, guard):
                 ok2, sol = ldlt6(H + lam * np.eye(6), b)
                 if ok2:
                     x = sol
+                else:
+                    res.failed_solves += 1
                 pose = pose + x                                     # oplus, with the stale x after a failed solve
                 active_errors(act)
                 tempChi = active_robust_chi2(act)
+                res.late_nonfinite[1] += not math.isfinite(tempChi)
                 if not ok2:
                     tempChi = DBL_MAX
                 rho = currentChi - tempChi
@@ -356,10 +394,16 @@ def _optimize(pr, reverse, fix, guard):
                 for j in range(6):
                     scale += x[j] * (lam * x[j] + b[j])
                 scale += 1e-3
+                if not ok2 and not math.isnan(scale):   # the stale x against the new b: scale has either sign, and with tempChi = DBL_MAX it alone decides the trial (DECISION MARGINS)
+                    margins.append(abs(scale) / max(sum(abs(x[j] * (lam * x[j] + b[j])) for j in range(6)) + 1e-3, 1e-300))
                 rho = float(np.float64(rho) / np.float64(scale))                 # IEEE division: inf or NaN where C++ gives them
-                margins.append(abs(currentChi - tempChi) / max(abs(currentChi), abs(tempChi), 1e-300) * 1e3)   # sign of rho: see DECISION MARGINS
+                margins.append(sum_margin(currentChi, tempChi))   # sign of rho: see DECISION MARGINS
                 if rho > 0 and math.isfinite(tempChi):
-                    alpha = 1.0 - (2 * rho - 1) ** 3
+                    res.accepted_failed += not ok2                  # DBL_MAX is finite: a failed solve whose scale is negative is accepted
+                    try:
+                        alpha = 1.0 - (2 * rho - 1) ** 3
+                    except OverflowError:                           # pow() gives the infinity where Python's ** raises
+                        alpha = -math.inf
                     alpha = min(alpha, 2.0 / 3.0)
                     lam *= max(1.0 / 3.0, alpha)
                     ni = 2.0
@@ -399,7 +443,8 @@ def _optimize(pr, reverse, fix, guard):
         # ---- the outlier pass behind this round (:412-427, :433-447)
         c2 = chi2_of(state["err"], omega)
         if rnd == 0:
-            margins.append(float(np.min(np.abs(c2 - th2) / th2)))
+            margins.append(threshold_margin(c2, th2))
+            res.flag_margin = min(res.flag_margin, margins[-1])
             level[c2 > th2] = 1
             nBad = int((c2 > th2).sum())
         else:
@@ -412,7 +457,8 @@ def _optimize(pr, reverse, fix, guard):
                 level[:] = 0
                 nBad = 0
             if live.any():
-                margins.append(float(np.min(np.abs(c2[live] - th2) / th2)))
+                margins.append(threshold_margin(c2[live], th2))
+                res.flag_margin = min(res.flag_margin, margins[-1])
             second = live & (c2 > th2)
             nBad += int(second.sum())
             level[second] = 1
@@ -422,7 +468,7 @@ def _optimize(pr, reverse, fix, guard):
     res.n_inliers = nInitial - nBad
     res.share = (nInitial - nBad) / nInitial if "share_is_inliers" in fix else nBad / nInitial
     res.MtMc, res.MtMc_inv = rig_from_min(pose, pr.Mc_min)
-    res.margin = min(margins) if margins else math.inf
+    res.margin = (0.0 if any(math.isnan(v) for v in margins) else min(margins)) if margins else math.inf   # a NaN distance vouches for nothing
     return res
 
 
@@ -431,6 +477,9 @@ def _optimize(pr, reverse, fix, guard):
 # against iniChi.  A SIGN test (rho > 0, rho < 0, gain >= 0) has no threshold to be relative to: it compares two chi2 sums, and by construction it is taken
 # when they differ by less than 1e-6 of themselves (that is when the gain test fires).  Its margin is the relative difference of the two sums, scaled by 1e3,
 # so that margin >= 1e-6 means they differ by >= 1e-9 of themselves: three orders above the 1e-12 the summation order moves them.
+# After a FAILED solve tempChi is DBL_MAX and the sign of rho is the sign of `scale`, the stale x against the new b, which cancels like any sum: its margin is
+# |scale| relative to the sum of its terms' magnitudes.  (A scale of NaN, lambda = inf against x = 0, decides nothing: rho is NaN on either side.)
+# threshold_margin() is the distance from a chi2 threshold: infinite against an infinite threshold, absolute against a threshold of 0.
 MARGIN = 1e-6
 
 
