@@ -539,11 +539,12 @@ int mcs_create_new_map_points(mcs_ctx*, int nsets, const mcs_kf_geom* kf1, const
  *   min_dist / max_dist   GetMinDistanceInvariance() / GetMaxDistanceInvariance()
  *   flags                 bit0 = isBad(), bit1 = (mnLastFrameSeen == mCurrentFrame.mnId) AFTER the function's first loop (:957-976), which stays with the caller
  * The rig: Get_MtMc_inv(c) / Get_MtMc(c) (4x4 row-major per camera), the camera models (the backward polynomial, width and height are read) and the nr_cams
- * level-0 mirror masks (rows of cams[c].width bytes; the pointer array, or NULL for the bounds test only).
+ * level-0 mirror masks (rows of cams[c].width bytes; the pointer array, or NULL for the bounds test only; a NULL ENTRY is refused by host-kind calls and
+ * means the bounds test only for that camera in device-kind calls).
  * The tracking fields the reference keeps on every map point, [n][nr_cams] each, slot p = i * nr_cams + c:
  *   in_view = mbTrackInView[c], proj_x / proj_y = mTrackProjX / Y[c], level = mnTrackScaleLevel[c], view_cos = mTrackViewCos[c]
- * They are IN/OUT state: the slots of a point whose flags are non-zero are not written (:985-988), a slot that isInFrustum rejects gets in_view = 0 and keeps its
- * other four fields, a slot it accepts gets all five.  Every POINTER lives where the call's `kind` says (matrices, camera models, the mask pointer array and the
+ * They are IN/OUT state: the slots of a point with MCS_LP_BAD or MCS_LP_SEEN set are not written (:985-988; every other bit of flags is
+ * ignored, here and in the search), a slot that isInFrustum rejects gets in_view = 0 and keeps its other four fields, a slot it accepts gets all five.  Every POINTER lives where the call's `kind` says (matrices, camera models, the mask pointer array and the
  * masks too); the structs and their counts are host values. */
 typedef struct {
 	const double* pos; const double* normal; const double* min_dist; const double* max_dist; const uint8_t* flags; int32_t n;
@@ -554,10 +555,10 @@ typedef struct {
 typedef struct {
 	uint8_t* in_view; double* proj_x; double* proj_y; int32_t* level; double* view_cos;
 } mcs_track_state;
-#define MCS_LP_BAD 1    /* mcs_local_points.flags */
+#define MCS_LP_BAD 1    /* mcs_local_points.flags: bits 0 and 1, the other six are ignored */
 #define MCS_LP_SEEN 2
 /* mcs_frustum              bool cMultiFrame::isInFrustum(int cam, cMapPoint*, double viewingCosLimit) (src/cMultiFrame.cpp:218-270) for every camera of every point
- *     whose flags are 0, i.e. the loop :981-999.  visible_inc[i] = cameras point i came into view in (one IncreaseVisible() each, :995), n_to_match = their sum
+ *     with neither MCS_LP_BAD nor MCS_LP_SEEN set, i.e. the loop :981-999.  visible_inc[i] = cameras point i came into view in (one IncreaseVisible() each, :995), n_to_match = their sum
  *     (nToMatch).  scale_factors / nlevels: mvScaleFactors, mnScaleLevels (1 .. MCS_MAX_LEVELS).  As in the reference viewingCosLimit is not applied (:249-250), a
  *     point behind a camera is in view if it projects inside the mask, and NaN distances pass the range test.
  * mcs_search_local_points  the function from :978 on: that loop, then, only if n_to_match > 0 (:1001), cORBmatcher::SearchByProjection(F, mvpLocalMapPoints, th)

@@ -28,8 +28,8 @@ __global__ __launch_bounds__(256) void k_frustum(FrustumArgs a) {
 	bool inView = false;
 	if (live) {
 		if (a.pcam) a.pcam[p] = c;
-		// :985-988: a point seen in this frame or bad is not projected; its slots keep whatever earlier frames left there
-		if (a.flags[i] == 0) {
+		// :985-988: a point seen in this frame or bad is not projected; its slots keep whatever earlier frames left there.  Bits 0 and 1 alone have a meaning
+		if ((a.flags[i] & (MCS_LP_BAD | MCS_LP_SEEN)) == 0) {
 			const double P0 = a.pos[3 * (size_t)i], P1 = a.pos[3 * (size_t)i + 1], P2 = a.pos[3 * (size_t)i + 2];
 			const mcs_ocam& m = a.cams[c];
 			double u, v;
@@ -61,7 +61,7 @@ __global__ __launch_bounds__(256) void k_frustum(FrustumArgs a) {
 __global__ __launch_bounds__(256) void k_frustum_finish(FrustumArgs a) {
 	const int i = blockIdx.x * 256 + threadIdx.x;
 	if (i >= a.npoints) return;
-	const bool search = *a.nToMatch > 0 && !(a.flags[i] & 1);
+	const bool search = *a.nToMatch > 0 && !(a.flags[i] & MCS_LP_BAD);
 	int vis = 0;
 	for (int c = 0; c < a.nrCams; ++c) {
 		const size_t p = (size_t)i * a.nrCams + c;

@@ -117,15 +117,24 @@ MCS_GEOM void omni_world_to_img(const OcamDev& cam, double x, double y, double z
 }
 
 // cCamModelGeneral_::isPointInMirrorMask(u, v, 0) (src/cam_model_omni.cpp:163-178): cvRound, the open bounds test, then the level-0 mask (nullptr: bounds only).
-// The host branch rounds as the oracle's cvRound does ((int)lrint); it serves the CPU test only.
-MCS_GEOM bool in_mirror_mask(double u, double v, int W, int H, const uint8_t* m) {
-#ifdef __HIP_DEVICE_COMPILE__
-	const int ur = __double2int_rn(u), vr = __double2int_rn(v);
-#else
-	const int ur = (int)lrint(u), vr = (int)lrint(v);
-#endif
+// cvRound is cvtsd2si on x86-64: round-half-even, and INT_MIN for a NaN or a rounded value outside int.  The device's conversion saturates instead (NaN -> 0,
+// +-huge -> INT_MAX / INT_MIN); the open bounds test rejects 0, INT_MIN and INT_MAX alike (W <= INT_MAX), so both give the same answer for every double
+// (DESIGN.md section 7).  The host branch states the x86 rule — not (int)lrint, which keeps the low 32 bits of a long and would let 2^32 + 5 in; it serves
+// the CPU tests only.
+MCS_GEOM int cv_round_host(double v) {
+	const double r = nearbyint(v);
+	return (r >= -2147483648.0 && r < 2147483648.0) ? (int)r : (-2147483647 - 1);
+}
+MCS_GEOM bool in_mirror_mask_at(int ur, int vr, int W, int H, const uint8_t* m) {
 	if (ur >= W || ur <= 0 || vr >= H || vr <= 0) return false;
 	return !m || m[(size_t)vr * W + ur] > 0;
+}
+MCS_GEOM bool in_mirror_mask(double u, double v, int W, int H, const uint8_t* m) {
+#ifdef __HIP_DEVICE_COMPILE__
+	return in_mirror_mask_at(__double2int_rn(u), __double2int_rn(v), W, H, m);
+#else
+	return in_mirror_mask_at(cv_round_host(u), cv_round_host(v), W, H, m);
+#endif
 }
 
 // bool cMultiCamSys_::WorldToCamHom_fast(int c, pt, pt2) with M = MtMc_inv[c] (src/cam_system_omni.cpp:92-133, the flagMcMt branch): ptRot = M * pt, WorldToImg,

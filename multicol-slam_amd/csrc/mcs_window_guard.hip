@@ -100,7 +100,7 @@ int guard_local_points_content(const LocalCall& q) {
 	if (int r = check_rig_cameras(rig, nr)) return r;
 	if (q.search())
 		for (int i = 0; i < np; ++i) {
-			if (pts->flags[i] != MCS_LP_SEEN) continue;   // the stale slots SearchByProjection reads
+			if ((pts->flags[i] & (MCS_LP_BAD | MCS_LP_SEEN)) != MCS_LP_SEEN) continue;   // the stale slots SearchByProjection reads (bits 0 and 1 alone count)
 			for (int k = 0; k < nr; ++k)
 				if (stt->in_view[(size_t)i * nr + k] && (stt->level[(size_t)i * nr + k] < 0 || stt->level[(size_t)i * nr + k] >= nlevels)) return bad_level();
 		}

@@ -1420,7 +1420,7 @@ void orc_world_to_cam(const double* MtMc_inv /* nrCams x 16 row-major */, const 
 		double u = 0.0, v = 0.0;
 		orc_world2img(&cams[c], ptRot[0], ptRot[1], ptRot[2], &u, &v);
 		uv[2 * i] = u; uv[2 * i + 1] = v;
-		const int ur = cvRound_(u), vr = cvRound_(v);
+		const int ur = cvRound_x86_(u), vr = cvRound_x86_(v);   // a projection is as large as the caller's geometry makes it: 2^32 + 5 is not pixel 5
 		uint8_t fl = 0;
 		if (!(ur >= cams[c].width || ur <= 0 || vr >= cams[c].height || vr <= 0)) {
 			if (!mirrorMasks || !mirrorMasks[c] || mirrorMasks[c][(size_t)vr * cams[c].width + ur] > 0) fl |= 1;

@@ -22,7 +22,7 @@ class Call:
         ocs = (cap.Ocam * nr)(*[pkg.make_ocam(c) for c in rig["cams"]])
         mp = None
         if rig["masks"] is not None:
-            mp = mem.p(np.array([mem.p(m) for m in rig["masks"]], np.uint64))
+            mp = mem.p(np.array([mem.p(m) or 0 for m in rig["masks"]], np.uint64))     # a None entry is a NULL pointer in the array
         self.rig = cap.RigView(mem.p(np.stack(rig["MtMc_inv"]).reshape(-1)), mem.p(np.stack(rig["MtMc"]).reshape(-1)), mem.p(np.frombuffer(ocs, np.uint8).copy()),
                                mp, nr)
         self.init = dict(in_view=st["in_view"].copy(), proj_x=st["proj_x"].copy(), proj_y=st["proj_y"].copy(), level=st["level"].copy(),
