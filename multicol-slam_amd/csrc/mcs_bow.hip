@@ -3,7 +3,8 @@
 // One lane per feature: the descriptor (32 bytes, what FORB compares) sits in 8 VGPRs, every level reads the <= k child descriptors of the
 // current node (the small vocabulary — 8823 nodes x 32 B — stays in L2) and keeps the first strict minimum, like the reference.
 // Outputs per feature: the leaf node reached and the node of the path at level L - levelsup; word ids, weights and the BowVector /
-// FeatureVector maps are table look-ups and a sort on the host.
+// FeatureVector maps are table look-ups and a sort on the host; mcs_bow_vector builds the BowVector of one multi-frame from the leaf nodes on the device
+// (TemplatedVocabulary.h:1127-1205, BowVector.cpp normalize), from the word table of mcs_vocabulary_set_words (m_nodes[i].word_id / weight).
 #include "mcs_host.h"
 
 namespace mcs {
@@ -43,19 +44,71 @@ __global__ __launch_bounds__(256) void k_bow_transform(BowArgs a) {
 	a.nid[f] = nidv;
 }
 
+// BowVector of one frame from its leaf nodes (TemplatedVocabulary::transform, TF_IDF branch :1147-1163, then BowVector::normalize(L1)).
+// Every addend of a word is that word's one weight, so the value is `count` sequential additions of it; no sort of the features is needed.
+// hist (n_words ints) is zero between calls: the kernel clears what it touched.
+__global__ __launch_bounds__(1024) void k_bow_vector(const int* leaf, int n, int nNodes, int nWords, const int* wordOf, const double* weightOf, int* hist, int* dW,
+                                                     double* dWt, int* outW, double* outV, int* nOut, int* err) {
+	__shared__ int sd;
+	__shared__ double snorm;
+	if (threadIdx.x == 0) sd = 0;
+	__syncthreads();
+	for (int i = threadIdx.x; i < n; i += 1024) {
+		const int nd = leaf[i];
+		if (nd < 0 || nd >= nNodes) { atomicOr(err, 1); continue; }
+		const double w = weightOf[nd];
+		if (!(w > 0)) continue;
+		const int wid = wordOf[nd];
+		if (wid < 0 || wid >= nWords) { atomicOr(err, 2); continue; }
+		if (atomicAdd(&hist[wid], 1) == 0) {
+			const int k = atomicAdd(&sd, 1);
+			dW[k] = wid; dWt[k] = w;
+		}
+	}
+	__syncthreads();
+	const int d = sd;
+	for (int k = threadIdx.x; k < d; k += 1024) {
+		const int wid = dW[k];
+		int r = 0;
+		for (int j = 0; j < d; ++j) r += dW[j] < wid;
+		const double w = dWt[k];
+		double v = w;
+		for (int c = hist[wid]; c > 1; --c) v += w;
+		outW[r] = wid;
+		outV[r] = v;
+	}
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		double norm = 0.0;
+		for (int r = 0; r < d; ++r) norm += fabs(outV[r]);
+		snorm = norm;
+		*nOut = d;
+	}
+	__syncthreads();
+	const double norm = snorm;
+	for (int k = threadIdx.x; k < d; k += 1024) {
+		if (norm > 0.0) outV[k] /= norm;
+		hist[dW[k]] = 0;
+	}
+}
+
 }  // namespace mcs
 
 using namespace mcs;
 
+// Both halves are one buffer each, laid out and filled by the Staging that uploads them (as mcs_sim3_create keeps what it uploads).
 struct mcs_vocabulary {
 	mcs_ctx* ctx = nullptr;
 	int nNodes = 0, L = 0;
-	uint8_t* nodeDesc = nullptr; int* childOff = nullptr; int* childIdx = nullptr;
-	// word id and weight of every node (mcs_vocabulary_set_words) and a zeroed per-word histogram for mcs_bow_vector (mcs_kfdb.hip)
-	int nWords = 0; int* wordOf = nullptr; double* weightOf = nullptr; int* hist = nullptr;
+	DevBuf tree;
+	const uint8_t* nodeDesc = nullptr; const int* childOff = nullptr; const int* childIdx = nullptr;
+	// word id and weight of every node (mcs_vocabulary_set_words) and a zeroed per-word histogram for mcs_bow_vector; wordOf is null until a table is set
+	DevBuf table;
+	int nWords = 0; const int* wordOf = nullptr; const double* weightOf = nullptr; int* hist = nullptr;
 };
 
-int mcs_vocabulary_set_words_internal(mcs_vocabulary* v, const int32_t* word_id_per_node, const double* weight_per_node) {
+int mcs_vocabulary_set_words(mcs_vocabulary* v, const int32_t* word_id_per_node, const double* weight_per_node) {
+	if (!v || !word_id_per_node || !weight_per_node) return fail(MCS_ERR_INVALID, "null argument");
 	int mx = -1;
 	for (int i = 0; i < v->nNodes; ++i) {
 		if (word_id_per_node[i] < -1) return fail(MCS_ERR_INVALID, "word ids must be >= 0 (-1: an inner node)");
@@ -70,22 +123,17 @@ int mcs_vocabulary_set_words_internal(mcs_vocabulary* v, const int32_t* word_id_
 	std::sort(weighted.begin(), weighted.end());
 	if (std::adjacent_find(weighted.begin(), weighted.end()) != weighted.end())
 		return fail(MCS_ERR_INVALID, "two nodes with a weight > 0 carry the same word id (every word has one leaf)");
-	HIPCHK(hipSetDevice(v->ctx->device));
-	(void)hipFree(v->wordOf); (void)hipFree(v->weightOf); (void)hipFree(v->hist);
-	v->wordOf = nullptr; v->weightOf = nullptr; v->hist = nullptr; v->nWords = 0;
+	mcs_ctx* c = v->ctx;
+	HIPCHK(hipSetDevice(c->device));
 	const size_t nn = (size_t)v->nNodes, nw = (size_t)std::max(mx + 1, 1);
-	bool ok = hipMalloc((void**)&v->wordOf, nn * 4) == hipSuccess && hipMalloc((void**)&v->weightOf, nn * 8) == hipSuccess &&
-	          hipMalloc((void**)&v->hist, nw * 4) == hipSuccess;
-	ok = ok && hipMemcpy(v->wordOf, word_id_per_node, nn * 4, hipMemcpyHostToDevice) == hipSuccess &&
-	     hipMemcpy(v->weightOf, weight_per_node, nn * 8, hipMemcpyHostToDevice) == hipSuccess && hipMemset(v->hist, 0, nw * 4) == hipSuccess;
-	if (!ok) return fail(MCS_ERR_HIP, "vocabulary word upload failed");
+	v->wordOf = nullptr; v->nWords = 0;   // from here on the stored table is being replaced: there is none until the new one is complete
+	Staging stg(c, true);
+	stg.upload(&v->wordOf, word_id_per_node, nn * 4); stg.upload(&v->weightOf, weight_per_node, nn * 8); stg.scratch(&v->hist, nw * 4);
+	hipError_t e = v->table.reserve(stg.bytes());
+	if (e == hipSuccess && stg.commit(v->table.p) != MCS_OK) e = hipErrorUnknown;
+	if (e == hipSuccess) e = hipMemsetAsync(v->hist, 0, nw * 4, c->stream);
+	if (stg.finish(e == hipSuccess ? MCS_OK : MCS_ERR_HIP) != MCS_OK) { v->wordOf = nullptr; return fail(MCS_ERR_HIP, "vocabulary word upload failed"); }
 	v->nWords = (int)nw;
-	return MCS_OK;
-}
-
-int mcs_vocabulary_words_internal(mcs_vocabulary* v, mcs_ctx** c, int* nNodes, int** wordOf, double** weightOf, int** hist, int* nWords) {
-	if (!v->wordOf) return fail(MCS_ERR_INVALID, "mcs_bow_vector: call mcs_vocabulary_set_words first");
-	*c = v->ctx; *nNodes = v->nNodes; *wordOf = v->wordOf; *weightOf = v->weightOf; *hist = v->hist; *nWords = v->nWords;
 	return MCS_OK;
 }
 
@@ -103,21 +151,18 @@ int mcs_vocabulary_create(mcs_ctx* c, int n_nodes, const uint8_t* node_desc, con
 	HIPCHK(hipSetDevice(c->device));
 	mcs_vocabulary* v = new mcs_vocabulary();
 	v->ctx = c; v->nNodes = n_nodes; v->L = L;
-	const size_t nidx = (size_t)child_off[n_nodes];
-	bool ok = hipMalloc((void**)&v->nodeDesc, (size_t)n_nodes * 32) == hipSuccess && hipMalloc((void**)&v->childOff, ((size_t)n_nodes + 1) * 4) == hipSuccess &&
-	          hipMalloc((void**)&v->childIdx, std::max<size_t>(nidx, 1) * 4) == hipSuccess;
-	ok = ok && hipMemcpy(v->nodeDesc, node_desc, (size_t)n_nodes * 32, hipMemcpyHostToDevice) == hipSuccess &&
-	     hipMemcpy(v->childOff, child_off, ((size_t)n_nodes + 1) * 4, hipMemcpyHostToDevice) == hipSuccess &&
-	     hipMemcpy(v->childIdx, child_idx, nidx * 4, hipMemcpyHostToDevice) == hipSuccess;
-	if (!ok) { mcs_vocabulary_destroy(v); return fail(MCS_ERR_HIP, "vocabulary upload failed"); }
+	Staging stg(c, true);
+	stg.upload(&v->nodeDesc, node_desc, (size_t)n_nodes * 32); stg.upload(&v->childOff, child_off, ((size_t)n_nodes + 1) * 4);
+	stg.upload(&v->childIdx, child_idx, (size_t)child_off[n_nodes] * 4);
+	const bool ok = v->tree.reserve(stg.bytes()) == hipSuccess && stg.commit(v->tree.p) == MCS_OK;
+	if (stg.finish(ok ? MCS_OK : MCS_ERR_HIP) != MCS_OK) { delete v; return fail(MCS_ERR_HIP, "vocabulary upload failed"); }
 	*out = v;
 	return MCS_OK;
 }
 
 void mcs_vocabulary_destroy(mcs_vocabulary* v) {
 	if (!v) return;
-	(void)hipFree(v->nodeDesc); (void)hipFree(v->childOff); (void)hipFree(v->childIdx);
-	(void)hipFree(v->wordOf); (void)hipFree(v->weightOf); (void)hipFree(v->hist);
+	(void)hipSetDevice(v->ctx->device);
 	delete v;
 }
 
@@ -136,4 +181,37 @@ int mcs_bow_transform(mcs_vocabulary* v, const uint8_t* desc, int n, int stride,
 	const hipError_t e = hipGetLastError();
 	if (e != hipSuccess) return fail(MCS_ERR_HIP, std::string("bow transform: ") + hipGetErrorString(e));
 	return st.finish(MCS_OK);
+}
+
+int mcs_bow_vector(mcs_vocabulary* v, const int32_t* leaf_nodes, int n, mcs_mem_kind kind, int32_t* word_ids_out, double* values_out, int32_t* nwords_out) {
+	if (!v || n < 0 || (n && (!leaf_nodes || !word_ids_out || !values_out)) || !nwords_out) return fail(MCS_ERR_INVALID, "null argument");
+	if (!v->wordOf) return fail(MCS_ERR_INVALID, "mcs_bow_vector: call mcs_vocabulary_set_words first");
+	mcs_ctx* c = v->ctx;
+	HIPCHK(hipSetDevice(c->device));
+	hipStream_t st = c->stream;
+	const bool host = kind == MCS_MEM_HOST;
+	const size_t nn = std::max(n, 1);
+	// host kind: the outputs hold nwords_out entries, known only after the kernel, so they are fetched below from the block (intact until the next call)
+	const int* dLeaf = nullptr; int *dW = nullptr, *outW = nullptr, *nOut = nullptr, *dErr = nullptr; double *dWt = nullptr, *outV = nullptr;
+	int errv = 0, d = 0;
+	Staging stg(c, host);
+	stg.in(&dLeaf, leaf_nodes, (size_t)n * 4); stg.scratch(&dW, nn * 4); stg.scratch(&dWt, nn * 8); stg.download(&dErr, &errv, 4);
+	if (host) { stg.scratch(&outW, nn * 4); stg.scratch(&outV, nn * 8); stg.download(&nOut, &d, 4); }
+	else { outW = word_ids_out; outV = values_out; nOut = nwords_out; }
+	if (int r = stg.commit()) return r;
+	HIPCHK(hipMemsetAsync(dErr, 0, 4, st));
+	hipLaunchKernelGGL(k_bow_vector, dim3(1), dim3(1024), 0, st, dLeaf, n, v->nNodes, v->nWords, v->wordOf, v->weightOf, v->hist, dW, dWt, outW, outV, nOut, dErr);
+	HIPCHK(hipGetLastError());
+	if (int r = stg.finish(MCS_OK)) return r;
+	if (errv & 1) return fail(MCS_ERR_INVALID, "mcs_bow_vector: leaf node id out of range");
+	if (errv & 2) return fail(MCS_ERR_INVALID, "mcs_bow_vector: a node with a weight > 0 has no word id (not a leaf)");
+	if (host) {
+		*nwords_out = d;
+		if (d) {
+			HIPCHK(hipMemcpyAsync(word_ids_out, outW, (size_t)d * 4, hipMemcpyDeviceToHost, st));
+			HIPCHK(hipMemcpyAsync(values_out, outV, (size_t)d * 8, hipMemcpyDeviceToHost, st));
+			HIPCHK(hipStreamSynchronize(st));
+		}
+	}
+	return MCS_OK;
 }

@@ -374,14 +374,13 @@ int mcs_selftest_shared_reciprocal(mcs_ctx* c, uint64_t seed, int n, int32_t* mi
 	if (!c || !mismatches || n < 1) return fail(MCS_ERR_INVALID, "bad argument");
 	HIPCHK(hipSetDevice(c->device));
 	int* d = nullptr;
-	HIPCHK(hipMalloc((void**)&d, 4));
+	Staging st(c, true);
+	st.download(&d, mismatches, 4);
+	if (int r = st.commit()) return r;
 	(void)hipMemsetAsync(d, 0, 4, c->stream);
 	launch_selftest_recip(seed, n, d, c->stream);
-	const hipError_t e1 = hipGetLastError();
-	const hipError_t e2 = hipMemcpyAsync(mismatches, d, 4, hipMemcpyDeviceToHost, c->stream);
-	const hipError_t e3 = hipStreamSynchronize(c->stream);
-	(void)hipFree(d);
-	if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return fail(MCS_ERR_HIP, "selftest kernel failed");
+	const bool launched = hipGetLastError() == hipSuccess;
+	if (st.finish(launched ? MCS_OK : MCS_ERR_HIP) != MCS_OK) return fail(MCS_ERR_HIP, "selftest kernel failed");
 	return MCS_OK;
 }
 

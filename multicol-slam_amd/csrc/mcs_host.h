@@ -37,6 +37,8 @@ inline void* device_view(const void* host) {
 
 // Grow-only device buffer: at least `bytes` long after reserve(), contents lost when it grows.  Growing goes through hipFree, which waits for the device, so
 // nothing still reads the old allocation.  Freed with its owner (context, extractor, keyframe database), whose destroy call has set the device (mcs_ctx_destroy does before `delete c`: keep it that way).
+// grow_keep() is the growth that keeps the contents, for a store whose owner sets the capacity schedule itself: exactly `bytes` long afterwards (no slack),
+// the first `keep` bytes (<= cap) copied over and the rest zero, both on stream `s` and complete on return.  A failure leaves the buffer as it was.
 struct DevBuf {
 	uint8_t* p = nullptr; size_t cap = 0;
 	DevBuf() = default;
@@ -51,6 +53,19 @@ struct DevBuf {
 		const hipError_t e = hipMalloc((void**)&p, want);
 		if (e == hipSuccess) cap = want;
 		return e;
+	}
+	hipError_t grow_keep(size_t bytes, size_t keep, hipStream_t s) {
+		if (cap >= bytes) return hipSuccess;
+		uint8_t* np = nullptr;
+		hipError_t e = hipMalloc((void**)&np, bytes);
+		if (e != hipSuccess) return e;
+		if (keep) e = hipMemcpyAsync(np, p, keep, hipMemcpyDeviceToDevice, s);
+		if (e == hipSuccess) e = hipMemsetAsync(np + keep, 0, bytes - keep, s);
+		if (e == hipSuccess) e = hipStreamSynchronize(s);
+		if (e != hipSuccess) { (void)hipFree(np); return e; }
+		if (p) (void)hipFree(p);
+		p = np; cap = bytes;
+		return hipSuccess;
 	}
 	template <class T> T* as() const { return (T*)p; }
 };

@@ -1,5 +1,5 @@
-// mcs_kfdb.hip — cMultiKeyFrameDatabase (src/cMultiKeyFrameDatabase.cpp) on the device, and the BowVector of one multi-frame from the leaf
-// nodes of mcs_bow_transform (ThirdParty/DBoW2/DBoW2/TemplatedVocabulary.h:1127-1205, BowVector.cpp normalize).
+// mcs_kfdb.hip — cMultiKeyFrameDatabase (src/cMultiKeyFrameDatabase.cpp) on the device.  (The BowVector of a multi-frame, mcs_bow_vector, is in
+// mcs_bow.hip with the vocabulary it reads.)
 //
 // The inverted file is not kept as lists: a keyframe is a row of its BowVector (ascending word ids, L1-normalised doubles) in a growable slab,
 // with a slot, its mnId, an add sequence number (re-set on re-add) and its persistent query state.  The list order of the reference
@@ -16,6 +16,11 @@
 //               persistent one — trap (a))
 //   k_final     one workgroup per query: covisibility accumulation, list order, 0.75 * bestAccScore retention, dedup, outputs
 // The new persistent state is written to the second copy of the state arrays and becomes current only when the whole call succeeds.
+//
+// Memory: the slab, the state arrays and the metadata are DevBufs of the database; the arrays of one call are a Staging on the context's block.  Slab and
+// state grow with DevBuf::grow_keep to exactly the size of their schedule (slab max(need, 2 * capacity, 64) elements, state max(2 * slots, 256) slots): the
+// hostile scripts count on WHICH call reallocates.  Every copy and fill is on the context's stream, like the kernels, and every call ends behind a
+// synchronisation of it.
 #include "mcs_host.h"
 #include <unordered_map>
 
@@ -301,88 +306,28 @@ __global__ __launch_bounds__(256) void k_score_list(const int* qw, const double*
 	out[i] = l1_score(qw, qv, nqw, words + rowOff[s], vals + rowOff[s], rowLen[s]);
 }
 
-// BowVector of one frame from its leaf nodes (TemplatedVocabulary::transform, TF_IDF branch :1147-1163, then BowVector::normalize(L1)).
-// Every addend of a word is that word's one weight, so the value is `count` sequential additions of it; no sort of the features is needed.
-// hist (n_words ints) is zero between calls: the kernel clears what it touched.
-__global__ __launch_bounds__(1024) void k_bow_vector(const int* leaf, int n, int nNodes, int nWords, const int* wordOf, const double* weightOf, int* hist, int* dW,
-                                                     double* dWt, int* outW, double* outV, int* nOut, int* err) {
-	__shared__ int sd;
-	__shared__ double snorm;
-	if (threadIdx.x == 0) sd = 0;
-	__syncthreads();
-	for (int i = threadIdx.x; i < n; i += 1024) {
-		const int nd = leaf[i];
-		if (nd < 0 || nd >= nNodes) { atomicOr(err, 1); continue; }
-		const double w = weightOf[nd];
-		if (!(w > 0)) continue;
-		const int wid = wordOf[nd];
-		if (wid < 0 || wid >= nWords) { atomicOr(err, 2); continue; }
-		if (atomicAdd(&hist[wid], 1) == 0) {
-			const int k = atomicAdd(&sd, 1);
-			dW[k] = wid; dWt[k] = w;
-		}
-	}
-	__syncthreads();
-	const int d = sd;
-	for (int k = threadIdx.x; k < d; k += 1024) {
-		const int wid = dW[k];
-		int r = 0;
-		for (int j = 0; j < d; ++j) r += dW[j] < wid;
-		const double w = dWt[k];
-		double v = w;
-		for (int c = hist[wid]; c > 1; --c) v += w;
-		outW[r] = wid;
-		outV[r] = v;
-	}
-	__syncthreads();
-	if (threadIdx.x == 0) {
-		double norm = 0.0;
-		for (int r = 0; r < d; ++r) norm += fabs(outV[r]);
-		snorm = norm;
-		*nOut = d;
-	}
-	__syncthreads();
-	const double norm = snorm;
-	for (int k = threadIdx.x; k < d; k += 1024) {
-		if (norm > 0.0) outV[k] /= norm;
-		hist[dW[k]] = 0;
-	}
-}
-
 }  // namespace mcs
 
 using namespace mcs;
 
-// ------------------------------------------------------------------ vocabulary words (the node table of TemplatedVocabulary: m_nodes[i].word_id / weight)
-
-struct mcs_vocabulary;
-int mcs_vocabulary_words_internal(mcs_vocabulary* v, mcs_ctx** c, int* nNodes, int** wordOf, double** weightOf, int** hist, int* nWords);
-int mcs_vocabulary_set_words_internal(mcs_vocabulary* v, const int32_t* word_id_per_node, const double* weight_per_node);
-
 namespace {
 
+// copy n elements of a caller array (host or device) into a host vector; the device branch goes on the context's stream and waits for it
 template <class T>
-hipError_t grow(T** p, size_t& cap, size_t need, size_t keep) {
-	if (need <= cap) return hipSuccess;
-	size_t nc = std::max<size_t>(need, cap * 2);
-	nc = std::max<size_t>(nc, 64);
-	T* np = nullptr;
-	hipError_t e = hipMalloc((void**)&np, nc * sizeof(T));
-	if (e != hipSuccess) return e;
-	if (*p && keep) e = hipMemcpy(np, *p, keep * sizeof(T), hipMemcpyDeviceToDevice);
-	if (*p) (void)hipFree(*p);
-	*p = np;
-	cap = nc;
-	return e;
-}
-
-// copy `bytes` of a caller array (host or device) into a host vector
-template <class T>
-hipError_t fetch(std::vector<T>& dst, const T* src, size_t n, mcs_mem_kind kind) {
+hipError_t fetch(std::vector<T>& dst, const T* src, size_t n, mcs_mem_kind kind, hipStream_t st) {
 	dst.resize(n);
 	if (!n) return hipSuccess;
 	if (kind == MCS_MEM_HOST) { memcpy(dst.data(), src, n * sizeof(T)); return hipSuccess; }
-	return hipMemcpy(dst.data(), src, n * sizeof(T), hipMemcpyDeviceToHost);
+	const hipError_t e = hipMemcpyAsync(dst.data(), src, n * sizeof(T), hipMemcpyDeviceToHost, st);
+	return e != hipSuccess ? e : hipStreamSynchronize(st);
+}
+
+// one output array of a detection call: `bytes` to the caller's array (host or device memory, by `host`) from a host vector (`fromHost`) or from a slot of the
+// call's scratch.  Issued on the context's stream: the caller synchronises once, behind the last one.
+hipError_t put(void* dst, const void* src, bool fromHost, size_t bytes, bool host, hipStream_t st) {
+	if (!bytes) return hipSuccess;
+	if (host && fromHost) { memcpy(dst, src, bytes); return hipSuccess; }
+	return hipMemcpyAsync(dst, src, bytes, host ? hipMemcpyDeviceToHost : fromHost ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st);
 }
 
 }  // namespace
@@ -397,20 +342,18 @@ struct mcs_kfdb {
 	std::vector<uint32_t> addSeq;
 	uint32_t seq = 0;
 	bool metaDirty = true;
-	size_t slabUsed = 0, slabCap = 0, slabValsCap = 0;
-	int* words = nullptr; double* vals = nullptr;
-	// device copies of the slot metadata
-	size_t slotCap = 0, c1 = 0, c2 = 0, c3 = 0, c4 = 0, c5 = 0, c6 = 0;
-	int* dRowOff = nullptr; int* dRowLen = nullptr; int* dActive = nullptr; int* dCovisN = nullptr; int* dCovis = nullptr; uint32_t* dAddSeq = nullptr;
-	int64_t* dId = nullptr;
-	// persistent state, two copies each (current / next): [0] relocalisation, [1] loop
+	// the slab of rows: slabCap elements each, capacity max(need, 2 * slabCap, 64) when a row does not fit
+	size_t slabUsed = 0, slabCap = 0;
+	DevBuf words, vals;   // int / double
+	// device copy of the slot metadata: one buffer, laid out and uploaded whole by kfdb_sync
+	DevBuf meta;
+	const int *dRowOff = nullptr, *dRowLen = nullptr, *dActive = nullptr, *dCovisN = nullptr, *dCovis = nullptr;
+	const uint32_t* dAddSeq = nullptr; const int64_t* dId = nullptr;
+	// persistent state, two copies each (current / next): [0] relocalisation, [1] loop; stCap slots each, capacity max(2 * slots, 256) when a slot does not fit
+	struct State { DevBuf q, w, s; };   // int64_t query id, int word counter, double score
 	int cur[2] = {0, 0};
-	int64_t* stQ[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-	int* stW[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-	double* stS[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+	State st[2][2];
 	size_t stCap = 0;
-	// scratch of one batch
-	DevBuf scratch;
 };
 
 static int kfdb_slot(mcs_kfdb* db, int64_t kid) {
@@ -426,39 +369,38 @@ static int kfdb_slot(mcs_kfdb* db, int64_t kid) {
 	return s;
 }
 
-// device metadata and state arrays sized for every slot; new slots get the state of a keyframe never queried (query ids 0, counters 0, scores 0.0)
+// room for `need` slab elements; the rows in use are kept
+static hipError_t kfdb_slab(mcs_kfdb* db, size_t need) {
+	if (need <= db->slabCap) return hipSuccess;
+	const size_t nc = std::max<size_t>(std::max(need, db->slabCap * 2), 64);
+	hipError_t e = db->words.grow_keep(nc * 4, db->slabUsed * 4, db->ctx->stream);
+	if (e == hipSuccess) e = db->vals.grow_keep(nc * 8, db->slabUsed * 8, db->ctx->stream);
+	if (e == hipSuccess) db->slabCap = nc;
+	return e;
+}
+
+// device metadata and state arrays sized for every slot; new slots get the state of a keyframe never queried (query ids 0, counters 0, scores 0.0): the zero
+// fill of grow_keep.  A growth that fails half way leaves stCap as it was, and the next call grows the arrays that are still short.
 static int kfdb_sync(mcs_kfdb* db) {
 	const size_t S = db->id.size();
+	mcs_ctx* c = db->ctx;
 	if (S > db->stCap) {
-		const size_t nc = std::max<size_t>(S * 2, 256);
+		const size_t nc = std::max<size_t>(S * 2, 256), old = db->stCap;
 		for (int m = 0; m < 2; ++m)
 			for (int b = 0; b < 2; ++b) {
-				int64_t* q = nullptr; int* w = nullptr; double* s = nullptr;
-				HIPCHK(hipMalloc((void**)&q, nc * 8)); HIPCHK(hipMalloc((void**)&w, nc * 4)); HIPCHK(hipMalloc((void**)&s, nc * 8));
-				HIPCHK(hipMemset(q, 0, nc * 8)); HIPCHK(hipMemset(w, 0, nc * 4)); HIPCHK(hipMemset(s, 0, nc * 8));
-				if (db->stQ[m][b] && db->stCap) {
-					HIPCHK(hipMemcpy(q, db->stQ[m][b], db->stCap * 8, hipMemcpyDeviceToDevice));
-					HIPCHK(hipMemcpy(w, db->stW[m][b], db->stCap * 4, hipMemcpyDeviceToDevice));
-					HIPCHK(hipMemcpy(s, db->stS[m][b], db->stCap * 8, hipMemcpyDeviceToDevice));
-				}
-				(void)hipFree(db->stQ[m][b]); (void)hipFree(db->stW[m][b]); (void)hipFree(db->stS[m][b]);
-				db->stQ[m][b] = q; db->stW[m][b] = w; db->stS[m][b] = s;
+				mcs_kfdb::State& x = db->st[m][b];
+				HIPCHK(x.q.grow_keep(nc * 8, old * 8, c->stream)); HIPCHK(x.w.grow_keep(nc * 4, old * 4, c->stream)); HIPCHK(x.s.grow_keep(nc * 8, old * 8, c->stream));
 			}
 		db->stCap = nc;
 	}
 	if (!db->metaDirty) return MCS_OK;
-	HIPCHK(grow(&db->dRowOff, db->c1, S, 0)); HIPCHK(grow(&db->dRowLen, db->c2, S, 0)); HIPCHK(grow(&db->dActive, db->c3, S, 0));
-	HIPCHK(grow(&db->dCovisN, db->c4, S, 0)); HIPCHK(grow(&db->dCovis, db->c5, S * KF_COVIS, 0)); HIPCHK(grow(&db->dAddSeq, db->slotCap, S, 0));
-	HIPCHK(grow(&db->dId, db->c6, S, 0));
-	if (S) {
-		HIPCHK(hipMemcpy(db->dRowOff, db->rowOff.data(), S * 4, hipMemcpyHostToDevice));
-		HIPCHK(hipMemcpy(db->dRowLen, db->rowLen.data(), S * 4, hipMemcpyHostToDevice));
-		HIPCHK(hipMemcpy(db->dActive, db->active.data(), S * 4, hipMemcpyHostToDevice));
-		HIPCHK(hipMemcpy(db->dCovisN, db->covisN.data(), S * 4, hipMemcpyHostToDevice));
-		HIPCHK(hipMemcpy(db->dCovis, db->covis.data(), S * KF_COVIS * 4, hipMemcpyHostToDevice));
-		HIPCHK(hipMemcpy(db->dAddSeq, db->addSeq.data(), S * 4, hipMemcpyHostToDevice));
-		HIPCHK(hipMemcpy(db->dId, db->id.data(), S * 8, hipMemcpyHostToDevice));
-	}
+	Staging stg(c, true);
+	stg.upload(&db->dRowOff, db->rowOff.data(), S * 4); stg.upload(&db->dRowLen, db->rowLen.data(), S * 4); stg.upload(&db->dActive, db->active.data(), S * 4);
+	stg.upload(&db->dCovisN, db->covisN.data(), S * 4); stg.upload(&db->dCovis, db->covis.data(), S * KF_COVIS * 4); stg.upload(&db->dAddSeq, db->addSeq.data(), S * 4);
+	stg.upload(&db->dId, db->id.data(), S * 8);
+	HIPCHK(db->meta.reserve(stg.bytes()));
+	if (int r = stg.commit(db->meta.p)) return r;
+	if (int r = stg.finish(MCS_OK)) return r;
 	db->metaDirty = false;
 	return MCS_OK;
 }
@@ -471,9 +413,7 @@ int mcs_kfdb_create(mcs_ctx* c, int n_words, int capacity_hint, mcs_kfdb** out) 
 	db->ctx = c; db->nWords = n_words; db->bmWords = (n_words + 31) / 32;
 	if (capacity_hint > 0) {
 		db->id.reserve(capacity_hint);
-		const hipError_t e = grow(&db->words, db->slabCap, (size_t)capacity_hint * 1024, 0);
-		const hipError_t e2 = e == hipSuccess ? grow(&db->vals, db->slabValsCap, (size_t)capacity_hint * 1024, 0) : e;
-		if (e2 != hipSuccess) { mcs_kfdb_destroy(db); return fail(MCS_ERR_HIP, "keyframe database allocation failed"); }
+		if (kfdb_slab(db, (size_t)capacity_hint * 1024) != hipSuccess) { delete db; return fail(MCS_ERR_HIP, "keyframe database allocation failed"); }
 	}
 	*out = db;
 	return MCS_OK;
@@ -482,11 +422,7 @@ int mcs_kfdb_create(mcs_ctx* c, int n_words, int capacity_hint, mcs_kfdb** out) 
 int mcs_kfdb_destroy(mcs_kfdb* db) {
 	if (!db) return MCS_OK;
 	(void)hipSetDevice(db->ctx->device);
-	(void)hipFree(db->words); (void)hipFree(db->vals);
-	(void)hipFree(db->dRowOff); (void)hipFree(db->dRowLen); (void)hipFree(db->dActive); (void)hipFree(db->dCovisN); (void)hipFree(db->dCovis);
-	(void)hipFree(db->dAddSeq); (void)hipFree(db->dId);
-	for (int m = 0; m < 2; ++m)
-		for (int b = 0; b < 2; ++b) { (void)hipFree(db->stQ[m][b]); (void)hipFree(db->stW[m][b]); (void)hipFree(db->stS[m][b]); }
+	(void)hipStreamSynchronize(db->ctx->stream);
 	delete db;
 	return MCS_OK;
 }
@@ -511,14 +447,15 @@ int mcs_kfdb_add(mcs_kfdb* db, int nkf, const int64_t* kf_ids, const int32_t* of
 	if (!db || nkf < 0 || (nkf && (!kf_ids || !offsets))) return fail(MCS_ERR_INVALID, "null argument");
 	if (nkf == 0) return MCS_OK;
 	HIPCHK(hipSetDevice(db->ctx->device));
+	hipStream_t st = db->ctx->stream;
 	std::vector<int64_t> ids;
 	std::vector<int> off, w;
-	HIPCHK(fetch(ids, kf_ids, nkf, kind));
-	HIPCHK(fetch(off, offsets, (size_t)nkf + 1, kind));
+	HIPCHK(fetch(ids, kf_ids, nkf, kind, st));
+	HIPCHK(fetch(off, offsets, (size_t)nkf + 1, kind, st));
 	if (int r = guard_bow_offsets(off.data(), nkf, "mcs_kfdb_add")) return r;   // before anything is sized by them
 	const size_t total = (size_t)off[nkf];
 	if (total && (!word_ids || !values)) return fail(MCS_ERR_INVALID, "null word / value array");
-	HIPCHK(fetch(w, word_ids, total, kind));
+	HIPCHK(fetch(w, word_ids, total, kind, st));
 	if (int r = guard_bow_words(off.data(), nkf, w.data(), db->nWords, "mcs_kfdb_add")) return r;
 	for (int i = 0; i < nkf; ++i) {
 		auto it = db->slotOf.find(ids[i]);
@@ -529,12 +466,11 @@ int mcs_kfdb_add(mcs_kfdb* db, int nkf, const int64_t* kf_ids, const int32_t* of
 	}
 	if (db->seq + (uint64_t)nkf >= 0xFFFFFFFFull) return fail(MCS_ERR_CAPACITY, "mcs_kfdb_add: add sequence exhausted (clear the database)");
 	const size_t base = db->slabUsed;
-	HIPCHK(grow(&db->words, db->slabCap, base + total, base));
-	HIPCHK(grow(&db->vals, db->slabValsCap, base + total, base));
-	const hipMemcpyKind mk = kind == MCS_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+	HIPCHK(kfdb_slab(db, base + total));
 	if (total) {
-		HIPCHK(hipMemcpy(db->words + base, w.data(), total * 4, hipMemcpyHostToDevice));
-		HIPCHK(hipMemcpy(db->vals + base, values, total * 8, mk));
+		HIPCHK(hipMemcpyAsync(db->words.as<int>() + base, w.data(), total * 4, hipMemcpyHostToDevice, st));
+		HIPCHK(hipMemcpyAsync(db->vals.as<double>() + base, values, total * 8, kind == MCS_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
+		HIPCHK(hipStreamSynchronize(st));   // w and the caller's values are free again
 	}
 	db->slabUsed = base + total;
 	for (int i = 0; i < nkf; ++i) {
@@ -589,12 +525,10 @@ static int kfdb_detect(mcs_kfdb* db, int loop, int nq, const int64_t* query_ids,
 	hipStream_t st = c->stream;
 	const bool host = kind == MCS_MEM_HOST;
 	std::vector<int> off;
-	HIPCHK(fetch(off, offsets, (size_t)nq + 1, kind));
+	HIPCHK(fetch(off, offsets, (size_t)nq + 1, kind, st));
 	if (int r = guard_bow_offsets(off.data(), nq, nullptr)) return r;
 	const size_t total = (size_t)off[nq];
 	if (total && (!word_ids || !values)) return fail(MCS_ERR_INVALID, "null word / value array");
-	std::vector<int64_t> qid;
-	HIPCHK(fetch(qid, query_ids, nq, kind));
 	if (host)
 		if (int r = guard_bow_words(off.data(), nq, word_ids, db->nWords, loop ? "mcs_kfdb_detect_loop" : "mcs_kfdb_detect_relocalisation")) return r;
 	int rc = kfdb_sync(db);
@@ -604,12 +538,12 @@ static int kfdb_detect(mcs_kfdb* db, int loop, int nq, const int64_t* query_ids,
 	if (loop && conn_offsets) {
 		std::vector<int> coff;
 		std::vector<int64_t> cids;
-		HIPCHK(fetch(coff, conn_offsets, (size_t)nq + 1, kind));
+		HIPCHK(fetch(coff, conn_offsets, (size_t)nq + 1, kind, st));
 		if (coff[0] != 0) return fail(MCS_ERR_INVALID, "connected offsets[0] must be 0");
 		for (int q = 0; q < nq; ++q)
 			if (coff[q + 1] < coff[q]) return fail(MCS_ERR_INVALID, "connected offsets must be non-decreasing");
 		if (coff[nq] && !conn_ids) return fail(MCS_ERR_INVALID, "null connected ids");
-		HIPCHK(fetch(cids, conn_ids, (size_t)coff[nq], kind));
+		HIPCHK(fetch(cids, conn_ids, (size_t)coff[nq], kind, st));
 		conn.assign((size_t)nq * std::max(S, 1), 0);
 		for (int q = 0; q < nq; ++q)
 			for (int k = coff[q]; k < coff[q + 1]; ++k) {
@@ -617,93 +551,76 @@ static int kfdb_detect(mcs_kfdb* db, int loop, int nq, const int64_t* query_ids,
 				if (it != db->slotOf.end()) conn[(size_t)q * S + it->second] = 1;
 			}
 	}
+	const size_t nq4 = (size_t)nq * 4;
 	if (S == 0) {   // empty database: nothing shares a word
-		std::vector<int> z(nq, 0);
-		if (host) memcpy(cand_count, z.data(), nq * 4); else HIPCHK(hipMemcpy(cand_count, z.data(), nq * 4, hipMemcpyHostToDevice));
-		if (diag && diag->count) { if (host) memcpy(diag->count, z.data(), nq * 4); else HIPCHK(hipMemcpy(diag->count, z.data(), nq * 4, hipMemcpyHostToDevice)); }
+		const std::vector<int> z(nq, 0);
+		HIPCHK(put(cand_count, z.data(), true, nq4, host, st));
+		if (diag && diag->count) HIPCHK(put(diag->count, z.data(), true, nq4, host, st));
+		HIPCHK(hipStreamSynchronize(st));
 		return MCS_OK;
 	}
 	const int dcap = diag ? std::max(diag->cap, 0) : 0;
-	const size_t NS = (size_t)nq * S;
-	// scratch layout
-	uint32_t* bm = nullptr; int* err = nullptr; int* qOff = nullptr; int64_t* xQId = nullptr; double* xMinS = nullptr; int* xMinC = nullptr; int* xNApp = nullptr;
-	int* xCnt = nullptr; int* xMinw = nullptr; int* xWA = nullptr; uint8_t* xFl = nullptr; double* xSc = nullptr; uint8_t* xConn = nullptr; int* xLSlot = nullptr;
-	uint64_t* xLKey = nullptr; double* xLAcc = nullptr; int* xLBest = nullptr; int* xLOrd = nullptr; uint8_t* xSeen = nullptr; int* xCandN = nullptr;
-	int64_t* xCand = nullptr; int* xDN = nullptr; int64_t* xDId = nullptr; int* xDW = nullptr; double* xDS = nullptr; double* xDA = nullptr; int64_t* xDB = nullptr;
-	int* xQW = nullptr; double* xQV = nullptr;
-	const size_t QC = (size_t)nq * std::max(cap, 1), QD = (size_t)nq * std::max(dcap, 1);
-	Layout lay;
-	lay.piece(&bm, (size_t)nq * db->bmWords * 4); lay.piece(&err, 4); lay.piece(&qOff, ((size_t)nq + 1) * 4); lay.piece(&xQId, (size_t)nq * 8);
-	lay.piece(&xMinS, (size_t)nq * 8); lay.piece(&xMinC, (size_t)nq * 4); lay.piece(&xNApp, (size_t)nq * 4); lay.piece(&xCnt, NS * 4); lay.piece(&xMinw, NS * 4);
-	lay.piece(&xWA, NS * 4); lay.piece(&xFl, NS); lay.piece(&xSc, NS * 8); lay.piece(&xConn, loop ? NS : 1); lay.piece(&xLSlot, NS * 4); lay.piece(&xLKey, NS * 8);
-	lay.piece(&xLAcc, NS * 8); lay.piece(&xLBest, NS * 4); lay.piece(&xLOrd, NS * 4); lay.piece(&xSeen, NS); lay.piece(&xCandN, (size_t)nq * 4);
-	lay.piece(&xCand, QC * 8); lay.piece(&xDN, (size_t)nq * 4); lay.piece(&xDId, QD * 8); lay.piece(&xDW, QD * 4); lay.piece(&xDS, QD * 8); lay.piece(&xDA, QD * 8);
-	lay.piece(&xDB, QD * 8); lay.piece(&xQW, host ? total * 4 : 8); lay.piece(&xQV, host ? total * 8 : 8);
-	HIPCHK(db->scratch.reserve(lay.total));
-	lay.place(db->scratch.p);
-	const int* dQWords = host ? xQW : word_ids;
-	const double* dQVals = host ? xQV : values;
-	HIPCHK(hipMemcpyAsync(qOff, off.data(), ((size_t)nq + 1) * 4, hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemcpyAsync(xQId, qid.data(), (size_t)nq * 8, hipMemcpyHostToDevice, st));
-	if (loop) {
-		std::vector<double> ms;
-		HIPCHK(fetch(ms, min_scores, nq, kind));
-		HIPCHK(hipMemcpyAsync(xMinS, ms.data(), (size_t)nq * 8, hipMemcpyHostToDevice, st));
-		if (conn.empty()) HIPCHK(hipMemsetAsync(xConn, 0, NS, st));
-		else HIPCHK(hipMemcpyAsync(xConn, conn.data(), NS, hipMemcpyHostToDevice, st));
-	}
-	if (host && total) {
-		HIPCHK(hipMemcpyAsync(xQW, word_ids, total * 4, hipMemcpyHostToDevice, st));
-		HIPCHK(hipMemcpyAsync(xQV, values, total * 8, hipMemcpyHostToDevice, st));
-	}
+	const size_t NS = (size_t)nq * S, QC = (size_t)nq * std::max(cap, 1), QD = (size_t)nq * std::max(dcap, 1);
+	// the call's arrays and scratch in the context's block: the connected matrix, made on the host, is uploaded; the caller's arrays are staged (host kind) or
+	// read where they are (device kind: nothing goes to the host and back but the offsets, which size the call); the rest is scratch.  Candidates and
+	// diagnostics land in scratch too: they reach the caller only when the query words are found good.
+	uint32_t* bm = nullptr; int* xRes = nullptr; const int* qOff = nullptr; const int64_t* xQId = nullptr; const double* xMinS = nullptr; int* xMinC = nullptr;
+	int* xNApp = nullptr; int* xCnt = nullptr; int* xMinw = nullptr; int* xWA = nullptr; uint8_t* xFl = nullptr; double* xSc = nullptr; uint8_t* xConn = nullptr;
+	int* xLSlot = nullptr; uint64_t* xLKey = nullptr; double* xLAcc = nullptr; int* xLBest = nullptr; int* xLOrd = nullptr; uint8_t* xSeen = nullptr;
+	int64_t* xCand = nullptr; int64_t* xDId = nullptr; int* xDW = nullptr; double* xDS = nullptr; double* xDA = nullptr;
+	int64_t* xDB = nullptr; const int* dQWords = nullptr; const double* dQVals = nullptr;
+	std::vector<int> res(2 * (size_t)nq + 1);   // what the host needs back, as one piece and one copy: candidate counts, diagnostic counts, the error word
+	const int *candN = res.data(), *dN = candN + nq, &errv = res[2 * (size_t)nq];
+	Staging stg(c, host);
+	stg.upload(&xConn, conn.data(), loop ? NS : 1); stg.in(&qOff, offsets, ((size_t)nq + 1) * 4); stg.in(&xQId, query_ids, (size_t)nq * 8);
+	stg.in(&xMinS, min_scores, (size_t)nq * 8); stg.in(&dQWords, word_ids, total * 4); stg.in(&dQVals, values, total * 8);
+	stg.scratch(&bm, (size_t)nq * db->bmWords * 4); stg.scratch(&xMinC, nq4); stg.scratch(&xNApp, nq4); stg.scratch(&xCnt, NS * 4); stg.scratch(&xMinw, NS * 4);
+	stg.scratch(&xWA, NS * 4); stg.scratch(&xFl, NS); stg.scratch(&xSc, NS * 8); stg.scratch(&xLSlot, NS * 4); stg.scratch(&xLKey, NS * 8); stg.scratch(&xLAcc, NS * 8);
+	stg.scratch(&xLBest, NS * 4); stg.scratch(&xLOrd, NS * 4); stg.scratch(&xSeen, NS); stg.scratch(&xCand, QC * 8); stg.scratch(&xDId, QD * 8);
+	stg.scratch(&xDW, QD * 4); stg.scratch(&xDS, QD * 8); stg.scratch(&xDA, QD * 8); stg.scratch(&xDB, QD * 8);
+	stg.download(&xRes, res.data(), res.size() * 4);
+	if (int r = stg.commit()) return r;
+	int *xCandN = xRes, *xDN = xRes + nq, *err = xRes + 2 * (size_t)nq;
+	if (loop && conn.empty()) HIPCHK(hipMemsetAsync(xConn, 0, NS, st));
 	HIPCHK(hipMemsetAsync(bm, 0, (size_t)nq * db->bmWords * 4, st));
 	HIPCHK(hipMemsetAsync(err, 0, 4, st));
 	HIPCHK(hipMemsetAsync(xSeen, 0, NS, st));
-	hipLaunchKernelGGL(k_qbitmap, dim3(nq), dim3(256), 0, st, (const int*)qOff, dQWords, nq, db->nWords, db->bmWords, bm, err);
-	CountArgs ca{bm, db->bmWords, nq, S, db->dRowOff, db->dRowLen, db->dActive, db->words, xCnt, xMinw};
+	hipLaunchKernelGGL(k_qbitmap, dim3(nq), dim3(256), 0, st, qOff, dQWords, nq, db->nWords, db->bmWords, bm, err);
+	const int* slabW = db->words.as<int>();
+	CountArgs ca{bm, db->bmWords, nq, S, db->dRowOff, db->dRowLen, db->dActive, slabW, xCnt, xMinw};
 	const size_t ldsBytes = (size_t)KF_QG * db->bmWords * 4;
 	const dim3 gc((S + 3) / 4, (nq + KF_QG - 1) / KF_QG);
 	if (ldsBytes <= (size_t)KF_LDS_BYTES) hipLaunchKernelGGL(k_count<true>, gc, dim3(256), ldsBytes, st, ca);
 	else hipLaunchKernelGGL(k_count<false>, gc, dim3(256), 0, st, ca);
 	const int m = loop ? 1 : 0;
 	const int cu = db->cur[m], nx = 1 - cu;
-	WalkArgs wa{nq, S, loop, xQId, xConn, xCnt, db->stQ[m][cu], db->stW[m][cu], db->stQ[m][nx], db->stW[m][nx], xWA, xFl};
+	const mcs_kfdb::State &sc = db->st[m][cu], &sn = db->st[m][nx];
+	WalkArgs wa{nq, S, loop, xQId, xConn, xCnt, sc.q.as<int64_t>(), sc.w.as<int>(), sn.q.as<int64_t>(), sn.w.as<int>(), xWA, xFl};
 	hipLaunchKernelGGL(k_walk, dim3((S + 255) / 256), dim3(256), 0, st, wa);
 	hipLaunchKernelGGL(k_maxc, dim3(nq), dim3(256), 0, st, S, (const int*)xWA, (const uint8_t*)xFl, xMinC, xNApp);
-	ScoreArgs sa{nq, S, loop, qOff, dQWords, dQVals, xMinS, db->dRowOff, db->dRowLen, db->words, db->vals, xWA, xMinC, xFl, xSc};
+	ScoreArgs sa{nq, S, loop, qOff, dQWords, dQVals, xMinS, db->dRowOff, db->dRowLen, slabW, db->vals.as<double>(), xWA, xMinC, xFl, xSc};
 	hipLaunchKernelGGL(k_score, dim3((S + 255) / 256, nq), dim3(256), 0, st, sa);
-	hipLaunchKernelGGL(k_carry, dim3((S + 255) / 256), dim3(256), 0, st, nq, S, (const uint8_t*)xFl, xSc, db->stS[m][cu], db->stS[m][nx]);
+	hipLaunchKernelGGL(k_carry, dim3((S + 255) / 256), dim3(256), 0, st, nq, S, (const uint8_t*)xFl, xSc, (const double*)sc.s.as<double>(), sn.s.as<double>());
 	FinalArgs fa{nq, S, loop, xMinS, xMinC, xNApp, xWA, xFl, xSc, xMinw, db->dAddSeq, db->dId, db->dCovis, db->dCovisN, xLSlot, xLKey, xLAcc, xLBest, xLOrd, xSeen, cap,
 	             xCand, xCandN, dcap, xDN, xDId, xDW, xDS, xDA, xDB};
 	hipLaunchKernelGGL(k_final, dim3(nq), dim3(1024), 0, st, fa);
 	HIPCHK(hipGetLastError());
-	std::vector<int> candN(nq), dN(nq);
-	int errv = 0;
-	HIPCHK(hipMemcpyAsync(candN.data(), xCandN, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipMemcpyAsync(dN.data(), xDN, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipMemcpyAsync(&errv, err, 4, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipStreamSynchronize(st));
+	if (int r = stg.finish(MCS_OK)) return r;   // candN, dN, errv are back; the block stays as it is until the next call
 	if (errv & 1) return fail(MCS_ERR_INVALID, "query BowVector: word id out of range");
 	if (errv & 2) return fail(MCS_ERR_INVALID, "query BowVector: word ids must be strictly ascending");
 	// outputs (counts are the full counts, also when they exceed the capacity)
-	const hipMemcpyKind toUser = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
 	int needC = 0, needD = 0;
 	for (int q = 0; q < nq; ++q) { needC = std::max(needC, candN[q]); needD = std::max(needD, dN[q]); }
-	if (host) memcpy(cand_count, candN.data(), (size_t)nq * 4);
-	else HIPCHK(hipMemcpy(cand_count, candN.data(), (size_t)nq * 4, hipMemcpyHostToDevice));
-	if (cap > 0) HIPCHK(hipMemcpy(cand_ids, xCand, (size_t)nq * cap * 8, toUser));
+	HIPCHK(put(cand_count, host ? (const void*)candN : xCandN, host, nq4, host, st));
+	HIPCHK(put(cand_ids, xCand, false, (size_t)nq * cap * 8, host, st));
 	if (diag && diag->count) {
-		if (host) memcpy(diag->count, dN.data(), (size_t)nq * 4);
-		else HIPCHK(hipMemcpy(diag->count, dN.data(), (size_t)nq * 4, hipMemcpyHostToDevice));
-		if (dcap > 0) {
-			const size_t nd = (size_t)nq * dcap;
-			HIPCHK(hipMemcpy(diag->kf_id, xDId, nd * 8, toUser));
-			HIPCHK(hipMemcpy(diag->words, xDW, nd * 4, toUser));
-			HIPCHK(hipMemcpy(diag->score, xDS, nd * 8, toUser));
-			HIPCHK(hipMemcpy(diag->acc, xDA, nd * 8, toUser));
-			HIPCHK(hipMemcpy(diag->best, xDB, nd * 8, toUser));
-		}
+		const size_t nd = (size_t)nq * dcap;
+		HIPCHK(put(diag->count, host ? (const void*)dN : xDN, host, nq4, host, st));
+		HIPCHK(put(diag->kf_id, xDId, false, nd * 8, host, st)); HIPCHK(put(diag->words, xDW, false, nd * 4, host, st));
+		HIPCHK(put(diag->score, xDS, false, nd * 8, host, st)); HIPCHK(put(diag->acc, xDA, false, nd * 8, host, st));
+		HIPCHK(put(diag->best, xDB, false, nd * 8, host, st));
 	}
+	HIPCHK(hipStreamSynchronize(st));
 	if (needC > cap) return fail(MCS_ERR_CAPACITY, "keyframe database: a query has " + std::to_string(needC) + " candidates, cap is " + std::to_string(cap) +
 	                                                   " (cand_count holds the counts needed; the database state is unchanged)");
 	if (diag && needD > dcap)
@@ -732,7 +649,7 @@ int mcs_kfdb_score(mcs_kfdb* db, int nw, const int32_t* word_ids, const double* 
 	hipStream_t st = c->stream;
 	const bool host = kind == MCS_MEM_HOST;
 	std::vector<int64_t> ids;
-	HIPCHK(fetch(ids, kf_ids, nkf, kind));
+	HIPCHK(fetch(ids, kf_ids, nkf, kind, st));
 	std::vector<int> slots(nkf);
 	for (int i = 0; i < nkf; ++i) {
 		auto it = db->slotOf.find(ids[i]);
@@ -750,48 +667,9 @@ int mcs_kfdb_score(mcs_kfdb* db, int nw, const int32_t* word_ids, const double* 
 	Staging stg(c, host);
 	stg.upload(&dSlots, slots.data(), (size_t)nkf * 4); stg.in(&dW, word_ids, (size_t)nw * 4); stg.in(&dV, values, (size_t)nw * 8); stg.out(&dOut, scores, (size_t)nkf * 8);
 	if (int r = stg.commit()) return r;
-	hipLaunchKernelGGL(k_score_list, dim3((nkf + 255) / 256), dim3(256), 0, st, dW, dV, nw, dSlots, nkf, db->dRowOff, db->dRowLen, db->words, db->vals, dOut);
+	hipLaunchKernelGGL(k_score_list, dim3((nkf + 255) / 256), dim3(256), 0, st, dW, dV, nw, dSlots, nkf, db->dRowOff, db->dRowLen, db->words.as<int>(),
+	                   db->vals.as<double>(), dOut);
 	HIPCHK(hipGetLastError());
 	return stg.finish(MCS_OK);
 }
 
-int mcs_vocabulary_set_words(mcs_vocabulary* v, const int32_t* word_id_per_node, const double* weight_per_node) {
-	if (!v || !word_id_per_node || !weight_per_node) return fail(MCS_ERR_INVALID, "null argument");
-	return mcs_vocabulary_set_words_internal(v, word_id_per_node, weight_per_node);
-}
-
-int mcs_bow_vector(mcs_vocabulary* v, const int32_t* leaf_nodes, int n, mcs_mem_kind kind, int32_t* word_ids_out, double* values_out, int32_t* nwords_out) {
-	if (!v || n < 0 || (n && (!leaf_nodes || !word_ids_out || !values_out)) || !nwords_out) return fail(MCS_ERR_INVALID, "null argument");
-	mcs_ctx* c = nullptr;
-	int nNodes = 0, nWords = 0;
-	int *wordOf = nullptr, *hist = nullptr;
-	double* weightOf = nullptr;
-	int rc = mcs_vocabulary_words_internal(v, &c, &nNodes, &wordOf, &weightOf, &hist, &nWords);
-	if (rc != MCS_OK) return rc;
-	HIPCHK(hipSetDevice(c->device));
-	hipStream_t st = c->stream;
-	const bool host = kind == MCS_MEM_HOST;
-	const size_t nn = std::max(n, 1);
-	// host kind: the outputs hold nwords_out entries, known only after the kernel, so they are fetched below from the block (intact until the next call)
-	const int* dLeaf = nullptr; int *dW = nullptr, *outW = nullptr, *nOut = nullptr, *dErr = nullptr; double *dWt = nullptr, *outV = nullptr;
-	int errv = 0, d = 0;
-	Staging stg(c, host);
-	stg.in(&dLeaf, leaf_nodes, (size_t)n * 4); stg.scratch(&dW, nn * 4); stg.scratch(&dWt, nn * 8); stg.download(&dErr, &errv, 4);
-	if (host) { stg.scratch(&outW, nn * 4); stg.scratch(&outV, nn * 8); stg.download(&nOut, &d, 4); }
-	else { outW = word_ids_out; outV = values_out; nOut = nwords_out; }
-	if (int r = stg.commit()) return r;
-	HIPCHK(hipMemsetAsync(dErr, 0, 4, st));
-	hipLaunchKernelGGL(k_bow_vector, dim3(1), dim3(1024), 0, st, dLeaf, n, nNodes, nWords, wordOf, weightOf, hist, dW, dWt, outW, outV, nOut, dErr);
-	HIPCHK(hipGetLastError());
-	if (int r = stg.finish(MCS_OK)) return r;
-	if (errv & 1) return fail(MCS_ERR_INVALID, "mcs_bow_vector: leaf node id out of range");
-	if (errv & 2) return fail(MCS_ERR_INVALID, "mcs_bow_vector: a node with a weight > 0 has no word id (not a leaf)");
-	if (host) {
-		*nwords_out = d;
-		if (d) {
-			HIPCHK(hipMemcpy(word_ids_out, outW, (size_t)d * 4, hipMemcpyDeviceToHost));
-			HIPCHK(hipMemcpy(values_out, outV, (size_t)d * 8, hipMemcpyDeviceToHost));
-		}
-	}
-	return MCS_OK;
-}

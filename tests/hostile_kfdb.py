@@ -8,6 +8,7 @@ imported.  Every builder names the launch shape it is aimed at:
     k_walk / k_score / k_carry   256-thread blocks over the slots
     k_final / k_bow_vector       1024-thread strides over the list / the leaves
     state arrays                 capacity max(2 * slots, 256) at the first query that finds it too small, the old contents copied
+    slab of rows                 capacity max(need, 2 * capacity, 64) elements at the first add that finds it too small, the rows in use copied
 
 Values are plain doubles; nothing needs them normalised (the library and the model do the same arithmetic on whatever they are given)."""
 import math
@@ -219,7 +220,14 @@ def long_queries(n):
     committed, everything would be appended again); then fresh ids, a batch of two, and the loop form at and one ulp above the common score"""
     q = lambda i: [(i, *LONG_QUERY)]   # noqa: E731
     return [("reloc", q(7000)), ("reloc", q(7001), {"cap": 3, "expect": "capacity"}), ("reloc", q(7002), {"dcap": 100, "expect": "capacity"}), ("reloc", q(7000)),
-            ("reloc", q(7003) + q(7004)), ("loop", q_loop(7005, 0.0)), ("loop", q_loop(7006, 0.75) + q_loop(7007, 0.7500000000000001))]
+            ("reloc", q(7003) + q(7004)), ("loop", q_loop(7005, 0.0)), ("loop", q_loop(7006, 0.75) + q_loop(7007, 0.7500000000000001)),
+            host_score(LONG_QUERY, [1, 2, n])]
+
+
+def host_score(query, ids):
+    """the last operation of a script with refused calls: a score call in HOST memory whatever the kind of the run, so it stages its arrays in the context's
+    block; a refused call that had kept its claim on the block would make it fail"""
+    return ("score", *query, list(ids), {"host": True})
 
 
 def q_loop(i, min_score, conn=()):
@@ -233,7 +241,7 @@ def count_only():
     still stores id 7 with 2 words, so the score of call 1 is added to kf 4's.  Had call 1 not committed, kf 2 would store id 0 and add nothing."""
     return [("add", [(2, *uni([8, 9])), (4, *uni([5]))]), ("covis", 4, [2]),
             ("loop", [(7, *uni([8, 9]), math.inf, [])], {"cap": 0, "null_cands": True}), ("hook", "after_count_only"),
-            ("loop", [(7, *uni([5]), 0.0, [])]), ("reloc", [(7, *uni([5, 8]))])]
+            ("loop", [(7, *uni([5]), 0.0, [])]), ("reloc", [(7, *uni([5, 8]))]), host_score(uni([5, 8]), [2, 4])]
 
 
 # ------------------------------------------------------------------ 5. thresholds and ties
@@ -332,7 +340,7 @@ def add_calls(n_words=40):
 
 def bad_queries(n_words=40):
     """a detection query with a word out of range and one with descending words, each in a batch behind a good query (whose state change must not stay), in
-    both forms; then the good query alone.  Host kind: the guard's texts; device kind: k_qbitmap's."""
+    both forms; then a host-memory score call (host_score), then the good query alone.  Host kind: the guard's texts; device kind: k_qbitmap's."""
     nw = n_words
     good, later = (60, *uni([5, 6])), (61, *uni([5, 6, 31]))
     r = lambda form, host, dev: {"refuse": {False: (INVALID, "mcs_kfdb_detect_%s: %s" % (form, host)), True: (INVALID, dev)}}   # noqa: E731
@@ -343,7 +351,7 @@ def bad_queries(n_words=40):
     return [("add", [(1, *uni([5, 6, 31])), (2, *uni([5, 32])), (3, *uni([6, nw - 1]))]), ("covis", 1, [2, 3]), ("covis", 2, [1]),
             ("reloc", [good, (62, [5, nw], [0.5, 0.5])], rel), ("reloc", [good, (62, [6, 5], [0.5, 0.5])], rel2), ("reloc", [good, (62, [5, 5], [0.5, 0.5])], rel2),
             ("loop", [lq(good), lq((62, [-1, 5], [0.5, 0.5]))], lp), ("loop", [lq(good), lq((62, [31, 6], [0.5, 0.5]))], lp2),
-            ("reloc", [later, good]), ("loop", [lq(later), lq(good)])]
+            host_score(uni([5, 6]), [1, 2, 3]), ("reloc", [later, good]), ("loop", [lq(later), lq(good)])]
 
 
 SCORE_COUNTS = (0, 1, 255, 256, 257)
@@ -360,6 +368,22 @@ def score_calls(nkf):
     if nkf >= 2:
         script += [("erase", [nkf]), ("score", *q, ids, {"expect": (INVALID, "mcs_kfdb_score: keyframe %d is not in the database" % nkf)}), ("score", *q, ids[:-1])]
     return script
+
+
+SLAB_ADDS, SLAB_ROW, SLAB_WORDS = 40, 5, 256
+
+
+def slab_growth():
+    """40 add calls of one keyframe each, 5 words per row, into a database created without a capacity hint: the slab holds 64 elements from the first add,
+    128 from the 13th (60 elements of 12 rows behind it) and 256 from the 26th (125 elements of 25 rows).  Row i (keyframe i + 1) = words i, 40 + i, ...,
+    160 + i with values that differ from row to row, so a row lost or shifted by a reallocation shows in its score.  Then one score call over all 40
+    keyframes against every word, and one relocalisation query {0, 39} that shares a word with the first row and with the last."""
+    def row(i):
+        raw = [1.0 + (i + 3 * k) % 7 for k in range(SLAB_ROW)]
+        return (i + 1, [i + SLAB_ADDS * k for k in range(SLAB_ROW)], [x / sum(raw) for x in raw])
+
+    return [("add", [row(i)]) for i in range(SLAB_ADDS)] + \
+           [("score", *uni(range(SLAB_ADDS * SLAB_ROW)), list(range(1, SLAB_ADDS + 1))), ("reloc", [(500, *uni([0, SLAB_ADDS - 1]))])]
 
 
 # ------------------------------------------------------------------ 8. mcs_bow_vector: a root with N leaf children

@@ -14,7 +14,8 @@ A script is a list of operations:
     ("loop", [(query id, words, values, min score, [connected ids]), ...], opts)
                                                          opts of both: refuse = {device kind?: (code, text)}: a bad query batch, refused; no state moves
     ("add_raw", ids, offsets, words, values, opts)       an add by its raw CSR arrays (offsets that no list of rows gives); opts: expect = (code, text)
-    ("score", words, values, [ids], opts)                mcs_kfdb_score, bits against the model's l1_score; opts: expect = (code, text)
+    ("score", words, values, [ids], opts)                mcs_kfdb_score, bits against the model's l1_score; opts: expect = (code, text), host = True: this
+                                                         call's arrays in host memory whatever the kind of the run
     ("hook", name)                                      nothing; a place where a mutation of the model can act (tests/test_kfdb_hostile_cpu.py)
 This module imports nothing of the library: the package and gpu_common are handed in."""
 import ctypes as C
@@ -193,13 +194,19 @@ class DeviceSide:
             traces.append(list(zip(i_[r].tolist(), w_[r].tolist(), s_[r].view(np.uint64).tolist(), a_[r].view(np.uint64).tolist(), b_[r].tolist())))
         return rc, cnt, cands, dc, traces
 
-    def score(self, w, v, ids):
-        keep = []
-        po, ro = self._out(np.full(max(len(ids), 1), -7.0), keep)
-        rc = self.L.mcs_kfdb_score(self.h, len(w), self._in(np.asarray(w, np.int32), keep) if len(w) else None,
-                                   self._in(np.asarray(v, np.float64), keep) if len(w) else None, len(ids),
-                                   self._in(np.asarray(ids, np.int64), keep) if len(ids) else None, self.kind, po)
-        return rc, (ro()[:len(ids)] if rc == OK else None)
+    def score(self, w, v, ids, host=False):
+        """host: the arrays in host memory for this one call, whatever the kind of the side"""
+        keep, was = [], (self.device, self.kind)
+        if host:
+            self.device, self.kind = False, self.pkg.MEM_HOST
+        try:
+            po, ro = self._out(np.full(max(len(ids), 1), -7.0), keep)
+            rc = self.L.mcs_kfdb_score(self.h, len(w), self._in(np.asarray(w, np.int32), keep) if len(w) else None,
+                                       self._in(np.asarray(v, np.float64), keep) if len(w) else None, len(ids),
+                                       self._in(np.asarray(ids, np.int64), keep) if len(ids) else None, self.kind, po)
+            return rc, (ro()[:len(ids)] if rc == OK else None)
+        finally:
+            self.device, self.kind = was
 
 
 class Vocab:
@@ -294,7 +301,7 @@ def check(script, n_words, dev=None, batched=True, mut=None, mod=None):
             want = None if "expect" in opts else mod.score(bow(op[1], op[2]), op[3])
             results.append(want)
             if dev is not None:
-                rc, got = dev.score(op[1], op[2], op[3])
+                rc, got = dev.score(op[1], op[2], op[3], host=opts.get("host", False))
                 if "expect" in opts:
                     assert (rc, dev.error()) == tuple(opts["expect"]), (rc, dev.error())
                 else:

@@ -1,5 +1,5 @@
 """-m gpu: the device keyframe database (csrc/mcs_kfdb.hip: k_qbitmap, k_count, k_walk, k_maxc, k_score, k_carry, k_final, k_score_list) and the device
-BowVector (k_bow_vector) on the hostile cases of tests/hostile_kfdb.py, against the model of tests/kfdb_model.py through tests/kfdb_pack.py.
+BowVector (k_bow_vector, csrc/mcs_bow.hip) on the hostile cases of tests/hostile_kfdb.py, against the model of tests/kfdb_model.py through tests/kfdb_pack.py.
 
 Every comparison is exact: ids, word counters, counts and orders as equal values, doubles as equal bits; nothing has a tolerance.  In both memory kinds only
 the first cand_count[q] candidate ids and the first diag.count[q] diagnostic rows of a query are compared (the first `cap` of them where a call is refused
@@ -144,6 +144,13 @@ def test_add_calls_and_refusals(env, device):
     """a batched add with empty rows in the middle; every refusal by code and text (the bad offsets among them, refused before anything is sized by them);
     size() and a following query equal the model after each"""
     check(env, H.add_calls(), 40, device)
+
+
+@pytest.mark.parametrize("device", KINDS)
+def test_slab_grows_behind_rows(env, device):
+    """40 adds of one 5-word row each: the slab is reallocated at 64 and at 128 elements with rows in it; every row's score and a query over the first and
+    the last row"""
+    check(env, H.slab_growth(), H.SLAB_WORDS, device)
 
 
 @pytest.mark.parametrize("device", KINDS)

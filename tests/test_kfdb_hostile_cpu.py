@@ -229,6 +229,21 @@ def test_add_and_score_scripts_run_on_the_model():
         assert len(res[0]) == n and (n < 2 or res[0][1] == 0.0) and all(x == 0.0 for x in res[1])
 
 
+def test_slab_growth_has_rows_behind_each_reallocation():
+    script = H.slab_growth()
+    adds = [op for op in script if op[0] == "add"]
+    assert len(adds) == H.SLAB_ADDS and all(len(op[1]) == 1 and len(op[1][0][1]) == H.SLAB_ROW for op in adds)
+    used = np.cumsum([len(op[1][0][1]) for op in adds]).tolist()   # slab elements in use after each add; capacities 64 -> 128 -> 256 (max(need, 2 * cap, 64))
+    for cap in (64, 128):
+        k = [i for i in range(1, len(used)) if used[i - 1] <= cap < used[i]]
+        assert len(k) == 1 and used[k[0] - 1] > 0, cap   # one add crosses the capacity, with rows in the slab before it
+    assert 128 < used[-1] <= 256
+    assert all(max(op[1][0][1]) < H.SLAB_WORDS for op in adds)
+    scores, reloc = run(script, H.SLAB_WORDS)
+    assert len(scores) == H.SLAB_ADDS and all(0.0 < s < 1.0 for s in scores) and len(set(scores)) > 1   # rows differ: a shifted row shows
+    assert sorted(ids(reloc[0][1])) == [1, H.SLAB_ADDS]   # the query meets the first row and the last, nothing between
+
+
 # ------------------------------------------------------------------ 8. BowVectors
 
 def test_bow_vector_preconditions():
