@@ -2,7 +2,7 @@
 // Reference: src/mdBRIEFextractorOct.cpp:863-949 (one cv::FastFeatureDetector(th, nonmax=true, TYPE_9_16)->detect()
 // per ~30x30 cell view with its mask view); FAST arithmetic per SURVEY Appendix A.3.
 //
-// One 256-thread workgroup per (image, cell): the cell's processed region plus its 3-px ring is staged in LDS once,
+// One workgroup per (image, cell), of one, two or four waves (FastThreads below): the cell's processed region plus its 3-px ring is staged in LDS once,
 // every pixel's corner score is computed from LDS, NMS runs on an LDS score tile whose 1-px frame is zero — which is
 // exactly the reference's behaviour: every cell is its own FAST() call, so a neighbour outside the cell's processed
 // region counts as score 0 and corners are never suppressed across a cell seam.
@@ -28,11 +28,17 @@
 namespace mcs {
 
 // LDS geometry for cells of at most CW x CW processed pixels (the level's wCell / hCell): tile = cell + 3-px ring, score tile = cell + 1-px zero frame.
-// Two instances: CW = 40 (7.8 KB per workgroup: every level with four or more cell columns AND rows — a 30-px grid on w px gives cells of
-// ceil(w / floor(w / 30)) <= 40 from 120 px on) and CW = 60 (any cell).
-#ifndef MCS_FAST_BS
-#define MCS_FAST_BS 128
-#endif
+// Two instances: CW = 40 (every level with four or more cell columns AND rows — a 30-px grid on w px gives cells of ceil(w / floor(w / 30)) <= 40 from
+// 120 px on) and CW = 60 (any cell).
+// Threads per cell are a property of the detector instance.  FAST 9/16 on cells of up to 40 px is ONE wave per cell: its compass pass and its arc score were one
+// trip of one wave already, and a second wave paid the prologue, the scans and the loop bookkeeping again to carry a sixth of the staging and the tail of the
+// suppression trip.  The small rings and AGAST have suppression walks of their own and keep two waves; the 60-px instances keep four.
+template <int CW, int P, int AG> struct FastThreads { static constexpr int value = CW > 44 ? 256 : (P == 16 && AG < 0 ? 64 : 128); };
+// The one-wave instance bounds its survivor list (kFastListCap entries instead of one per pixel of the cell): a workgroup of one wave pays the cell's LDS alone,
+// and LDS is what limits the cells per CU (granules of 1 280 bytes: 7.3 KB with the full list is 21 cells, 6.2 KB is 25).  The bench stream's cells list 166
+// survivors on average, 699 at the 99.9th percentile and 814 at most (profiles/NOTES.md); a cell that would list more is exact all the same, see pass 1.  (384
+// entries, 5.0 KB, 32 cells per CU: 8 % of the stream's cells then leave the list path, and the kernel takes 0.268 ms instead of 0.259.)
+constexpr int kFastListCap = 1024;
 template <int CW> struct FastGeom {
 	static constexpr int kTileX = 4;   // tile column of the cell's first processed pixel: a 4-byte left margin (3 ring pixels + 1), so that groups of 4 pixels are aligned dwords
 	static constexpr int kTilePitch = (CW + kTileX + 3 + 4 + 3) / 4 * 4, kTileRows = CW + 6;   // + 4: the packed compass test reads one dword past the right ring
@@ -285,13 +291,17 @@ __global__ __launch_bounds__(kFastBS) void k_fast_cells(ExtractBuffers b, int ni
 	__shared__ int rowOff[64];           // exclusive prefix of the kept-pixel counts per row
 	__shared__ int runBase;
 	__shared__ int nSurv;
-	__shared__ unsigned short surv[CW * CW];   // codes of the pixels that pass the compass test
 	constexpr int QR = AG >= 0 ? AgastGeom<AG < 0 ? 3 : AG>::R : 3;   // radius of the compass test
 	// FAST on the 16-pixel ring: the survivor list is kept in ROW-MAJOR order (round 6), so that a kept survivor's place in the output is the number of kept survivors in
 	// front of it in the list — non-max suppression, mask and emission are then ONE loop with a ballot, where a verdict bitmap, a row prefix and a second loop stood
 	constexpr bool kOrdered = P == 16 && AG < 0;
-	__shared__ int waveTot[kFastBS / 64];
-	int listRun = 0;   // survivors listed by the trips so far (uniform)
+	// one wave per cell: the list base and the output rank are running totals in registers (no totals through LDS, no barrier inside a pass), and the list is bounded
+	constexpr bool kOneWave = kOrdered && kFastBS == 64;
+	constexpr int kListCap = kOneWave && kFastListCap < CW * CW ? kFastListCap : CW * CW;
+	__shared__ unsigned short surv[kListCap];   // codes of the pixels that pass the compass test
+	__shared__ int waveTot[kFastBS / 64];   // the waves' totals of a trip (several waves per cell only: the one-wave instance never touches it, and the compiler drops it there)
+	int listRun = 0;           // survivors listed by the trips so far (uniform)
+	bool incomplete = false;   // (bounded list) some survivors were scored without being listed (uniform)
 
 	// XCD-aware mapping: hardware places block i on XCD i%8; give every XCD a contiguous run of cells so that the
 	// overlapping cell rings / shared cache lines of neighbouring cells hit the same L2.
@@ -333,7 +343,7 @@ __global__ __launch_bounds__(kFastBS) void k_fast_cells(ExtractBuffers b, int ni
 		}
 		for (int i = tid; i < (kScRows * kScPitch + 15) / 16; i += kFastBS) reinterpret_cast<uint4*>(sc)[i] = uint4{0u, 0u, 0u, 0u};   // the score tile cleared as 16-byte words
 		if (!kOrdered) for (int i = tid; i < 2 * ch; i += kFastBS) keepBits[i] = 0;
-		if (tid == 0) { runBase = 0; nSurv = 0; }
+		if (!kOrdered && tid == 0) { runBase = 0; nSurv = 0; }
 		__syncthreads();
 	} else {
 		const int tw = cw + Geo::kTileX + 3;
@@ -357,7 +367,7 @@ __global__ __launch_bounds__(kFastBS) void k_fast_cells(ExtractBuffers b, int ni
 		const int sh = ch + 2;
 		for (int i = tid; i < sh * (kScPitch / 4); i += kFastBS) reinterpret_cast<uint32_t*>(sc)[i] = 0;   // score tile cleared as dwords
 		if (!kOrdered) for (int i = tid; i < 2 * ch; i += kFastBS) keepBits[i] = 0;
-		if (tid == 0) { runBase = 0; nSurv = 0; }
+		if (!kOrdered && tid == 0) { runBase = 0; nSurv = 0; }
 		__syncthreads();
 	}
 
@@ -395,7 +405,29 @@ __global__ __launch_bounds__(kFastBS) void k_fast_cells(ExtractBuffers b, int ni
 			const int incl = wave_incl_scan(cnt);
 			const int total = __builtin_amdgcn_readlane(incl, 63);
 			int wbase = 0;
-			if constexpr (kOrdered) {
+			if constexpr (kOneWave) {
+				// list space in (trip, lane) order = the segments' row-major order; the base is the running total.
+				// A trip that would push the list past its capacity is not listed: every lane scores its own survivors at once (the same fast_score2, into the
+				// same `sc`; the tile is complete and `sc` is cleared behind the barrier above, and nothing reads `sc` before the barrier in front of pass 3), the
+				// list keeps what it has, and the cell is marked: pass 3 then finds the survivors in the score tile instead of in the list.
+				if (listRun + total > kListCap) {
+					incomplete = true;
+					const uint8_t* crow = &tile[((code >> 6) + 3) * kTilePitch + (code & 63) + Geo::kTileX];
+					uint8_t* srow = &sc[((code >> 6) + 1) * kScPitch + (code & 63) + 1];
+					while (bits) {
+						const int ja = __builtin_ctz(bits);
+						bits &= bits - 1u;
+						const int jb = bits ? __builtin_ctz(bits) : ja;
+						bits &= bits - 1u;   // (0 stays 0)
+						const uint32_t s2 = fast_score2<kTilePitch>(crow + ja, crow + jb, t);
+						srow[ja] = (uint8_t)s2;
+						if (jb != ja) srow[jb] = (uint8_t)(s2 >> 8);
+					}
+				} else {
+					wbase = listRun;
+					listRun += total;
+				}
+			} else if constexpr (kOrdered) {
 				// list space in (trip, wave, lane) order = the segments' row-major order: the waves' totals meet in LDS (one barrier per trip: a cell of up to 40 x 40 is one
 				// trip) instead of racing for an atomic — pass 3 below then ranks the kept survivors by list position alone
 				if (lane == 0) waveTot[wave] = total;
@@ -434,6 +466,8 @@ __global__ __launch_bounds__(kFastBS) void k_fast_cells(ExtractBuffers b, int ni
 			if (pass) surv[wbase + __popcll(bal & ((1ull << lane) - 1ull))] = (unsigned short)code;
 		}
 	}
+	// (one wave per cell: the list entries and scores that pass 2 and 3 read were written by OTHER lanes, so the barriers between the passes stay — a workgroup of
+	// one wave pays next to nothing for them, and nothing here leans on the order of a wave's LDS operations)
 	__syncthreads();
 	const int ns = kOrdered ? listRun : nSurv;
 	if constexpr (P == 16) {
@@ -561,15 +595,21 @@ __global__ __launch_bounds__(kFastBS) void k_fast_cells(ExtractBuffers b, int ni
 	}
 	if constexpr (kOrdered) {
 		// pass 3, ordered list: suppression + mask + emission in one loop.  A trip covers kFastBS consecutive list entries; the kept ones among them leave in list order:
-		// a ballot per wave, the waves' counts through LDS (one barrier per trip; 113 survivors per cell on the bench stream: one trip)
+		// a ballot per wave.  Several waves per cell (the 60-px instance): the waves' counts meet in `waveTot`, one barrier per trip.  One wave per cell: the rank is
+		// a running total in a register, no barrier (166 survivors per cell on the bench stream: three trips).
+		// A cell whose list is incomplete walks the score tile itself, row-major, a pixel per lane: pass 3 keeps only s0 > nb >= 0, so every kept pixel has a score,
+		// every pixel with a score is a survivor, and row-major order is the emission order.
 		int run = 0;
-		for (int base = 0; base < ns; base += kFastBS) {
+		const int n3 = incomplete ? cw * ch : ns;
+		const unsigned divM = incomplete ? (262144u + (unsigned)cw - 1u) / (unsigned)cw : 0u;   // p / cw = (p * divM) >> 18, exact for cw <= 60 and p < 3600 (see the small rings' pass 1)
+		for (int base = 0; base < n3; base += kFastBS) {
 			const int i = base + tid;
 			bool keep = false;
 			uint32_t rec = 0;
-			if (i < ns) {
-				const int p = surv[i];
-				const int py = p >> 6, px = p & 63;
+			if (i < n3) {
+				int py, px;
+				if (incomplete) { py = (int)(((unsigned)i * divM) >> 18); px = i - py * cw; }
+				else { const int p = surv[i]; py = p >> 6; px = p & 63; }
 				const uint8_t* q = &sc[(py + 1) * kScPitch + px + 1];
 				const int s0 = q[0];
 				const int nb = max(max(max((int)q[-1], (int)q[1]), max((int)q[-kScPitch - 1], (int)q[-kScPitch])),
@@ -582,14 +622,17 @@ __global__ __launch_bounds__(kFastBS) void k_fast_cells(ExtractBuffers b, int ni
 				rec = (uint32_t)(cell.x0 + px - kMinBorder) | ((uint32_t)(cell.y0 + py - kMinBorder) << 12) | ((uint32_t)s0 << 24);
 			}
 			const unsigned long long bal = __ballot(keep);
-			if (lane == 0) waveTot[wave] = __popcll(bal);
-			__syncthreads();
-			int before = 0, all = 0;
+			int before = 0, all = __popcll(bal);
+			if constexpr (!kOneWave) {
+				if (lane == 0) waveTot[wave] = all;
+				__syncthreads();
+				all = 0;
 #pragma unroll
-			for (int w = 0; w < kFastBS / 64; ++w) { const int tw_ = waveTot[w]; before += w < wave ? tw_ : 0; all += tw_; }
+				for (int w = 0; w < kFastBS / 64; ++w) { const int tw_ = waveTot[w]; before += w < wave ? tw_ : 0; all += tw_; }
+			}
 			if (keep) slots[run + before + __popcll(bal & ((1ull << lane) - 1ull))] = rec;
 			run += all;
-			if (base + kFastBS < ns) __syncthreads();   // (waveTot is rewritten by the next trip)
+			if (!kOneWave && base + kFastBS < n3) __syncthreads();   // (waveTot is rewritten by the next trip)
 		}
 		if (tid == 0) *countOut = run;
 		return;
@@ -649,15 +692,16 @@ void launch_fast(const ExtractBuffers& b, const PyrDesc& hd, int nimg, hipStream
 	const int perXcd = (nblocks + kNumXCD - 1) / kNumXCD;
 	int cellMax = 0;
 	for (int l = level0; l < level1; ++l) cellMax = std::max(cellMax, std::max(hd.lv[l].wCell, hd.lv[l].hCell));
-	// two waves per cell for the small instance: alone 0.46 ms against 0.52 (one wave) and 0.55 (four waves); in the overlapped step one and two waves are within 1 %
+	// threads per cell: FastThreads (one wave for FAST 9/16 on the 40-px instance; the measurements are in profiles/NOTES.md, "k_fast_cells: one wave per cell")
 	const dim3 grid(perXcd * kNumXCD);
 	// block -> image by multiplication: M = ceil(2^32 / ncells) is exact while block * ncells < 2^32 (block * (M * ncells - 2^32) < 2^32)
 	if ((unsigned long long)nblocks * (unsigned long long)ncells >= (1ull << 32)) { fprintf(stderr, "mcs: FAST launch too large (%d blocks)\n", nblocks); abort(); }
 	const unsigned ncellsM = (unsigned)(((1ull << 32) + (unsigned long long)ncells - 1ull) / (unsigned long long)ncells);
 #define MCS_FAST_LAUNCH(P)                                                                                                                      \
 	do {                                                                                                                                        \
-		if (cellMax <= 40) hipLaunchKernelGGL((k_fast_cells<40, MCS_FAST_BS, P>), grid, dim3(MCS_FAST_BS), 0, s, b, nimg, nblocks, perXcd, cell0, ncells, ncellsM);     \
-		else hipLaunchKernelGGL((k_fast_cells<60, 256, P>), grid, dim3(256), 0, s, b, nimg, nblocks, perXcd, cell0, ncells, ncellsM);                   \
+		constexpr int T40 = FastThreads<40, P, -1>::value, T60 = FastThreads<60, P, -1>::value;                                                       \
+		if (cellMax <= 40) hipLaunchKernelGGL((k_fast_cells<40, T40, P>), grid, dim3(T40), 0, s, b, nimg, nblocks, perXcd, cell0, ncells, ncellsM);   \
+		else hipLaunchKernelGGL((k_fast_cells<60, T60, P>), grid, dim3(T60), 0, s, b, nimg, nblocks, perXcd, cell0, ncells, ncellsM);                 \
 	} while (0)
 	if (hd.agast >= 0) {
 		// AGAST: the processed region of a cell is its view minus the ring's radius on every side (FAST: minus 3), so cells are up to 4 pixels larger
@@ -665,8 +709,9 @@ void launch_fast(const ExtractBuffers& b, const PyrDesc& hd, int nimg, hipStream
 		const int cellMaxA = cellMax + 6 - 2 * B;
 #define MCS_AGAST_LAUNCH(T)                                                                                                                                              \
 		do {                                                                                                                                                                 \
-			if (cellMaxA <= 44) hipLaunchKernelGGL((k_fast_cells<44, 128, AgastGeom<T>::P, T>), grid, dim3(128), 0, s, b, nimg, nblocks, perXcd, cell0, ncells, ncellsM);   \
-			else hipLaunchKernelGGL((k_fast_cells<64, 256, AgastGeom<T>::P, T>), grid, dim3(256), 0, s, b, nimg, nblocks, perXcd, cell0, ncells, ncellsM);                    \
+			constexpr int T44 = FastThreads<44, AgastGeom<T>::P, T>::value, T64 = FastThreads<64, AgastGeom<T>::P, T>::value;                                                 \
+			if (cellMaxA <= 44) hipLaunchKernelGGL((k_fast_cells<44, T44, AgastGeom<T>::P, T>), grid, dim3(T44), 0, s, b, nimg, nblocks, perXcd, cell0, ncells, ncellsM);   \
+			else hipLaunchKernelGGL((k_fast_cells<64, T64, AgastGeom<T>::P, T>), grid, dim3(T64), 0, s, b, nimg, nblocks, perXcd, cell0, ncells, ncellsM);                    \
 		} while (0)
 		if (hd.agast == 0) MCS_AGAST_LAUNCH(0);
 		else if (hd.agast == 1) MCS_AGAST_LAUNCH(1);
