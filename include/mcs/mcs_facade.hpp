@@ -1162,6 +1162,70 @@ struct cOptimizer {
 		inliers = share[0];
 		return r[0];
 	}
+
+	// cOptimizer::OptimizeSim3 (src/cOptimizerLoopStuff.cpp:58-264) over mcs_sim3_optimize (host kind), with the reference's signature: vpMatches1 is nulled
+	// in place where the reference nulls it, g2oS12 receives the optimised estimate (and is left alone on the `return 0` path, :234-235), the inlier count is
+	// returned.  KF: camSystem (a cMultiCamSys_ of this header; M_c and the cameras of pKF1 serve both sides, M_t of each), GetMapPointMatches() (a vector
+	// of MP*), GetKeyPoint(i) (ptx, pty, octave), GetInvSigma2(level), GetSigma2(level), keypoint_to_cam (find(i)->second).  MP: isBad(),
+	// GetIndexInKeyFrame(KF*) (a vector of indices, the first is used), GetWorldPos() (indexable by 0..2).  Reproduced: the information
+	// of the second edge is GetSigma2, not its inverse (:188); e12 projects with pKF1's camera of feature i2 and e21 with pKF2's camera of feature i (the
+	// point vertex an edge holds carries the other side's index).  Chosen: a match that pKF2 does not observe is skipped like i2 < 0 (the reference indexes
+	// an empty vector); a crossed index that the other keyframe's keypoint_to_cam does not hold throws (the reference dereferences end()).
+	struct Sim3 {   // g2o::Sim3: built from (R, t, s) as cLoopClosing::ComputeSim3 builds it; q (x y z w, not normalised) is set by an optimisation
+		double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t[3] = {0, 0, 0}, s = 1.0, q[4] = {0, 0, 0, 1};
+	};
+	static double& stdSim() { static double v = 4.0; return v; }   // cOptimizer::stdSim (:55)
+	template <class KF, class MP>
+	static int OptimizeSim3(Context& ctx, KF* pKF1, KF* pKF2, std::vector<MP*>& vpMatches1, Sim3& g2oS12, mcs_sim3opt_diag* diag = nullptr) {
+		cMultiCamSys_& cs = pKF1->camSystem;
+		const size_t nr = (size_t)cs.GetNrCams();
+		const std::vector<MP*> vpMapPoints1 = pKF1->GetMapPointMatches();
+		std::vector<double> Xw, obs, w;
+		std::vector<int32_t> cam;
+		std::vector<size_t> at;
+		for (size_t i = 0; i < vpMatches1.size(); ++i) {   // :117-199
+			MP* pMP2 = vpMatches1[i];
+			if (!pMP2) continue;
+			MP* pMP1 = vpMapPoints1[i];
+			const auto idx2 = pMP2->GetIndexInKeyFrame(pKF2);
+			if (!pMP1 || idx2.empty() || pMP1->isBad() || pMP2->isBad() || (long long)idx2[0] < 0) continue;
+			const size_t i2 = (size_t)idx2[0];
+			const auto c1 = pKF1->keypoint_to_cam.find(i2), c2 = pKF2->keypoint_to_cam.find(i);
+			if (c1 == pKF1->keypoint_to_cam.end() || c2 == pKF2->keypoint_to_cam.end()) throw std::runtime_error("OptimizeSim3: a crossed feature index has no camera");
+			const auto X1 = pMP1->GetWorldPos();
+			const auto X2 = pMP2->GetWorldPos();
+			for (int k = 0; k < 3; ++k) Xw.push_back((double)X1[k]);
+			for (int k = 0; k < 3; ++k) Xw.push_back((double)X2[k]);
+			cam.push_back((int32_t)c1->second); cam.push_back((int32_t)c2->second);
+			const auto k1 = pKF1->GetKeyPoint(i);
+			const auto k2 = pKF2->GetKeyPoint(i2);
+			obs.push_back((double)k1.ptx); obs.push_back((double)k1.pty); obs.push_back((double)k2.ptx); obs.push_back((double)k2.pty);
+			w.push_back(pKF1->GetInvSigma2(k1.octave)); w.push_back(pKF2->GetSigma2(k2.octave));
+			at.push_back(i);
+		}
+		const size_t n = at.size();
+		std::vector<double> Mc(16 * nr), Mt(32);
+		std::vector<mcs_ocam> oc;
+		for (size_t c = 0; c < nr; ++c) { oc.push_back(cs.camModels[c].ocam); std::memcpy(&Mc[16 * c], cs.M_c[c].data(), 128); }
+		const Matx44d i1 = InvMat(pKF1->camSystem.M_t), i2m = InvMat(pKF2->camSystem.M_t);
+		std::memcpy(&Mt[0], i1.data(), 128); std::memcpy(&Mt[16], i2m.data(), 128);
+		std::vector<uint8_t> keep(std::max<size_t>(n, 1), 1);
+		uint8_t* keeps[1] = {keep.data()};
+		const mcs_sim3opt_problem pr{n ? Xw.data() : nullptr, n ? cam.data() : nullptr, n ? obs.data() : nullptr, n ? w.data() : nullptr, (int32_t)n};
+		const double std1 = stdSim();
+		double S12[8], Ro[9];
+		int32_t nin = 0;
+		mcs_sim3opt_diag d{};
+		mcs_throw(mcs_sim3_optimize(ctx.h, 1, &pr, Mc.data(), oc.data(), (int)nr, Mt.data(), &std1, g2oS12.R, g2oS12.t, &g2oS12.s, MCS_MEM_HOST, S12, Ro, keeps, &nin, &d));
+		if (diag) *diag = d;
+		for (size_t k = 0; k < n; ++k)
+			if (!keep[k]) vpMatches1[at[k]] = nullptr;   // :219, :253
+		if (d.status == MCS_SIM3OPT_OK && d.n_corr - d.n_bad1 >= 3) {   // :260-261; not on the return-0 path
+			std::copy(S12, S12 + 4, g2oS12.q); std::copy(S12 + 4, S12 + 7, g2oS12.t); g2oS12.s = S12[7];
+			std::copy(Ro, Ro + 9, g2oS12.R);
+		}
+		return nin;
+	}
 };
 
 // ---------------------------------------------------------------------------------------------- the local map and the covisibility counts

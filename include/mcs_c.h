@@ -37,7 +37,7 @@ extern "C" {
  * 9: the keyframe database mcs_kfdb_*, mcs_vocabulary_set_words, mcs_bow_vector; 10: the Sim3 RANSAC mcs_sim3_*).  Purely additive
  * entry points leave it alone: mcs_triangulate_matches / mcs_create_new_map_points and mcs_frustum / mcs_search_local_points arrived within revision 10, as did the
  * covisibility store mcs_covis_* with mcs_gather_rows / mcs_scatter_rows and its culling calls mcs_covis_set_keyframe_octaves / _cull_keyframes / _observations / _cull_points
- * and mcs_pose_optimization (look them up with dlsym).  mcs_abi_version() returns the value the LIBRARY was built with: compare it with MCS_ABI_VERSION after dlopen. */
+ * and mcs_pose_optimization and mcs_sim3_optimize (look them up with dlsym).  mcs_abi_version() returns the value the LIBRARY was built with: compare it with MCS_ABI_VERSION after dlopen. */
 #define MCS_ABI_VERSION 10
 
 #define MCS_MAX_POLY 16
@@ -646,6 +646,45 @@ typedef struct { int32_t status, iters[2], stop[2]; int32_t trials[2][10]; int32
 int mcs_pose_optimization(mcs_ctx*, int nproblems, const mcs_pose_frame* frames, const mcs_point_table* pts, const double* M_c_min, const mcs_ocam* cams,
                           int nr_cams, const double* inv_level_sigma2, int nlevels, const double* huber_multiplier, mcs_mem_kind kind, double* pose_min,
                           double* MtMc, double* MtMc_inv, uint8_t* const* outlier, int32_t* n_inliers, double* outlier_share, mcs_pose_diag* diag);
+
+/* ------------------------------------------------------------------ a loop candidate's Sim3, optimised on the device
+ *   int cOptimizer::OptimizeSim3(cMultiKeyFrame* pKF1, cMultiKeyFrame* pKF2, vector<cMapPoint*>& vpMatches1, g2o::Sim3& g2oS12)
+ *       (src/cOptimizerLoopStuff.cpp:58-264), step 3 of cLoopClosing::ComputeSim3 (src/cLoopClosing.cpp:300-367), once per candidate keyframe
+ * for a BATCH of independent candidates over ONE local rig, one workgroup per problem, both rounds of the reference's g2o run in one launch.  DESIGN.md 4m
+ * restates the algorithm (Levenberg-Marquardt over the 7 numbers of g2o::Sim3's exponential map, the NUMERIC Jacobian of g2o's binary edge with steps of 1e-9,
+ * Huber kernel with delta = 1.345 * std_sim, the terminate action with gain 1e-6, the two tests) and section 7 lists what is reproduced rather than repaired.
+ *   M_c [nr_cams][16]  Get_M_c(c), row-major 4x4, and cams: the rig of BOTH keyframes, as in mcs_sim3_create (the reference reads each keyframe's own copy,
+ *                      camSys1 / camSys2, which hold the same calibration).
+ *   problems[p]        n correspondences in the order the reference's loop keeps them (:117-199: vpMatches1[i] set, both points good, i2 >= 0):
+ *                      Xw  [n][2][3]  GetWorldPos() of pMP1 (= pKF1's point of feature i) and of pMP2 (= vpMatches1[i])
+ *                      cam [n][2]     the camera edge e12 projects with, then the camera edge e21 projects with.  The reference looks e12's up as
+ *                                     pKF1->keypoint_to_cam[i2] and e21's as pKF2->keypoint_to_cam[i]: the feature indices are CROSSED (the point vertex an
+ *                                     edge holds carries the other side's index).  That quirk lives in the wrappers that build this array.
+ *                      obs [n][2][2]  GetKeyPoint(i).pt of pKF1 and GetKeyPoint(i2).pt of pKF2, float widened to double
+ *                      w   [n][2]     the two information factors exactly as the caller's keyframes give them: pKF1->GetInvSigma2(octave1) and — the
+ *                                     reference's :188 — pKF2->GetSigma2(octave2), NOT its inverse.  That quirk too lives in the wrappers.
+ *   M_t_inv [p][2][16] invMat(Get_M_t()) of pKF1 and pKF2; std_sim [p]: cOptimizer::stdSim (default 4.0); R12 [p][9] row-major, t12 [p][3], s12 [p]: the
+ *                      start, what mcs_sim3_best returns; the vertex starts from Sim3(R, t, s), i.e. Eigen's Quaterniond(R).
+ *   S12 [p][8]         out, in g2o::Sim3::operator[] order: qx qy qz qw tx ty tz s (the quaternion is never normalised, as in the reference).
+ *   R12_out [p][9]     optional: r.toRotationMatrix(), row-major.
+ *   keep[p]            [problems[p].n] bytes, fully written: 1 = vpMatches1[i] stays, 0 = it is set to NULL.  The table `keep` itself is a host array.
+ *   n_inliers [p]      the return value.  On the `return 0` path (fewer than 3 correspondences left after round one, none at all included) S12 holds the
+ *                      INPUT estimate, converted, although the bad matches of round one stay nulled.
+ *   diag               optional, [nproblems]: n_corr = nCorrespondences, n_bad1 = nBad of round one, the rest as in mcs_pose_diag (round one has 5 iterations,
+ *                      round two 10 if n_bad1 > 0, else 5).
+ * A problem whose first evaluation holds a non-finite residual, Jacobian entry, weight, Huber delta or sum is not optimised: status MCS_SIM3OPT_NONFINITE,
+ * S12 = the input converted, keep all 1, n_inliers = n_corr (a status, not an error, for either kind).  Guards: a camera outside [0, nr_cams) is refused
+ * with MCS_ERR_INVALID in host kind before anything runs; in device kind that correspondence gives no edge pair (keep stays 1).  n <= 65536, nr_cams <= 32.
+ * nproblems = 0 is a successful no-op.  DEVICE: the call only enqueues on the context's stream — no host wait, nothing read back; it needs no scratch.
+ * HOST: through the staging block.  A problem's result does not depend on nproblems, on its place in the batch or on the run (sums over the edges run in a
+ * fixed order, without floating-point atomics).  Refused with MCS_ERR_UNSUPPORTED while deferred searches are on (mcs_ctx_set_async_search). */
+#define MCS_SIM3OPT_OK 0
+#define MCS_SIM3OPT_NONFINITE 1
+typedef struct { const double* Xw; const int32_t* cam; const double* obs; const double* w; int32_t n; } mcs_sim3opt_problem;
+typedef struct { int32_t status, n_corr, n_bad1, iters[2], stop[2]; int32_t trials[2][10]; int32_t pad; double lambda, chi2; } mcs_sim3opt_diag;
+int mcs_sim3_optimize(mcs_ctx*, int nproblems, const mcs_sim3opt_problem* problems, const double* M_c, const mcs_ocam* cams, int nr_cams,
+                      const double* M_t_inv, const double* std_sim, const double* R12, const double* t12, const double* s12, mcs_mem_kind kind,
+                      double* S12, double* R12_out, uint8_t* const* keep, int32_t* n_inliers, mcs_sim3opt_diag* diag);
 
 /* ------------------------------------------------------------------ the local map and the covisibility counts on the device
  * cTracking::UpdateReferenceKeyFrames + UpdateReferencePoints (src/cTracking.cpp:1024-1123), the first step of TrackLocalMap, and the counting and ordering of

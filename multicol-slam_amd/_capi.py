@@ -78,7 +78,7 @@ EXPORTS = [
     "mcs_sim3_hypotheses", "mcs_sim3_draw",
     "mcs_triangulate_matches", "mcs_create_new_map_points",
     "mcs_frustum", "mcs_search_local_points",
-    "mcs_search_last_frame", "mcs_window_search_frames", "mcs_pose_optimization",
+    "mcs_search_last_frame", "mcs_window_search_frames", "mcs_pose_optimization", "mcs_sim3_optimize",
     "mcs_covis_create", "mcs_covis_destroy", "mcs_covis_clear", "mcs_covis_size", "mcs_covis_slots", "mcs_covis_set_keyframe", "mcs_covis_set_keyframe_pose",
     "mcs_covis_erase_keyframe", "mcs_covis_set_keyframe_bad", "mcs_covis_set_points_bad", "mcs_covis_update_reference", "mcs_covis_update_connections",
     "mcs_gather_rows", "mcs_scatter_rows",
@@ -160,6 +160,15 @@ class PoseDiag(C.Structure):   # mcs_pose_diag
 
 POSE_DIAG_DTYPE = np.dtype([("status", "<i4"), ("iters", "<i4", 2), ("stop", "<i4", 2), ("trials", "<i4", (2, 10)), ("pad", "<i4"), ("lam", "<f8"), ("chi2", "<f8")])
 POSE_OK, POSE_NONFINITE = 0, 1   # MCS_POSE_* of include/mcs_c.h
+
+
+class Sim3OptProblem(C.Structure):   # mcs_sim3opt_problem: one candidate of mcs_sim3_optimize
+    _fields_ = [("Xw", C.c_void_p), ("cam", C.c_void_p), ("obs", C.c_void_p), ("w", C.c_void_p), ("n", C.c_int32)]
+
+
+SIM3OPT_DIAG_DTYPE = np.dtype([("status", "<i4"), ("n_corr", "<i4"), ("n_bad1", "<i4"), ("iters", "<i4", 2), ("stop", "<i4", 2), ("trials", "<i4", (2, 10)),
+                               ("pad", "<i4"), ("lam", "<f8"), ("chi2", "<f8")])   # mcs_sim3opt_diag
+SIM3OPT_OK, SIM3OPT_NONFINITE = 0, 1   # MCS_SIM3OPT_* of include/mcs_c.h
 
 
 _lib = None
@@ -269,6 +278,7 @@ def lib():
                                            C.c_int, C.c_int, vp, vp, vp]
     L.mcs_pose_optimization.argtypes = [vp, C.c_int, C.POINTER(PoseFrame), C.POINTER(PointTable), vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp,
                                         C.POINTER(vp), vp, vp, vp]
+    L.mcs_sim3_optimize.argtypes = [vp, C.c_int, C.POINTER(Sim3OptProblem), vp, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, C.POINTER(vp), vp, vp]
     L.mcs_covis_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
     L.mcs_covis_destroy.argtypes = [vp]
     L.mcs_covis_clear.argtypes = [vp]

@@ -323,9 +323,13 @@ class cMultiKeyFrame:
         self.mBowVec, self.mFeatVec = getattr(F, "mBowVec", None), getattr(F, "mFeatVec", None)
         self.mvpOrderedConnectedKeyFrames = []
         self.mvLevelSigma2 = list(getattr(F, "mvLevelSigma2", [1.0]))
+        self.mvInvLevelSigma2 = list(getattr(F, "mvInvLevelSigma2", [1 / s for s in self.mvLevelSigma2]))
 
     def GetSigma2(self, nLevel=1):                  # include/cMultiKeyFrame.h:162-163
         return self.mvLevelSigma2[nLevel]
+
+    def GetInvSigma2(self, nLevel=1):               # include/cMultiKeyFrame.h:165-166
+        return self.mvInvLevelSigma2[nLevel]
 
     def GetKeyPoint(self, idx):
         return self.mvKeys[idx]
@@ -1751,3 +1755,91 @@ def PoseOptimization(F, points, huberMultiplier=1.0, device=False, ctx=None):
     """int cOptimizer::PoseOptimization(cMultiFrame* pFrame, double& inliers, const double& huberMultiplier) -> (the return value, `inliers`): the second is the
     reference's out-parameter, which is the OUTLIER share nBad / nInitialCorrespondences (src/cOptimizer.cpp:454-456)."""
     return PoseOptimizationBatch([F], points, huberMultiplier, device, ctx)[0]
+
+
+# ---------------------------------------------------------------------------------------------- a loop candidate's Sim3 (mcs_sim3_optimize)
+class Sim3:
+    """g2o::Sim3 as OptimizeSim3 takes and leaves it.  Built from (R, t, s) like the g2o::Sim3 of cLoopClosing::ComputeSim3; after an optimisation q holds the
+    quaternion in coeffs() order (x, y, z, w; not normalised, as in the reference), R its toRotationMatrix(), t and s the rest."""
+
+    def __init__(self, R, t, s):
+        self.R, self.t, self.s = np.asarray(R, np.float64).reshape(3, 3).copy(), np.asarray(t, np.float64).reshape(3).copy(), float(s)
+        self.q = None
+
+
+def OptimizeSim3Batch(problems, camSystem, device=False, ctx=None, diag=False):
+    """cOptimizer::OptimizeSim3 (src/cOptimizerLoopStuff.cpp:58-264) for a list of candidates over one rig (camSystem: M_c and the cameras), as ONE call
+    (mcs_sim3_optimize).  problems: dicts with Xw [n][2][3], cam [n][2], obs [n][2][2], w [n][2] (include/mcs_c.h says what each holds), Mt_inv [2][4][4],
+    R12, t12, s12 and optionally std_sim (default 4.0, cOptimizer::stdSim).  device=True: every array in device memory, nothing read back before the call has
+    returned.  -> a list of dicts: S12 [8] (qx qy qz qw tx ty tz s), R12 [3][3], keep [n] (1 = the match stays), n_inliers; diag=True: (that list, the
+    mcs_sim3opt_diag records)"""
+    from ._capi import SIM3OPT_DIAG_DTYPE, Sim3OptProblem
+    ctx = ctx or default_context()
+    npb = len(problems)
+    if npb == 0:
+        check(lib().mcs_sim3_optimize(ctx.h, 0, None, None, None, 0, None, None, None, None, None, MEM_HOST, None, None, None, None, None))
+        return ([], np.zeros(0, SIM3OPT_DIAG_DTYPE)) if diag else []
+    mem = _DEVICE if device else _HOST
+    nr = camSystem.GetNrCams()
+    ocs = (type(camSystem.cams[0].ocam) * nr)(*[cm.ocam for cm in camSystem.cams])
+    f8 = lambda k, shape: np.ascontiguousarray([np.asarray(p[k], np.float64).reshape(shape) for p in problems], np.float64)
+    g = dict(Mc=np.ascontiguousarray([np.asarray(camSystem.M_c[c], np.float64).reshape(16) for c in range(nr)], np.float64), ocs=np.frombuffer(ocs, np.uint8).copy(),
+             Mt=f8("Mt_inv", 32), std=np.array([float(p.get("std_sim", 4.0)) for p in problems], np.float64), R=f8("R12", 9), t=f8("t12", 3),
+             s=np.array([float(p["s12"]) for p in problems], np.float64), S=np.zeros((npb, 8)), Ro=np.zeros((npb, 9)), nin=np.zeros(npb, np.int32),
+             diag=np.zeros(npb, SIM3OPT_DIAG_DTYPE))
+    g = {k: mem.put(v) for k, v in g.items()}
+    ns = [len(np.asarray(p["cam"]).reshape(-1, 2)) for p in problems]
+    per = [dict(Xw=mem.put(np.ascontiguousarray(p["Xw"], np.float64).reshape(-1)), cam=mem.put(np.ascontiguousarray(p["cam"], np.int32).reshape(-1)),
+                obs=mem.put(np.ascontiguousarray(p["obs"], np.float64).reshape(-1)), w=mem.put(np.ascontiguousarray(p["w"], np.float64).reshape(-1)),
+                keep=mem.put(np.zeros(max(n, 1), np.uint8))) for p, n in zip(problems, ns)]
+    pr = (Sim3OptProblem * npb)(*[Sim3OptProblem(mem.ptr(q["Xw"]) if n else None, mem.ptr(q["cam"]) if n else None, mem.ptr(q["obs"]) if n else None,
+                                                 mem.ptr(q["w"]) if n else None, n) for q, n in zip(per, ns)])
+    outs = (C.c_void_p * npb)(*[mem.ptr(q["keep"]) for q in per])
+    check(lib().mcs_sim3_optimize(ctx.h, npb, pr, mem.ptr(g["Mc"]), mem.ptr(g["ocs"]), nr, mem.ptr(g["Mt"]), mem.ptr(g["std"]), mem.ptr(g["R"]), mem.ptr(g["t"]),
+                                  mem.ptr(g["s"]), mem.kind, mem.ptr(g["S"]), mem.ptr(g["Ro"]), outs, mem.ptr(g["nin"]), mem.ptr(g["diag"])))
+    # ---- only now the host looks at anything
+    S, Ro, nin = (mem.read(g[k]) for k in ("S", "Ro", "nin"))
+    res = [dict(S12=S[p].copy(), R12=Ro[p].reshape(3, 3).copy(), keep=mem.read(per[p]["keep"])[:ns[p]].copy(), n_inliers=int(nin[p])) for p in range(npb)]
+    return (res, mem.read(g["diag"])) if diag else res
+
+
+def _sim3_correspondences(pKF1, pKF2, vpMatches1, stdSim):
+    """the pointer tests of src/cOptimizerLoopStuff.cpp:117-199 -> (the problem's arrays, the index into vpMatches1 of each correspondence).  Reproduced: e12
+    projects with pKF1's camera of feature i2 and e21 with pKF2's camera of feature i (the point vertex an edge holds carries the other side's index), and the
+    information of e21 is GetSigma2, not its inverse (:188).  A match that pKF2 does not observe (GetIndexInKeyFrame empty: the reference indexes an empty
+    vector) is skipped like i2 < 0; a crossed index beyond the other keyframe's features (the reference dereferences find() == end()) is an IndexError."""
+    vp1 = pKF1.GetMapPointMatches()
+    Xw, cam, obs, w, at = [], [], [], [], []
+    for i, mp2 in enumerate(vpMatches1):
+        if mp2 is None:
+            continue
+        mp1 = vp1[i]
+        idx2 = mp2.GetIndexInKeyFrame(pKF2)
+        if mp1 is None or not idx2 or mp1.isBad() or mp2.isBad() or idx2[0] < 0:
+            continue
+        i2 = int(idx2[0])
+        k1, k2 = pKF1.GetKeyPoint(i), pKF2.GetKeyPoint(i2)
+        Xw.append([np.asarray(mp1.GetWorldPos(), np.float64).reshape(-1)[:3], np.asarray(mp2.GetWorldPos(), np.float64).reshape(-1)[:3]])
+        cam.append([int(pKF1.keypoint_to_cam[i2]), int(pKF2.keypoint_to_cam[i])])
+        obs.append([[float(k1["x"]), float(k1["y"])], [float(k2["x"]), float(k2["y"])]])
+        w.append([float(pKF1.GetInvSigma2(int(k1["octave"]))), float(pKF2.GetSigma2(int(k2["octave"])))])
+        at.append(i)
+    n = len(at)
+    return dict(Xw=np.asarray(Xw, np.float64).reshape(n, 2, 3), cam=np.asarray(cam, np.int32).reshape(n, 2), obs=np.asarray(obs, np.float64).reshape(n, 2, 2),
+                w=np.asarray(w, np.float64).reshape(n, 2), Mt_inv=[_inv_mat(pKF1.camSystem.M_t), _inv_mat(pKF2.camSystem.M_t)], std_sim=stdSim), at
+
+
+def OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, stdSim=4.0, device=False, ctx=None):
+    """int cOptimizer::OptimizeSim3(cMultiKeyFrame*, cMultiKeyFrame*, vector<cMapPoint*>& vpMatches1, g2o::Sim3& g2oS12) -> the return value.  vpMatches1 is
+    nulled in place (None) where the reference nulls it; g2oS12 (a Sim3 built from R, t, s) gets q, R, t, s of the optimised estimate, and is left as it
+    was on the `return 0` path.  stdSim: cOptimizer::stdSim."""
+    pr, at = _sim3_correspondences(pKF1, pKF2, vpMatches1, stdSim)
+    pr.update(R12=g2oS12.R, t12=g2oS12.t, s12=g2oS12.s)
+    res, dg = OptimizeSim3Batch([pr], pKF1.camSystem, device, ctx, diag=True)
+    r, d = res[0], dg[0]
+    for k, i in zip(r["keep"], at):
+        if not k:
+            vpMatches1[i] = None
+    if d["status"] == 0 and d["n_corr"] - d["n_bad1"] >= 3:   # not the return-0 path (:234-235): g2oS12 = vSim3_recov->estimate() (:260-261)
+        g2oS12.q, g2oS12.R, g2oS12.t, g2oS12.s = r["S12"][:4].copy(), r["R12"], r["S12"][4:7].copy(), float(r["S12"][7])
+    return r["n_inliers"]
