@@ -20,6 +20,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <list>
 #include <map>
 #include <set>
 #include <sstream>
@@ -1225,6 +1226,104 @@ struct cOptimizer {
 			std::copy(Ro, Ro + 9, g2oS12.R);
 		}
 		return nin;
+	}
+
+	// cOptimizer::LocalBundleAdjustment (src/cOptimizer.cpp:461-874) over mcs_local_bundle_adjustment (host kind), with the reference's signature less the map,
+	// the iteration count and the covariance switch, which it does not read: builds lLocalKeyFrames, lLocalMapPoints and lFixedCameras and the fixing rules
+	// (:473-529, :555-595), runs the call, applies the erasures (EraseMapPointMatch + EraseObservation), the bad flags, the positions and the poses, and returns
+	// lLocalKeyFrames (empty when there is at most one, :489).  KF: mnId, isBad(), GetVectorCovisibleKeyFrames(), GetMapPointMatches() (vectors of pointers),
+	// camSystem (a cMultiCamSys_ of this header: M_c_min, M_t_min, Set_M_t_from_min), keypoint_to_cam (find(i)->second), GetKeyPoint(i) (ptx, pty, octave),
+	// mvInvLevelSigma2, EraseMapPointMatch(idx).  MP: isBad(), GetObservations() (a map KF* -> vector of feature indices), GetWorldPos() (indexable by 0..2),
+	// SetWorldPos(const double*), EraseObservation(KF*, idx), SetBadFlag().  Where the reference iterates std::map<cMultiKeyFrame*, ...> the order here is
+	// ascending mnId.  pbStopFlag as in the reference: g2o's terminate action WRITES it when round one converges and nothing is then written back (:756-762,
+	// DESIGN.md section 7) — pass nullptr for the call that optimises.  UpdateNormalAndDepth / ComputeDistinctiveDescriptors of the written points (:866-867)
+	// are the caller's (cCovisibility::UpdateMapPoints): `written`, optional, receives them.
+	static double& stdRecon() { static double v = 2.0; return v; }   // cOptimizer::stdRecon
+	template <class KF, class MP = typename std::remove_pointer<typename decltype(std::declval<KF>().GetMapPointMatches())::value_type>::type>
+	static std::list<KF*> LocalBundleAdjustment(Context& ctx, KF* pKF, bool* pbStopFlag = nullptr, mcs_lba_diag* diag = nullptr, std::vector<MP*>* written = nullptr) {
+		std::vector<KF*> local{pKF}, fixed;
+		std::set<KF*> marked{pKF};
+		for (KF* k : pKF->GetVectorCovisibleKeyFrames()) { marked.insert(k); if (!k->isBad()) local.push_back(k); }   // mnBALocalForKF is set on bad ones too (:484)
+		if (local.size() <= 1) return std::list<KF*>();
+		auto observations = [](MP* mp) {   // as std::map<cMultiKeyFrame*, ...> iterates: ascending mnId (the project's convention)
+			std::vector<std::pair<KF*, std::vector<size_t>>> o;
+			for (const auto& kv : mp->GetObservations()) o.emplace_back(kv.first, std::vector<size_t>(kv.second.begin(), kv.second.end()));
+			std::stable_sort(o.begin(), o.end(), [](const std::pair<KF*, std::vector<size_t>>& a, const std::pair<KF*, std::vector<size_t>>& b) { return a.first->mnId < b.first->mnId; });
+			return o;
+		};
+		std::vector<MP*> points;
+		std::set<MP*> seen;
+		for (KF* k : local)
+			for (MP* mp : k->GetMapPointMatches())
+				if (mp && !mp->isBad() && seen.insert(mp).second) points.push_back(mp);
+		for (MP* mp : points)
+			for (const auto& kv : observations(mp))
+				if (marked.insert(kv.first).second && !kv.first->isBad()) fixed.push_back(kv.first);   // mnBAFixedForKF is set before the isBad test (:524-526)
+		std::vector<KF*> kfs(local);
+		kfs.insert(kfs.end(), fixed.begin(), fixed.end());
+		std::vector<uint8_t> isFixed(kfs.size(), 1);
+		bool oneFixed = false;
+		for (size_t i = 0; i < local.size(); ++i) { oneFixed = local[i]->mnId == 0; isFixed[i] = oneFixed ? 1 : 0; }   // :564: overwritten per keyframe
+		if (!oneFixed && fixed.empty()) isFixed[0] = 1;                                                                  // :575-581
+		std::map<KF*, int32_t> slot;
+		for (size_t i = 0; i < kfs.size(); ++i) slot[kfs[i]] = (int32_t)i;
+		std::vector<int32_t> first{0}, ekf, ecam, total, badObs;
+		std::vector<mcs_keypoint> keys;
+		std::vector<std::pair<KF*, size_t>> at;
+		std::vector<size_t> ptOf;
+		std::vector<double> pos;
+		for (size_t p = 0; p < points.size(); ++p) {
+			int32_t t = 0, b = 0;
+			for (const auto& kv : observations(points[p])) {
+				t += (int32_t)kv.second.size();
+				if (kv.first->isBad()) { b += (int32_t)kv.second.size(); continue; }
+				for (size_t i : kv.second) {
+					const auto kp = kv.first->GetKeyPoint(i);
+					mcs_keypoint q{};
+					q.x = kp.ptx; q.y = kp.pty; q.octave = kp.octave;
+					keys.push_back(q);
+					ekf.push_back(slot[kv.first]);
+					ecam.push_back((int32_t)kv.first->keypoint_to_cam.find(i)->second);
+					at.emplace_back(kv.first, i);
+					ptOf.push_back(p);
+				}
+			}
+			first.push_back((int32_t)ekf.size());
+			total.push_back(t); badObs.push_back(b);
+			const auto X = points[p]->GetWorldPos();
+			for (int k = 0; k < 3; ++k) pos.push_back((double)X[k]);
+		}
+		cMultiCamSys_& cs = pKF->camSystem;
+		const size_t nr = (size_t)cs.GetNrCams(), nl = local.size();
+		if (cs.M_c_min.size() != nr) throw std::runtime_error("LocalBundleAdjustment: camSystem.M_c_min is not set");
+		std::vector<double> pose(6 * kfs.size()), McMin(6 * nr), kfT(3 * nl);
+		std::vector<mcs_ocam> oc;
+		for (size_t c = 0; c < nr; ++c) { oc.push_back(cs.camModels[c].ocam); std::copy(cs.M_c_min[c].begin(), cs.M_c_min[c].end(), McMin.begin() + 6 * c); }
+		for (size_t i = 0; i < kfs.size(); ++i) std::copy(kfs[i]->camSystem.M_t_min.begin(), kfs[i]->camSystem.M_t_min.end(), pose.begin() + 6 * i);
+		std::vector<uint8_t> es(std::max<size_t>(ekf.size(), 1), 0), ps(std::max<size_t>(points.size(), 1), 1);
+		first.resize(std::max<size_t>(first.size(), 1));
+		int flag = pbStopFlag && *pbStopFlag ? 1 : 0;
+		mcs_lba_diag d{};
+		const std::vector<double>& sigma = pKF->mvInvLevelSigma2;
+		mcs_throw(mcs_local_bundle_adjustment(ctx.h, (int)kfs.size(), (int)nl, pose.data(), isFixed.data(), kfT.data(), (int)points.size(), pos.data(), first.data(),
+		                                      (int)ekf.size(), ekf.data(), ecam.data(), keys.data(), total.data(), badObs.data(), McMin.data(), oc.data(), (int)nr,
+		                                      sigma.data(), (int)sigma.size(), stdRecon(), pbStopFlag ? &flag : nullptr, MCS_MEM_HOST, es.data(), ps.data(), &d));
+		if (pbStopFlag) *pbStopFlag = flag != 0;
+		if (diag) *diag = d;
+		for (size_t e = 0; e < ekf.size(); ++e)
+			if (es[e]) { at[e].first->EraseMapPointMatch(at[e].second); points[ptOf[e]]->EraseObservation(at[e].first, at[e].second); }   // :777-778, :810-811
+		for (size_t p = 0; p < points.size(); ++p) {
+			if (ps[p] == 2) points[p]->SetBadFlag();
+			else if (ps[p] == 0) { points[p]->SetWorldPos(&pos[3 * p]); if (written) written->push_back(points[p]); }   // :865
+		}
+		if (d.status == MCS_LBA_OK)
+			for (size_t i = 0; i < nl; ++i) {
+				if (local[i]->isBad()) continue;
+				std::array<double, 6> m;
+				std::copy(pose.begin() + 6 * i, pose.begin() + 6 * i + 6, m.begin());
+				local[i]->camSystem.Set_M_t_from_min(m);   // :833
+			}
+		return std::list<KF*>(local.begin(), local.end());
 	}
 };
 

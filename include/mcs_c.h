@@ -686,6 +686,61 @@ int mcs_sim3_optimize(mcs_ctx*, int nproblems, const mcs_sim3opt_problem* proble
                       const double* M_t_inv, const double* std_sim, const double* R12, const double* t12, const double* s12, mcs_mem_kind kind,
                       double* S12, double* R12_out, uint8_t* const* keep, int32_t* n_inliers, mcs_sim3opt_diag* diag);
 
+/* ------------------------------------------------------------------ local bundle adjustment on the device
+ *   std::list<cMultiKeyFrame*> cOptimizer::LocalBundleAdjustment(cMultiKeyFrame* pKF, cMap*, int, bool, bool* pbStopFlag)   (src/cOptimizer.cpp:461-874),
+ *       the step of cLocalMapping::Run between the searches and the culling (src/cLocalMapping.cpp:99)
+ * as ONE problem over the whole device: both rounds of the reference's g2o run (optimize(10), the first pass at chi2 > thHuber^2, optimize(15), the second pass,
+ * the write-back) over the poses of the free keyframes and the positions of the local map points, the points marginalised (Schur complement).  DESIGN.md 4n
+ * restates the algorithm and names the kernels; section 7 lists what is reproduced rather than repaired.  Who is local, who is fixed and what happens to the map
+ * stay with the caller (frontend.LocalBundleAdjustment, the facade): the call takes arrays, each where `kind` says unless stated.
+ *   kf_pose_min [n_kfs][6]  in/out: Get_M_t_min() of every keyframe vertex, the n_local keyframes of lLocalKeyFrames first, then lFixedCameras.  Out: the poses
+ *                           of the n_local first (a fixed one keeps its value); kf_t [n_local][3], optional: Hom2T of the new pose, what
+ *                           mcs_covis_set_keyframe_pose takes.
+ *   kf_fixed [n_kfs]        bytes, non-zero = the vertex is fixed (the rules of :556-595 are the caller's).
+ *   pos [n_points][3]       in/out: GetWorldPos() of the good local points in the reference's order; written where pt_state says so.
+ *   pt_first [n_points + 1] the edges of point p are [pt_first[p], pt_first[p + 1]) in the order the reference adds them (:685-735: keyframes in ascending mnId,
+ *                           a keyframe's features in vector order; bad keyframes give no edge).  Per edge: edge_kf (index into the keyframe list), edge_cam,
+ *                           edge_key (pt and octave are read).
+ *   pt_total_obs [n_points] optional: every observation of the point, those at bad keyframes included — what EraseObservation counts (src/cMapPoint.cpp:
+ *                           139-145); NULL: the number of edges.  pt_bad_obs, optional: those of them that lie at bad keyframes (TotalNrObservations of the
+ *                           write-back, :856, skips them); NULL: none.
+ *   M_c_min, cams, nr_cams, inv_level_sigma2, nlevels   the rig, as in mcs_pose_optimization.  std_recon: cOptimizer::stdRecon; thHuber = 1.345 * std_recon.
+ *   stop_flag               HOST int, in/out, may be NULL: pbStopFlag.  The reference hands it to g2o (setForceStopFlag), whose terminate action then WRITES it
+ *                           when the gain test fires (core/sparse_optimizer_terminate_action.cpp:64-72): with a flag given, a first round that ends on the
+ *                           gain test leaves *stop_flag = 1 and the call returns status MCS_LBA_STOPPED with every output as it came in (:756-762) — as does
+ *                           a flag that is set on entry (:739) or found set after round one.  The flag is read before every Levenberg trial and where
+ *                           optimize() tests terminate().  NULL is the call that optimises: the action's own flag ends round one, round two then runs no
+ *                           iteration (it is never cleared), both passes and the write-back happen.
+ *   edge_state [n_edges]    out: 0 kept, 1 erased by the first pass, 2 by the second (EraseMapPointMatch + EraseObservation are the caller's to apply).  A pass
+ *                           is sequential inside a point: an erasure that leaves fewer than 2 observations makes the point bad and shields the edges behind it.
+ *   pt_state [n_points]     out: 0 written back (pos holds the new position: the point is good, has more than one observation left outside bad keyframes and
+ *                           held at least 2 edges), 1 not written, 2 the point went bad.
+ *   diag                    HOST, optional.  status: MCS_LBA_*.  iters / stop / trials / lambda / chi2 as in mcs_pose_diag (round two has up to 15 iterations);
+ *                           n_free = free pose vertices; n_edges1 = edges that passed the guards; n_erased[r] = erasures of pass r.
+ * Statuses that optimise nothing and write nothing: MCS_LBA_TOO_FEW (n_local < 2, :489), MCS_LBA_STOPPED, MCS_LBA_NO_FREE_POSE (a choice: g2o's behaviour with
+ * an empty pose block was not established), MCS_LBA_NONFINITE (the first evaluation holds a non-finite residual, Jacobian entry, weight, delta or sum), and
+ * MCS_LBA_FAILED in round one (no edge: optimize() returns Fail, :750).  MCS_LBA_FAILED in round two (pass one erased every edge, :788) writes edge_state and
+ * the bad points of pass one, no pose and no position.
+ * Refused with MCS_ERR_CAPACITY before anything runs: more than 64 free keyframes (the reduced system is at most 384 x 384), nr_cams > 32, n_kfs > 4096,
+ * n_points > 2^20, n_edges > 2^22.  Guards: a keyframe index, camera or octave out of range or a pt_first that is not monotone within [0, n_edges] is
+ * MCS_ERR_INVALID in host kind before anything runs; in device kind such an edge (every edge of such a point) contributes nothing.  Refused with
+ * MCS_ERR_UNSUPPORTED while deferred searches are on.
+ * FP64 without contraction, no floating-point atomic, every sum in an order that the problem alone decides: the same call twice is bit-identical.  The phases are
+ * separate launches; the host waits for the stream once per Levenberg trial (that is where stop_flag is honoured) and reads a 64-byte record of the decisions
+ * the device took.  In device kind kf_fixed is read back once, before anything runs.  Scratch comes from the context's grow-only block. */
+#define MCS_LBA_OK 0
+#define MCS_LBA_NONFINITE 1
+#define MCS_LBA_STOPPED 2
+#define MCS_LBA_NO_FREE_POSE 3
+#define MCS_LBA_FAILED 4
+#define MCS_LBA_TOO_FEW 5
+typedef struct { int32_t status, iters[2], stop[2]; int32_t trials[2][15]; int32_t n_free, n_edges1, n_erased[2]; int32_t pad; double lambda, chi2; } mcs_lba_diag;
+int mcs_local_bundle_adjustment(mcs_ctx*, int n_kfs, int n_local, double* kf_pose_min, const uint8_t* kf_fixed, double* kf_t, int n_points, double* pos,
+                                const int32_t* pt_first, int n_edges, const int32_t* edge_kf, const int32_t* edge_cam, const mcs_keypoint* edge_key,
+                                const int32_t* pt_total_obs, const int32_t* pt_bad_obs, const double* M_c_min, const mcs_ocam* cams, int nr_cams,
+                                const double* inv_level_sigma2, int nlevels, double std_recon, int* stop_flag, mcs_mem_kind kind, uint8_t* edge_state,
+                                uint8_t* pt_state, mcs_lba_diag* diag);
+
 /* ------------------------------------------------------------------ the local map and the covisibility counts on the device
  * cTracking::UpdateReferenceKeyFrames + UpdateReferencePoints (src/cTracking.cpp:1024-1123), the first step of TrackLocalMap, and the counting and ordering of
  * cMultiKeyFrame::UpdateConnections (src/cMultiKeyFrame.cpp:406-500) over a device-resident observation store: one row of map point ids per keyframe.

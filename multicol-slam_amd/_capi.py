@@ -78,7 +78,7 @@ EXPORTS = [
     "mcs_sim3_hypotheses", "mcs_sim3_draw",
     "mcs_triangulate_matches", "mcs_create_new_map_points",
     "mcs_frustum", "mcs_search_local_points",
-    "mcs_search_last_frame", "mcs_window_search_frames", "mcs_pose_optimization", "mcs_sim3_optimize",
+    "mcs_search_last_frame", "mcs_window_search_frames", "mcs_pose_optimization", "mcs_sim3_optimize", "mcs_local_bundle_adjustment",
     "mcs_covis_create", "mcs_covis_destroy", "mcs_covis_clear", "mcs_covis_size", "mcs_covis_slots", "mcs_covis_set_keyframe", "mcs_covis_set_keyframe_pose",
     "mcs_covis_erase_keyframe", "mcs_covis_set_keyframe_bad", "mcs_covis_set_points_bad", "mcs_covis_update_reference", "mcs_covis_update_connections",
     "mcs_gather_rows", "mcs_scatter_rows",
@@ -169,6 +169,17 @@ class Sim3OptProblem(C.Structure):   # mcs_sim3opt_problem: one candidate of mcs
 SIM3OPT_DIAG_DTYPE = np.dtype([("status", "<i4"), ("n_corr", "<i4"), ("n_bad1", "<i4"), ("iters", "<i4", 2), ("stop", "<i4", 2), ("trials", "<i4", (2, 10)),
                                ("pad", "<i4"), ("lam", "<f8"), ("chi2", "<f8")])   # mcs_sim3opt_diag
 SIM3OPT_OK, SIM3OPT_NONFINITE = 0, 1   # MCS_SIM3OPT_* of include/mcs_c.h
+
+
+class LbaDiag(C.Structure):   # mcs_lba_diag
+    _fields_ = [("status", C.c_int32), ("iters", C.c_int32 * 2), ("stop", C.c_int32 * 2), ("trials", (C.c_int32 * 15) * 2), ("n_free", C.c_int32),
+                ("n_edges1", C.c_int32), ("n_erased", C.c_int32 * 2), ("pad", C.c_int32), ("lam", C.c_double), ("chi2", C.c_double)]
+
+
+LBA_DIAG_DTYPE = np.dtype([("status", "<i4"), ("iters", "<i4", 2), ("stop", "<i4", 2), ("trials", "<i4", (2, 15)), ("n_free", "<i4"), ("n_edges1", "<i4"),
+                           ("n_erased", "<i4", 2), ("pad", "<i4"), ("lam", "<f8"), ("chi2", "<f8")])
+LBA_OK, LBA_NONFINITE, LBA_STOPPED, LBA_NO_FREE_POSE, LBA_FAILED, LBA_TOO_FEW = range(6)   # MCS_LBA_* of include/mcs_c.h
+LBA_PT_WRITTEN, LBA_PT_KEPT, LBA_PT_BAD = 0, 1, 2                                           # pt_state of mcs_local_bundle_adjustment
 
 
 _lib = None
@@ -279,6 +290,8 @@ def lib():
     L.mcs_pose_optimization.argtypes = [vp, C.c_int, C.POINTER(PoseFrame), C.POINTER(PointTable), vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp,
                                         C.POINTER(vp), vp, vp, vp]
     L.mcs_sim3_optimize.argtypes = [vp, C.c_int, C.POINTER(Sim3OptProblem), vp, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, C.POINTER(vp), vp, vp]
+    L.mcs_local_bundle_adjustment.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int,
+                                              C.c_double, i32p, C.c_int, vp, vp, vp]
     L.mcs_covis_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
     L.mcs_covis_destroy.argtypes = [vp]
     L.mcs_covis_clear.argtypes = [vp]

@@ -1843,3 +1843,147 @@ def OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, stdSim=4.0, device=False, ctx=N
     if d["status"] == 0 and d["n_corr"] - d["n_bad1"] >= 3:   # not the return-0 path (:234-235): g2oS12 = vSim3_recov->estimate() (:260-261)
         g2oS12.q, g2oS12.R, g2oS12.t, g2oS12.s = r["S12"][:4].copy(), r["R12"], r["S12"][4:7].copy(), float(r["S12"][7])
     return r["n_inliers"]
+
+
+# ---------------------------------------------------------------------------------------------- local bundle adjustment (mcs_local_bundle_adjustment)
+def LocalBundleAdjustmentArrays(kf_pose, kf_fixed, n_local, pos, pt_first, edge_kf, edge_cam, edge_key, Mc_min, cams, inv_sigma2, std_recon=2.0, total_obs=None,
+                                bad_obs=None, stop_flag=None, device=False, ctx=None, with_t=True):
+    """mcs_local_bundle_adjustment over arrays (include/mcs_c.h says what each holds).  cams: camera dicts or Ocam structs.  stop_flag: None (pbStopFlag ==
+    NULL: the call that optimises), a bool, or a one-element list that is read and written in place like the reference's bool*.  device=True: every array in
+    device memory.  -> dict: status, kf_pose [n_kfs][6], kf_t [n_local][3], pos, edge_state, pt_state, diag (an LBA_DIAG_DTYPE record), stop_flag (its value
+    on return, None without one), arrays (the call's arrays where they live: DeviceArray objects in device kind, for a chain without a host visit)"""
+    from ._capi import LBA_DIAG_DTYPE, LbaDiag, Ocam
+    ctx = ctx or default_context()
+    mem = _DEVICE if device else _HOST
+    kf_pose = np.ascontiguousarray(kf_pose, np.float64).reshape(-1, 6)
+    pos = np.ascontiguousarray(pos, np.float64).reshape(-1, 3)
+    nk, P, E, nr = len(kf_pose), len(pos), len(edge_kf), len(cams)
+    ocs = (Ocam * max(nr, 1))(*[c if isinstance(c, Ocam) else make_ocam(c) for c in cams])
+    sig = np.ascontiguousarray(inv_sigma2, np.float64)
+    i4 = lambda a, n: None if a is None else np.ascontiguousarray(a, np.int32).reshape(n)
+    g = dict(pose=kf_pose.copy(), fixed=np.ascontiguousarray(kf_fixed, np.uint8).reshape(nk), t=np.zeros((max(n_local, 1), 3)) if with_t else None, pos=pos.copy(),
+             first=i4(pt_first, P + 1), ekf=i4(edge_kf, E), ecam=i4(edge_cam, E), key=np.ascontiguousarray(edge_key, KP_DTYPE).reshape(E), total=i4(total_obs, P),
+             bad=i4(bad_obs, P), Mc=np.ascontiguousarray(Mc_min, np.float64).reshape(nr, 6), ocs=np.frombuffer(ocs, np.uint8).copy(), sig=sig,
+             estate=np.zeros(max(E, 1), np.uint8), pstate=np.full(max(P, 1), 1, np.uint8))
+    g = {k: mem.put(v) for k, v in g.items()}
+    flag = None if stop_flag is None else C.c_int32(int(bool(stop_flag[0] if isinstance(stop_flag, list) else stop_flag)))
+    dg = LbaDiag()
+    check(lib().mcs_local_bundle_adjustment(ctx.h, nk, int(n_local), mem.ptr(g["pose"]), mem.ptr(g["fixed"]), mem.ptr(g["t"]), P, mem.ptr(g["pos"]), mem.ptr(g["first"]),
+                                            E, mem.ptr(g["ekf"]), mem.ptr(g["ecam"]), mem.ptr(g["key"]), mem.ptr(g["total"]), mem.ptr(g["bad"]), mem.ptr(g["Mc"]),
+                                            mem.ptr(g["ocs"]), nr, mem.ptr(g["sig"]), len(sig), float(std_recon), None if flag is None else C.byref(flag), mem.kind,
+                                            mem.ptr(g["estate"]), mem.ptr(g["pstate"]), C.byref(dg)))
+    if isinstance(stop_flag, list):
+        stop_flag[0] = bool(flag.value)
+    diag = np.frombuffer(bytes(dg), LBA_DIAG_DTYPE)[0]
+    return dict(status=int(diag["status"]), kf_pose=mem.read(g["pose"]), kf_t=mem.read(g["t"])[:n_local] if with_t else None, pos=mem.read(g["pos"]),
+                edge_state=mem.read(g["estate"])[:E], pt_state=mem.read(g["pstate"])[:P], diag=diag, stop_flag=None if flag is None else bool(flag.value), arrays=g)
+
+
+def _observations(mp):
+    """{keyframe: [feature, ...]} of a map point as std::map<cMultiKeyFrame*, ...> iterates it: ascending mnId (the project's convention)"""
+    obs = mp.GetObservations() if hasattr(mp, "GetObservations") else mp.mObservations
+    items = obs.items() if hasattr(obs, "items") else obs
+    return sorted(((k, list(v)) for k, v in items), key=lambda kv: kv[0].mnId)
+
+
+def _lba_lists(pKF):
+    """lLocalKeyFrames, lLocalMapPoints, lFixedCameras and the fixed flags of src/cOptimizer.cpp:473-529, 555-595.  Reproduced: mnBALocalForKF is set on bad
+    neighbours too (:484), so a bad neighbour never becomes a fixed camera; oneFixed is overwritten per keyframe (:564) and so reflects the LAST local keyframe,
+    keyframe 0 is fixed wherever it stands, and the fallback (:575-581) fixes the first local keyframe as well unless keyframe 0 stood last or a fixed camera
+    exists."""
+    bad = lambda k: hasattr(k, "isBad") and k.isBad()
+    neigh = list(pKF.GetVectorCovisibleKeyFrames() if hasattr(pKF, "GetVectorCovisibleKeyFrames") else pKF.mvpOrderedConnectedKeyFrames)
+    local = [pKF] + [k for k in neigh if not bad(k)]
+    marked = {id(k) for k in [pKF] + neigh}
+    points, seen = [], set()
+    for k in local:
+        for mp in k.GetMapPointMatches():
+            if _good(mp) and id(mp) not in seen:
+                seen.add(id(mp))
+                points.append(mp)
+    fixed = []
+    for mp in points:
+        for k, _ in _observations(mp):
+            if id(k) not in marked:
+                marked.add(id(k))                        # mnBAFixedForKF is set before the isBad test (:524-526)
+                if not bad(k):
+                    fixed.append(k)
+    is_fixed = np.ones(len(local) + len(fixed), np.uint8)
+    one_fixed = False
+    for i, k in enumerate(local):
+        one_fixed = k.mnId == 0
+        is_fixed[i] = one_fixed
+    if not one_fixed and not fixed:
+        is_fixed[0] = 1
+    return local, points, fixed, is_fixed
+
+
+def LocalBundleAdjustment(pKF, pbStopFlag=None, device=False, store=None, ctx=None, stdRecon=2.0):
+    """std::list<cMultiKeyFrame*> cOptimizer::LocalBundleAdjustment(pKF, pMap, nrIters, getCovMats, pbStopFlag) (src/cOptimizer.cpp:461-874) -> lLocalKeyFrames.
+    Keyframes: mnId, isBad(), GetVectorCovisibleKeyFrames() (or mvpOrderedConnectedKeyFrames), GetMapPointMatches(), camSystem (GetPoseMin, Get_M_c_min,
+    Set_M_t_from_min), keypoint_to_cam, GetKeyPoint, mvInvLevelSigma2, and EraseMapPointMatch(idx) where they have it (else mvpMapPoints[idx] = None).  Points:
+    isBad(), GetWorldPos(), GetObservations() (or mObservations), and SetWorldPos / EraseObservation / SetBadFlag where they have them (else mWorldPos /
+    mObservations / mbBad are set).  pbStopFlag: None or a one-element list, as the reference's bool*: NULL is the call that optimises — with a flag, g2o's
+    terminate action writes it when round one converges, and the reference then writes nothing back (:756-762).
+    store: a cCovisibility; the call then ends with SetPose of the local keyframes and UpdateMapPoints of the written points (:866-867), which need mpRefKF on
+    the points and mvScaleFactors on pKF."""
+    local, points, fixed, is_fixed = _lba_lists(pKF)
+    if len(local) <= 1:                                   # :489
+        return []
+    kfs = local + fixed
+    slot = {id(k): i for i, k in enumerate(kfs)}
+    bad = lambda k: hasattr(k, "isBad") and k.isBad()
+    first, ekf, ecam, keys, at, total, badobs = [0], [], [], [], [], [], []
+    for mp in points:
+        t = b = 0
+        for k, feats in _observations(mp):
+            t += len(feats)
+            if bad(k):
+                b += len(feats)
+                continue
+            for i in feats:
+                ekf.append(slot[id(k)])
+                ecam.append(int(k.keypoint_to_cam[i]))
+                keys.append(k.GetKeyPoint(i))
+                at.append((k, int(i)))
+        first.append(len(ekf))
+        total.append(t)
+        badobs.append(b)
+    rig = pKF.camSystem
+    nr = rig.GetNrCams()
+    key = np.zeros(len(keys), KP_DTYPE)
+    for j, kp in enumerate(keys):
+        key[j]["x"], key[j]["y"], key[j]["octave"] = kp["x"], kp["y"], kp["octave"]
+    r = LocalBundleAdjustmentArrays([k.camSystem.GetPoseMin() for k in kfs], is_fixed, len(local), [np.asarray(mp.GetWorldPos(), np.float64).reshape(-1)[:3] for mp in points],
+                                    first, ekf, ecam, key, [rig.Get_M_c_min(c) for c in range(nr)], [cm.ocam for cm in rig.cams], pKF.mvInvLevelSigma2, stdRecon,
+                                    total_obs=total, bad_obs=badobs, stop_flag=pbStopFlag, device=device, ctx=ctx)
+    pt_of = np.repeat(np.arange(len(points)), np.diff(first))
+    for e in np.nonzero(r["edge_state"])[0]:              # EraseMapPointMatch + EraseObservation (:777-778, :810-811)
+        k, i = at[e]
+        mp = points[pt_of[e]]
+        if hasattr(k, "EraseMapPointMatch"):
+            k.EraseMapPointMatch(i)
+        else:
+            k.mvpMapPoints[i] = None
+        if hasattr(mp, "EraseObservation"):
+            mp.EraseObservation(k, i)
+        else:
+            for kf, lst in (mp.mObservations.items() if hasattr(mp.mObservations, "items") else mp.mObservations):
+                if kf is k and i in lst:
+                    lst.remove(i)
+    written = []
+    for p, mp in enumerate(points):
+        if r["pt_state"][p] == 2:
+            mp.SetBadFlag() if hasattr(mp, "SetBadFlag") else setattr(mp, "mbBad", True)
+        elif r["pt_state"][p] == 0:
+            mp.SetWorldPos(r["pos"][p].copy()) if hasattr(mp, "SetWorldPos") else setattr(mp, "mWorldPos", r["pos"][p].copy())
+            written.append(p)
+    if r["status"] == 0:
+        for i, k in enumerate(local):
+            if not bad(k):
+                k.camSystem.Set_M_t_from_min(r["kf_pose"][i])
+        if store is not None:
+            store.SetPose(local, ts=r["kf_t"])
+            if written and all(hasattr(points[p], "mpRefKF") for p in written):
+                store.UpdateMapPoints([points[p] for p in written], r["pos"][written], [points[p].mpRefKF for p in written], pKF.mvScaleFactors)
+    return local
