@@ -12,6 +12,10 @@
 // Survivors are emitted in the reference's order (row-major inside the cell) with wave64 ballots + prefix counts into
 // the cell's private slot range, so the later compaction is a pure prefix sum over cells (cell row-major order).
 // Candidate record: x | y<<12 | score<<24 with x,y relative to minBorder (22), like vToDistributeKeys.
+// The one-wave FAST 9/16 instance suppresses and emits over the CORNERS, not over the compass survivors: the suppression keeps only s0 > nb >= 0, and on the bench
+// stream 38 of a cell's 166 survivors have a score.  The arc-score pass moves those to the front of the survivor list, in list order (two ballots and a running
+// total), and the suppression loop walks that corner list: 0.98 trips per cell where the survivor list took 2.96 (profiles/NOTES.md, "k_fast_cells: suppress and
+// emit over corners").  A cell whose compass pass lists nothing (a quarter of the stream's cells) writes its count and leaves before the arc-score pass.
 //
 // AGAST (useAgast, reference :869-870, 912-914; cv::AgastFeatureDetector AGAST_5_8 / AGAST_7_12d / AGAST_7_12s / OAST_9_16) runs in the same kernel (template
 // parameter AG): the detector's decision trees decide the plain segment test "N contiguous of the P ring pixels all brighter than v + t or all darker than v - t",
@@ -277,6 +281,11 @@ __device__ __forceinline__ int wave_incl_scan(int x) {
 	return x;
 }
 
+// base + the set bits of a wave-wide ballot below this lane: v_mbcnt_lo / v_mbcnt_hi, two instructions (mask, mask, count, count and an addition otherwise)
+__device__ __forceinline__ int rank_below(unsigned long long bal, int base) {
+	return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, (uint32_t)base));
+}
+
 // A pixel of the cell is named by its code  row << 6 | column  (cells are at most 60 wide): row-major order, and the row / column come back with a shift and a mask.
 template <int CW, int kFastBS, int P, int AG = -1>   // P = ring size: 16 (TYPE_9_16), 12 (TYPE_7_12), 8 (TYPE_5_8); AG >= 0: AGAST type AG (P = its ring size)
 __global__ __launch_bounds__(kFastBS) void k_fast_cells(ExtractBuffers b, int nimg, int nblocks, int perXcd, int cell0, int ncells, unsigned ncellsM) {
@@ -468,9 +477,34 @@ __global__ __launch_bounds__(kFastBS) void k_fast_cells(ExtractBuffers b, int ni
 	}
 	// (one wave per cell: the list entries and scores that pass 2 and 3 read were written by OTHER lanes, so the barriers between the passes stay — a workgroup of
 	// one wave pays next to nothing for them, and nothing here leans on the order of a wave's LDS operations)
+	if constexpr (kOneWave) {
+		// a cell whose compass pass lists nothing has no corner: it is done here (uniform: the workgroup is this wave)
+		if (listRun == 0 && !incomplete) { if (tid == 0) *countOut = 0; return; }
+	}
 	__syncthreads();
 	const int ns = kOrdered ? listRun : nSurv;
-	if constexpr (P == 16) {
+	int nc = 0;   // (one wave per cell) corners on the list: the survivors with a score, compacted to the front of `surv` in list order
+	if constexpr (kOneWave) {
+		// pass 2, one wave per cell: the arc score, and the CORNER list.  Pass 3 keeps only s0 > nb >= 0, so a survivor without a score has nothing to do there, and
+		// about three survivors in four are no corners.  A lane holds list entries i and i + 1; the entries with a score move to the front of `surv`, in list order
+		// (= row-major, the emission order): two ballots and a running total in a register.  In place: a trip reads entries [128 k, 128 k + 128) before it
+		// writes (the positions depend on the scores), writes below 128 k + 128 at most, and the next trip reads from there on.
+		for (int i = 2 * tid; i < ns; i += 2 * kFastBS) {
+			const bool two = i + 1 < ns;   // (an odd list: the last lane scores its entry twice, and lists it once)
+			const int pa = surv[i], pb = surv[two ? i + 1 : i];
+			const int ya = pa >> 6, xa = pa & 63, yb = pb >> 6, xb = pb & 63;
+			const uint32_t s2 = fast_score2<kTilePitch>(&tile[(ya + 3) * kTilePitch + xa + Geo::kTileX], &tile[(yb + 3) * kTilePitch + xb + Geo::kTileX], t);
+			sc[(ya + 1) * kScPitch + xa + 1] = (uint8_t)s2;
+			if (two) sc[(yb + 1) * kScPitch + xb + 1] = (uint8_t)(s2 >> 8);
+			const bool ka = (s2 & 0xffu) != 0u, kb = two && (s2 >> 8) != 0u;
+			const unsigned long long balA = __ballot(ka), balB = __ballot(kb);
+			const int posA = rank_below(balB, rank_below(balA, nc));   // the corners of the trips before + the lower lanes' first and second entries
+			if (ka) surv[posA] = (unsigned short)pa;
+			if (kb) surv[posA + (ka ? 1 : 0)] = (unsigned short)pb;
+			nc += __popcll(balA) + __popcll(balB);
+		}
+		nc = __builtin_amdgcn_readfirstlane(nc);   // lane 0 took part in every trip; a lane past the list's end left early
+	} else if constexpr (P == 16) {
 		for (int i = 2 * tid; i < ns; i += 2 * kFastBS) {
 			const int pa = surv[i], pb = surv[i + 1 < ns ? i + 1 : i];
 			const int ya = pa >> 6, xa = pa & 63, yb = pb >> 6, xb = pb & 63;
@@ -596,11 +630,11 @@ __global__ __launch_bounds__(kFastBS) void k_fast_cells(ExtractBuffers b, int ni
 	if constexpr (kOrdered) {
 		// pass 3, ordered list: suppression + mask + emission in one loop.  A trip covers kFastBS consecutive list entries; the kept ones among them leave in list order:
 		// a ballot per wave.  Several waves per cell (the 60-px instance): the waves' counts meet in `waveTot`, one barrier per trip.  One wave per cell: the rank is
-		// a running total in a register, no barrier (166 survivors per cell on the bench stream: three trips).
+		// a running total in a register, no barrier, and the list is the CORNER list (the survivors with a score, see pass 2).
 		// A cell whose list is incomplete walks the score tile itself, row-major, a pixel per lane: pass 3 keeps only s0 > nb >= 0, so every kept pixel has a score,
 		// every pixel with a score is a survivor, and row-major order is the emission order.
 		int run = 0;
-		const int n3 = incomplete ? cw * ch : ns;
+		const int n3 = incomplete ? cw * ch : (kOneWave ? nc : ns);   // one wave per cell: the corner list of pass 2 (an incomplete list is not used at all)
 		const unsigned divM = incomplete ? (262144u + (unsigned)cw - 1u) / (unsigned)cw : 0u;   // p / cw = (p * divM) >> 18, exact for cw <= 60 and p < 3600 (see the small rings' pass 1)
 		for (int base = 0; base < n3; base += kFastBS) {
 			const int i = base + tid;
@@ -630,7 +664,7 @@ __global__ __launch_bounds__(kFastBS) void k_fast_cells(ExtractBuffers b, int ni
 #pragma unroll
 				for (int w = 0; w < kFastBS / 64; ++w) { const int tw_ = waveTot[w]; before += w < wave ? tw_ : 0; all += tw_; }
 			}
-			if (keep) slots[run + before + __popcll(bal & ((1ull << lane) - 1ull))] = rec;
+			if (keep) slots[kOneWave ? rank_below(bal, run) : run + before + __popcll(bal & ((1ull << lane) - 1ull))] = rec;
 			run += all;
 			if (!kOneWave && base + kFastBS < n3) __syncthreads();   // (waveTot is rewritten by the next trip)
 		}
