@@ -1325,6 +1325,119 @@ struct cOptimizer {
 			}
 		return std::list<KF*>(local.begin(), local.end());
 	}
+
+	// cOptimizer::OptimizeEssentialGraph (src/cOptimizerLoopStuff.cpp:267-513) over mcs_optimize_essential_graph (host kind), with the reference's signature
+	// (Scurw is not read there either): builds the vertex list without bad keyframes, the Sim3 of an uncorrected keyframe as Sim3(R, t, 1.0) of
+	// GetPoseInverse() makes it (Eigen's Shoemake conversion, as csrc/mcs_sim3g.h restates it), the edge list in the reference's order with minNumFeat = 100
+	// and the point references (:494-501), runs the call and applies SetPose and SetWorldPos.  A g2o::Sim3 is eight numbers in operator[] order, qx qy qz qw
+	// tx ty tz s (EgSim3).  MAP: GetAllKeyFrames(), GetAllMapPoints() (vectors of pointers).  KF: mnId, isBad(), GetPoseInverse() (a Matx44d), GetParent(),
+	// GetLoopEdges() and GetCovisiblesByWeight(w) (containers of KF*), GetWeight(KF*), SetPose(const Matx44d&).  MP: isBad(), GetWorldPos() (indexable by
+	// 0..2), SetWorldPos(const double*), mnCorrectedByKF, mnCorrectedReference, GetReferenceKeyFrame().  Where the reference iterates a container ordered by
+	// address (the keyframes, LoopConnections and its sets, GetLoopEdges) the order here is ascending mnId.  An edge that names a bad keyframe is left out
+	// and a point whose reference keyframe has no vertex is left as it is.  UpdateNormalAndDepth of the moved points (:511) is the
+	// caller's (cCovisibility::UpdateMapPoints): `moved`, optional, receives them.  Returns the call's status (MCS_EG_*); nothing is applied unless it is 0.
+	using EgSim3 = std::array<double, 8>;
+	static EgSim3 Sim3FromPose(const Matx44d& M) {   // Sim3(R, t, 1.0): Quaternion(const Matrix3d&), Geometry/Quaternion.h:720-759
+		const double* R = M.data();
+		auto m = [&](int i, int j) { return R[4 * i + j]; };
+		EgSim3 S{};
+		double t = m(0, 0) + (m(1, 1) + m(2, 2));
+		if (t > 0.0) {
+			t = std::sqrt(t + 1.0);
+			S[3] = 0.5 * t;
+			t = 0.5 / t;
+			S[0] = (m(2, 1) - m(1, 2)) * t; S[1] = (m(0, 2) - m(2, 0)) * t; S[2] = (m(1, 0) - m(0, 1)) * t;
+		} else {
+			int i = 0;
+			if (m(1, 1) > m(0, 0)) i = 1;
+			if (m(2, 2) > m(i, i)) i = 2;
+			const int j = (i + 1) % 3, k = (j + 1) % 3;
+			t = std::sqrt(m(i, i) - m(j, j) - m(k, k) + 1.0);
+			S[i] = 0.5 * t;
+			t = 0.5 / t;
+			S[3] = (m(k, j) - m(j, k)) * t;
+			S[j] = (m(j, i) + m(i, j)) * t;
+			S[k] = (m(k, i) + m(i, k)) * t;
+		}
+		S[4] = m(0, 3); S[5] = m(1, 3); S[6] = m(2, 3); S[7] = 1.0;
+		return S;
+	}
+	template <class MAP, class KF, class MP = typename std::remove_pointer<typename decltype(std::declval<MAP>().GetAllMapPoints())::value_type>::type>
+	static int OptimizeEssentialGraph(Context& ctx, MAP* pMap, KF* pLoopMKF, KF* pCurMKF, EgSim3& /*Scurw*/, const std::map<KF*, EgSim3>& NonCorrectedSim3,
+	                                  const std::map<KF*, EgSim3>& CorrectedSim3, const std::map<KF*, std::set<KF*>>& LoopConnections, mcs_eg_diag* diag = nullptr,
+	                                  std::vector<MP*>* moved = nullptr) {
+		const int minNumFeat = 100;
+		auto byId = [](std::vector<KF*> v) { std::stable_sort(v.begin(), v.end(), [](KF* a, KF* b) { return a->mnId < b->mnId; }); return v; };
+		std::vector<KF*> kfs;
+		for (KF* k : byId(pMap->GetAllKeyFrames()))
+			if (!k->isBad()) kfs.push_back(k);
+		std::map<KF*, int32_t> slot;
+		for (size_t i = 0; i < kfs.size(); ++i) slot[kfs[i]] = (int32_t)i;
+		const size_t K = kfs.size();
+		std::vector<double> Scw(8 * K), Snc(8 * K, 0.0);
+		std::vector<uint8_t> hasNc(K, 0), fixed(K, 0);
+		for (size_t i = 0; i < K; ++i) {   // :305-342
+			const auto c = CorrectedSim3.find(kfs[i]);
+			const EgSim3 S = c != CorrectedSim3.end() ? c->second : Sim3FromPose(kfs[i]->GetPoseInverse());
+			std::copy(S.begin(), S.end(), Scw.begin() + 8 * i);
+			const auto n = NonCorrectedSim3.find(kfs[i]);
+			if (n != NonCorrectedSim3.end()) { std::copy(n->second.begin(), n->second.end(), Snc.begin() + 8 * i); hasNc[i] = 1; }
+			fixed[i] = kfs[i] == pLoopMKF ? 1 : 0;
+		}
+		std::vector<int32_t> ei, ej;
+		std::vector<uint8_t> kind;
+		auto edge = [&](KF* a, KF* b, uint8_t k) {
+			const auto sa = slot.find(a), sb = slot.find(b);
+			if (sa == slot.end() || sb == slot.end()) return;
+			ei.push_back(sa->second); ej.push_back(sb->second); kind.push_back(k);
+		};
+		std::vector<KF*> heads;
+		for (const auto& kv : LoopConnections) heads.push_back(kv.first);
+		for (KF* k : byId(heads))   // :349-376
+			for (KF* c : byId(std::vector<KF*>(LoopConnections.at(k).begin(), LoopConnections.at(k).end()))) {
+				if ((k->mnId != pCurMKF->mnId || c->mnId != pLoopMKF->mnId) && k->GetWeight(c) < minNumFeat) continue;
+				edge(k, c, 0);
+			}
+		for (KF* k : kfs) {   // :379-464
+			if (KF* parent = k->GetParent()) edge(k, parent, 1);
+			const auto loops = k->GetLoopEdges();
+			for (KF* l : byId(std::vector<KF*>(loops.begin(), loops.end())))
+				if (l->mnId < k->mnId) edge(k, l, 1);
+			for (KF* c : k->GetCovisiblesByWeight(minNumFeat))
+				if (c->mnId < k->mnId) edge(k, c, 1);
+		}
+		std::vector<MP*> points;
+		for (MP* mp : pMap->GetAllMapPoints())
+			if (mp && !mp->isBad()) points.push_back(mp);
+		const size_t P = points.size();
+		std::vector<double> pos(3 * std::max<size_t>(P, 1));
+		std::vector<int32_t> ref(std::max<size_t>(P, 1), -1);
+		for (size_t p = 0; p < P; ++p) {   // :494-501
+			if ((long long)points[p]->mnCorrectedByKF == (long long)pCurMKF->mnId) {
+				for (size_t i = 0; i < K; ++i)
+					if ((long long)kfs[i]->mnId == (long long)points[p]->mnCorrectedReference) { ref[p] = (int32_t)i; break; }
+			} else {
+				const auto s = slot.find(points[p]->GetReferenceKeyFrame());
+				if (s != slot.end()) ref[p] = s->second;
+			}
+			const auto X = points[p]->GetWorldPos();
+			for (int k = 0; k < 3; ++k) pos[3 * p + k] = (double)X[k];
+		}
+		std::vector<double> out(8 * std::max<size_t>(K, 1)), pose(16 * std::max<size_t>(K, 1));
+		mcs_eg_diag d{};
+		mcs_throw(mcs_optimize_essential_graph(ctx.h, (int)K, Scw.data(), Snc.data(), hasNc.data(), fixed.data(), (int)ei.size(), ei.data(), ej.data(), kind.data(),
+		                                       (int)P, pos.data(), ref.data(), MCS_MEM_HOST, out.data(), pose.data(), nullptr, &d));
+		if (diag) *diag = d;
+		if (d.status != MCS_EG_OK) return d.status;
+		for (size_t i = 0; i < K; ++i) {   // :473-485
+			Matx44d M;
+			std::copy(pose.begin() + 16 * i, pose.begin() + 16 * i + 16, M.begin());
+			kfs[i]->SetPose(M);
+		}
+		for (size_t p = 0; p < P; ++p)
+			if (ref[p] >= 0) { points[p]->SetWorldPos(&pos[3 * p]); if (moved) moved->push_back(points[p]); }
+		return d.status;
+	}
 };
 
 // ---------------------------------------------------------------------------------------------- the local map and the covisibility counts

@@ -37,7 +37,7 @@ extern "C" {
  * 9: the keyframe database mcs_kfdb_*, mcs_vocabulary_set_words, mcs_bow_vector; 10: the Sim3 RANSAC mcs_sim3_*).  Purely additive
  * entry points leave it alone: mcs_triangulate_matches / mcs_create_new_map_points and mcs_frustum / mcs_search_local_points arrived within revision 10, as did the
  * covisibility store mcs_covis_* with mcs_gather_rows / mcs_scatter_rows and its culling calls mcs_covis_set_keyframe_octaves / _cull_keyframes / _observations / _cull_points
- * and mcs_pose_optimization and mcs_sim3_optimize (look them up with dlsym).  mcs_abi_version() returns the value the LIBRARY was built with: compare it with MCS_ABI_VERSION after dlopen. */
+ * and mcs_pose_optimization, mcs_sim3_optimize, mcs_local_bundle_adjustment and mcs_optimize_essential_graph (look them up with dlsym).  mcs_abi_version() returns the value the LIBRARY was built with: compare it with MCS_ABI_VERSION after dlopen. */
 #define MCS_ABI_VERSION 10
 
 #define MCS_MAX_POLY 16
@@ -740,6 +740,48 @@ int mcs_local_bundle_adjustment(mcs_ctx*, int n_kfs, int n_local, double* kf_pos
                                 const int32_t* pt_total_obs, const int32_t* pt_bad_obs, const double* M_c_min, const mcs_ocam* cams, int nr_cams,
                                 const double* inv_level_sigma2, int nlevels, double std_recon, int* stop_flag, mcs_mem_kind kind, uint8_t* edge_state,
                                 uint8_t* pt_state, mcs_lba_diag* diag);
+
+/* ------------------------------------------------------------------ the essential graph on the device
+ *   void cOptimizer::OptimizeEssentialGraph(cMap*, cMultiKeyFrame* pLoopMKF, cMultiKeyFrame* pCurMKF, g2o::Sim3&, const KeyFrameAndPose& NonCorrectedSim3,
+ *                                           const KeyFrameAndPose& CorrectedSim3, const map<cMultiKeyFrame*, set<cMultiKeyFrame*>>& LoopConnections)
+ *       (src/cOptimizerLoopStuff.cpp:267-513), the call of cLoopClosing::CorrectLoop (src/cLoopClosing.cpp:577)
+ * as ONE problem over the whole device: every keyframe a free 7-number Sim3 vertex (nothing marginalised), the edges log(C * Si * Sj^-1) with the identity as
+ * information and no robust kernel, the NUMERIC Jacobian of g2o's BaseBinaryEdge (1e-9 steps), Levenberg-Marquardt with setUserLambdaInit(1e-6),
+ * optimize(20) under the terminate action (gain 1e-6, setMaxIterations(15): at most SIXTEEN iterations, 0..15), the write-back of poses and map points.
+ * DESIGN.md 4o restates the algorithm and names the kernels; section 7 lists what is reproduced rather than repaired.  Who is in the map, which edges exist and
+ * what happens to the objects stay with the caller (frontend.OptimizeEssentialGraph): the call takes arrays, each where `kind` says unless stated.
+ *   Scw [n_kfs][8]          in: the estimate of every vertex as qx qy qz qw tx ty tz s, in ascending mnId (:314-333: the CorrectedSim3 entry where there is
+ *                           one, else Sim3(R, t, 1) of GetPoseInverse()).  The quaternion is taken as given and never normalised.
+ *   Snc [n_kfs][8], has_nc [n_kfs]   the NonCorrectedSim3 entry of a keyframe where has_nc (bytes) is non-zero; else the row is not read.
+ *   kf_fixed [n_kfs]        bytes, non-zero = the vertex is fixed (the reference fixes pLoopMKF; any set is honoured).
+ *   edge_i, edge_j [n_edges] vertex 0 and vertex 1 of every edge (indices into the keyframe list) in the order the reference adds them: the LoopConnections
+ *                           edges (:349-376), then per keyframe its spanning-tree edge, its loop edges and its covisibility edges (:379-464).  edge_kind
+ *                           (bytes): 0 = the measurement Sjw * Swi is formed from Scw on both sides (LoopConnections); non-zero = from Snc where has_nc is
+ *                           set, else Scw, separately for i and j.  A pair that appears twice gets two edges (insertedEdges is never consulted): they add up.
+ *   pos [n_points][3]       in/out: a point with pt_ref[p] = r >= 0 becomes estimate[r].inverse().map(Scw[r].map(pos)) (:504-510); pt_ref[p] = -1 leaves it
+ *                           untouched.  The rule behind pt_ref (mnCorrectedByKF / mnCorrectedReference, :494-501) is the caller's.
+ *   Scw_out [n_kfs][8]      out: the optimised Sim3 of every vertex.  pose [n_kfs][16]: invMat(toCvSE3(R, t / s)) of :481-484, row-major.  kf_t [n_kfs][3],
+ *                           optional: Hom2T of pose, what mcs_covis_set_keyframe_pose takes.
+ *   diag                    HOST, optional.  status: MCS_EG_*; iters; stop (0 optimize(20) ran out, 1 the gain test, 2 ten trials or rho == 0, 3 three bad
+ *                           iterations, 4 not run, 5 the action's cap at iteration 15); trials per iteration; n_free; n_edges = edges that passed the
+ *                           guards; the final lambda and the chi2 of the final estimate.
+ * Statuses that write nothing: MCS_EG_NO_FREE_VERTEX, MCS_EG_FAILED (no edge: optimize() returns Fail), MCS_EG_NONFINITE (the first evaluation holds a
+ * non-finite residual, Jacobian entry of a free vertex or sum).
+ * Refused with MCS_ERR_CAPACITY before anything runs: more than 512 free vertices (the system is at most 3584 x 3584, 103 MB of scratch), n_kfs > 4096,
+ * n_edges > 2^17 (an edge takes 929 bytes of scratch for its Jacobians, residual, measurement and list entries: 122 MB at the limit; 512 keyframes that
+ * are all covisible with each other have 2^17 pairs), n_points > 2^22 (28 bytes each, staged in host kind only).  Guards: an edge with an index out of range or edge_i == edge_j, or a pt_ref outside [-1, n_kfs), is MCS_ERR_INVALID in host
+ * kind before anything runs; in device kind such an edge contributes nothing and such a point stays untouched.  MCS_ERR_UNSUPPORTED while deferred searches are on.
+ * FP64 without contraction, no floating-point atomic, every sum in an order that the problem and the solver's panel width (32) alone decide: the same call
+ * twice is bit-identical.  The phases are separate launches; the host waits for the stream once per Levenberg trial and reads a 64-byte record of the
+ * decisions the device took.  In device kind kf_fixed is read back once, before anything runs.  Scratch comes from the context's grow-only block. */
+#define MCS_EG_OK 0
+#define MCS_EG_NONFINITE 1
+#define MCS_EG_NO_FREE_VERTEX 2
+#define MCS_EG_FAILED 3
+typedef struct { int32_t status, iters, stop; int32_t trials[20]; int32_t n_free, n_edges, pad; double lambda, chi2; } mcs_eg_diag;
+int mcs_optimize_essential_graph(mcs_ctx*, int n_kfs, const double* Scw, const double* Snc, const uint8_t* has_nc, const uint8_t* kf_fixed, int n_edges,
+                                 const int32_t* edge_i, const int32_t* edge_j, const uint8_t* edge_kind, int n_points, double* pos, const int32_t* pt_ref,
+                                 mcs_mem_kind kind, double* Scw_out, double* pose, double* kf_t, mcs_eg_diag* diag);
 
 /* ------------------------------------------------------------------ the local map and the covisibility counts on the device
  * cTracking::UpdateReferenceKeyFrames + UpdateReferencePoints (src/cTracking.cpp:1024-1123), the first step of TrackLocalMap, and the counting and ordering of

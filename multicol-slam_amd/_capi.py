@@ -79,6 +79,7 @@ EXPORTS = [
     "mcs_triangulate_matches", "mcs_create_new_map_points",
     "mcs_frustum", "mcs_search_local_points",
     "mcs_search_last_frame", "mcs_window_search_frames", "mcs_pose_optimization", "mcs_sim3_optimize", "mcs_local_bundle_adjustment",
+    "mcs_optimize_essential_graph",
     "mcs_covis_create", "mcs_covis_destroy", "mcs_covis_clear", "mcs_covis_size", "mcs_covis_slots", "mcs_covis_set_keyframe", "mcs_covis_set_keyframe_pose",
     "mcs_covis_erase_keyframe", "mcs_covis_set_keyframe_bad", "mcs_covis_set_points_bad", "mcs_covis_update_reference", "mcs_covis_update_connections",
     "mcs_gather_rows", "mcs_scatter_rows",
@@ -180,6 +181,16 @@ LBA_DIAG_DTYPE = np.dtype([("status", "<i4"), ("iters", "<i4", 2), ("stop", "<i4
                            ("n_erased", "<i4", 2), ("pad", "<i4"), ("lam", "<f8"), ("chi2", "<f8")])
 LBA_OK, LBA_NONFINITE, LBA_STOPPED, LBA_NO_FREE_POSE, LBA_FAILED, LBA_TOO_FEW = range(6)   # MCS_LBA_* of include/mcs_c.h
 LBA_PT_WRITTEN, LBA_PT_KEPT, LBA_PT_BAD = 0, 1, 2                                           # pt_state of mcs_local_bundle_adjustment
+
+
+class EgDiag(C.Structure):   # mcs_eg_diag
+    _fields_ = [("status", C.c_int32), ("iters", C.c_int32), ("stop", C.c_int32), ("trials", C.c_int32 * 20), ("n_free", C.c_int32), ("n_edges", C.c_int32),
+                ("pad", C.c_int32), ("lam", C.c_double), ("chi2", C.c_double)]
+
+
+EG_DIAG_DTYPE = np.dtype([("status", "<i4"), ("iters", "<i4"), ("stop", "<i4"), ("trials", "<i4", 20), ("n_free", "<i4"), ("n_edges", "<i4"), ("pad", "<i4"),
+                          ("lam", "<f8"), ("chi2", "<f8")])
+EG_OK, EG_NONFINITE, EG_NO_FREE_VERTEX, EG_FAILED = range(4)                                  # MCS_EG_* of include/mcs_c.h
 
 
 _lib = None
@@ -292,6 +303,7 @@ def lib():
     L.mcs_sim3_optimize.argtypes = [vp, C.c_int, C.POINTER(Sim3OptProblem), vp, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, C.POINTER(vp), vp, vp]
     L.mcs_local_bundle_adjustment.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int,
                                               C.c_double, i32p, C.c_int, vp, vp, vp]
+    L.mcs_optimize_essential_graph.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]
     L.mcs_covis_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
     L.mcs_covis_destroy.argtypes = [vp]
     L.mcs_covis_clear.argtypes = [vp]

@@ -98,7 +98,7 @@ struct mcs_ctx {
 	// windows, candidate lists and counts, the slot matches; mcs_capi_track.hip).  Its own buffer for the same reason: the device-kind call returns while its
 	// kernels run, and successive calls reuse it in the order of the context's stream.
 	DevBuf lmBuf;
-	void* lbaRec = nullptr;   // mcs_local_bundle_adjustment: the 64-byte control record its decide kernel leaves in page-locked memory (mcs_lba.hip)
+	void* lbaRec = nullptr;   // mcs_local_bundle_adjustment / mcs_optimize_essential_graph: the 64-byte control record the decide kernel leaves in page-locked memory
 	// Second HIP stream for the latency-bound / independent kernels (blur next to FAST+oct-tree, the greedy resolution next to the
 	// following batch's extraction): they leave most CUs idle, so overlapping them with the VALU-bound kernels is free throughput.
 	hipStream_t side = nullptr;    // extraction fork: resize chain + blur beside FAST + oct-tree

@@ -2,7 +2,8 @@
 // (ThirdParty/Eigen/Eigen/src/Geometry/Quaternion.h), stated once for mcs_sim3opt.hip.  Each function restates the cited lines in their scalar form (no SSE
 // path: an SSE2 build of the reference runs Eigen's vectorised quaternion product, which orders its operands differently): FP64, no contraction, every sum
 // in the order Eigen's expression evaluates it.  Host and device: tests/test_sim3g_cpu.py compiles this header alone for the host and holds it bit for bit to
-// tests/sim3opt_model.py.  log() is not needed and is left out.
+// tests/sim3opt_model.py.  log() and the edge error of the essential graph (mcs_essgraph.hip) follow at the end: tests/test_sim3g_log_cpu.py holds
+// them to tests/essgraph_model.py in the same way.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -182,6 +183,97 @@ MCS_GEOM Sim3g sim3_mul(const Sim3g& a, const Sim3g& b) {
 	for (int k = 0; k < 3; ++k) r.t[k] = a.s * v[k] + a.t[k];
 	r.s = a.s * b.s;
 	return r;
+}
+
+// PartialPivLU of a 3x3 and its solve, as Eigen 3.2.10 runs W.lu().solve(t) for fixed size 3: partial_lu_impl::unblocked_lu (LU/PartialPivLU.h:245-287) — per
+// column the FIRST largest |entry| at or below the diagonal (maxCoeff keeps the first), whole rows swapped, the column below divided by the pivot (a true
+// division, Core/Functors.h:544), the corner updated by one product per entry; a zero column is left alone — then dst = P b, the unit-lower and the upper
+// triangular solves unrolled (Core/SolveTriangular.h: x_i -= the sum of the products so far, two of them as a0 + a1; the upper one divides by the diagonal).
+// W row-major, destroyed.  pivots (optional): the rows chosen for columns 0 and 1.
+MCS_GEOM void lu3_solve(double* W, const double* b, double* x, int* pivots = nullptr) {
+	double y[3] = {b[0], b[1], b[2]};
+	for (int k = 0; k < 3; ++k) {
+		int piv = k;
+		double big = fabs(W[3 * k + k]);
+		for (int r = k + 1; r < 3; ++r)
+			if (fabs(W[3 * r + k]) > big) { big = fabs(W[3 * r + k]); piv = r; }
+		if (pivots && k < 2) pivots[k] = piv;
+		if (big != 0.0) {
+			if (piv != k) {
+				for (int c = 0; c < 3; ++c) { const double t = W[3 * k + c]; W[3 * k + c] = W[3 * piv + c]; W[3 * piv + c] = t; }
+			}
+			for (int r = k + 1; r < 3; ++r) W[3 * r + k] = W[3 * r + k] / W[3 * k + k];
+		}
+		if (piv != k) { const double t = y[k]; y[k] = y[piv]; y[piv] = t; }   // the transpositions applied to b in the order they were made
+		for (int r = k + 1; r < 3; ++r)
+			for (int c = k + 1; c < 3; ++c) W[3 * r + c] = W[3 * r + c] - W[3 * r + k] * W[3 * k + c];
+	}
+	y[1] -= W[3] * y[0];
+	y[2] -= W[6] * y[0] + W[7] * y[1];
+	x[2] = y[2] / W[8];
+	x[1] = (y[1] - W[5] * x[2]) / W[4];
+	x[0] = (y[0] - (W[1] * x[1] + W[2] * x[2])) / W[0];
+}
+
+// Sim3::log (sim3.h:148-230): four branches on |sigma| < 1e-5 and d > 1 - 1e-5 with d = 0.5 * (R00 + R11 + R22 - 1), left to right; deltaR and skew
+// (se3_ops.hpp:27-49); W = A * Omega + B * Omega * Omega + C * I, where B * Omega * Omega is the product of (B * Omega) with Omega summed in increasing k;
+// upsilon = W.lu().solve(t).  out: omega, upsilon, sigma.  branch (optional): 2 * (|sigma| >= eps) + (d <= 1 - eps).
+MCS_GEOM void sim3_log(const Sim3g& S, double* out, int* branch = nullptr, int* pivots = nullptr) {
+	const double sigma = log(S.s);
+	double R[9];
+	quat_to_mat(S.q, R);
+	const double d = 0.5 * (R[0] + R[4] + R[8] - 1);
+	const double dR[3] = {R[7] - R[5], R[2] - R[6], R[3] - R[1]};
+	const double eps = 0.00001;
+	const double s = S.s;
+	double A, B, C, f;
+	if (fabs(sigma) < eps) {
+		C = 1;
+		if (d > 1 - eps) { f = 0.5; A = 1. / 2.; B = 1. / 6.; }
+		else {
+			const double theta = acos(d);
+			const double theta2 = theta * theta;
+			f = theta / (2 * sqrt(1 - d * d));
+			A = (1 - cos(theta)) / (theta2);
+			B = (theta - sin(theta)) / (theta2 * theta);
+		}
+	} else {
+		C = (s - 1) / sigma;
+		if (d > 1 - eps) {
+			const double sigma2 = sigma * sigma;
+			f = 0.5;
+			A = ((sigma - 1) * s + 1) / (sigma2);
+			B = ((0.5 * sigma2 - sigma + 1) * s) / (sigma2 * sigma);
+		} else {
+			const double theta = acos(d);
+			f = theta / (2 * sqrt(1 - d * d));
+			const double theta2 = theta * theta;
+			const double a = s * sin(theta);
+			const double b = s * cos(theta);
+			const double c = theta2 + sigma * sigma;
+			A = (a * sigma + (1 - b) * theta) / (theta * c);
+			B = (C - ((b - 1) * sigma + a * theta) / (c)) * 1. / (theta2);
+		}
+	}
+	if (branch) *branch = (fabs(sigma) < eps ? 0 : 2) + (d > 1 - eps ? 0 : 1);
+	const double w[3] = {f * dR[0], f * dR[1], f * dR[2]};
+	const double Om[9] = {0.0, -w[2], w[1], w[2], 0.0, -w[0], -w[1], w[0], 0.0};
+	double W[9];
+	for (int i = 0; i < 3; ++i)
+		for (int j = 0; j < 3; ++j) {
+			double p = (B * Om[3 * i]) * Om[j];
+			p += (B * Om[3 * i + 1]) * Om[3 + j];
+			p += (B * Om[3 * i + 2]) * Om[6 + j];
+			W[3 * i + j] = (A * Om[3 * i + j] + p) + C * (i == j ? 1.0 : 0.0);
+		}
+	lu3_solve(W, S.t, out + 3, pivots);
+	out[0] = w[0]; out[1] = w[1]; out[2] = w[2];
+	out[6] = sigma;
+}
+
+// edgeSim3::computeError (include/g2o_MultiCol_sim3_expmap.h:86-94): log(C * v1 * v2.inverse()), the products left to right; Sjinv is v2's inverse
+MCS_GEOM void sim3_edge_error(const Sim3g& C, const Sim3g& Si, const Sim3g& Sjinv, double* e, int* branch = nullptr, int* pivots = nullptr) {
+	sim3_log(sim3_mul(sim3_mul(C, Si), Sjinv), e, branch, pivots);
 }
 
 }  // namespace mcs

@@ -16,6 +16,7 @@
 Everything numeric runs in libmcs_hip.so on the GPU; this file only shapes inputs/outputs (numpy stands in for cv::Mat).
 """
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -1987,3 +1988,142 @@ def LocalBundleAdjustment(pKF, pbStopFlag=None, device=False, store=None, ctx=No
             if written and all(hasattr(points[p], "mpRefKF") for p in written):
                 store.UpdateMapPoints([points[p] for p in written], r["pos"][written], [points[p].mpRefKF for p in written], pKF.mvScaleFactors)
     return local
+
+
+# ---------------------------------------------------------------------------------------------- the essential graph (mcs_optimize_essential_graph)
+def OptimizeEssentialGraphArrays(Scw, Snc, has_nc, kf_fixed, edge_i, edge_j, edge_kind, pos, pt_ref, device=False, ctx=None, with_t=True):
+    """mcs_optimize_essential_graph over arrays (include/mcs_c.h says what each holds).  device=True: every array in device memory.  -> dict: status, Scw_out
+    [n_kfs][8], pose [n_kfs][16], kf_t [n_kfs][3], pos, diag (an EG_DIAG_DTYPE record), arrays (the call's arrays where they live: DeviceArray objects in
+    device kind, for a chain without a host visit)"""
+    from ._capi import EG_DIAG_DTYPE, EgDiag
+    ctx = ctx or default_context()
+    mem = _DEVICE if device else _HOST
+    Scw = np.ascontiguousarray(Scw, np.float64).reshape(-1, 8)
+    pos = np.ascontiguousarray(pos, np.float64).reshape(-1, 3)
+    K, E, P = len(Scw), len(edge_i), len(pos)
+    g = dict(Scw=Scw, Snc=np.ascontiguousarray(Snc, np.float64).reshape(K, 8), has_nc=np.ascontiguousarray(has_nc, np.uint8).reshape(K),
+             fixed=np.ascontiguousarray(kf_fixed, np.uint8).reshape(K), ei=np.ascontiguousarray(edge_i, np.int32).reshape(E),
+             ej=np.ascontiguousarray(edge_j, np.int32).reshape(E), kind=np.ascontiguousarray(edge_kind, np.uint8).reshape(E), pos=pos.copy(),
+             ref=np.ascontiguousarray(pt_ref, np.int32).reshape(P), out=np.zeros((max(K, 1), 8)), pose=np.zeros((max(K, 1), 16)),
+             t=np.zeros((max(K, 1), 3)) if with_t else None)
+    g = {k: mem.put(v) for k, v in g.items()}
+    dg = EgDiag()
+    check(lib().mcs_optimize_essential_graph(ctx.h, K, mem.ptr(g["Scw"]), mem.ptr(g["Snc"]), mem.ptr(g["has_nc"]), mem.ptr(g["fixed"]), E, mem.ptr(g["ei"]),
+                                             mem.ptr(g["ej"]), mem.ptr(g["kind"]), P, mem.ptr(g["pos"]), mem.ptr(g["ref"]), mem.kind, mem.ptr(g["out"]),
+                                             mem.ptr(g["pose"]), mem.ptr(g["t"]), C.byref(dg)))
+    diag = np.frombuffer(bytes(dg), EG_DIAG_DTYPE)[0]
+    return dict(status=int(diag["status"]), Scw_out=mem.read(g["out"])[:K], pose=mem.read(g["pose"])[:K], kf_t=mem.read(g["t"])[:K] if with_t else None,
+                pos=mem.read(g["pos"]), diag=diag, arrays=g)
+
+
+def _quat_from_rotation(R):
+    """Eigen's Quaternion(const Matrix3d&) (Geometry/Quaternion.h:720-759, Shoemake) as Sim3(R, t, 1.0) runs it and csrc/mcs_sim3g.h restates it: x y z w"""
+    R = np.asarray(R, np.float64).reshape(3, 3)
+    t = float(R[0, 0]) + (float(R[1, 1]) + float(R[2, 2]))
+    q = [0.0] * 4
+    if t > 0.0:
+        t = math.sqrt(t + 1.0)
+        q[3] = 0.5 * t
+        t = 0.5 / t
+        q[0], q[1], q[2] = (float(R[2, 1]) - float(R[1, 2])) * t, (float(R[0, 2]) - float(R[2, 0])) * t, (float(R[1, 0]) - float(R[0, 1])) * t
+    else:
+        i = 0
+        if R[1, 1] > R[0, 0]:
+            i = 1
+        if R[2, 2] > R[i, i]:
+            i = 2
+        j, k = (i + 1) % 3, (i + 2) % 3
+        v = float(R[i, i]) - float(R[j, j]) - float(R[k, k]) + 1.0
+        t = math.sqrt(v) if v >= 0 else math.nan
+        q[i] = 0.5 * t
+        t = float(np.float64(0.5) / np.float64(t))
+        q[3] = (float(R[k, j]) - float(R[j, k])) * t
+        q[j] = (float(R[j, i]) + float(R[i, j])) * t
+        q[k] = (float(R[k, i]) + float(R[i, k])) * t
+    return q
+
+
+def _sim3_row(S):
+    """qx qy qz qw tx ty tz s of a KeyFrameAndPose entry: eight numbers as they are, or a Sim3 (its q where an optimisation left one, else the conversion of R)"""
+    if isinstance(S, Sim3):
+        return list(S.q if S.q is not None else _quat_from_rotation(S.R)) + [float(v) for v in S.t] + [float(S.s)]
+    return [float(v) for v in np.asarray(S, np.float64).reshape(8)]
+
+
+def _essential_graph_lists(pMap, pLoopMKF, pCurMKF, NonCorrectedSim3, CorrectedSim3, LoopConnections, minNumFeat=100):
+    """The vertices, edges and point references of src/cOptimizerLoopStuff.cpp:291-464, 490-501 -> (kfs, points, arrays).  Keyframes and the entries of
+    LoopConnections are taken in ascending mnId (the project's convention where the reference iterates a container ordered by address).  A bad keyframe gets
+    no vertex; an edge that names one is left out (the reference hands g2o a null vertex there, which its addEdge dereferences)."""
+    bad = lambda k: hasattr(k, "isBad") and k.isBad()
+    by_id = lambda ks: sorted(ks, key=lambda k: k.mnId)
+    kfs = [k for k in by_id(pMap.GetAllKeyFrames()) if not bad(k)]
+    slot = {id(k): i for i, k in enumerate(kfs)}
+    find = lambda table, k: next((v for kk, v in (table.items() if hasattr(table, "items") else table) if kk is k), None)
+    Scw, Snc, has_nc = [], [], []
+    for k in kfs:
+        c = find(CorrectedSim3, k)
+        if c is not None:
+            Scw.append(_sim3_row(c))
+        else:
+            Minv = np.asarray(k.GetPoseInverse(), np.float64).reshape(4, 4)
+            Scw.append(_quat_from_rotation(Minv[:3, :3]) + [float(v) for v in Minv[:3, 3]] + [1.0])
+        n = find(NonCorrectedSim3, k)
+        Snc.append(_sim3_row(n) if n is not None else [0.0] * 8)
+        has_nc.append(0 if n is None else 1)
+    ei, ej, kind = [], [], []
+    items = LoopConnections.items() if hasattr(LoopConnections, "items") else LoopConnections
+    for k, conns in sorted(items, key=lambda kv: kv[0].mnId):
+        for c in by_id(conns):
+            if (k.mnId != pCurMKF.mnId or c.mnId != pLoopMKF.mnId) and k.GetWeight(c) < minNumFeat:
+                continue
+            if id(k) in slot and id(c) in slot:
+                ei.append(slot[id(k)]), ej.append(slot[id(c)]), kind.append(0)
+    for k in kfs:
+        others = []
+        parent = k.GetParent()
+        if parent is not None:
+            others.append(parent)
+        others += [l for l in by_id(k.GetLoopEdges()) if l.mnId < k.mnId]
+        others += [c for c in k.GetCovisiblesByWeight(minNumFeat) if c.mnId < k.mnId]
+        for o in others:
+            if id(o) in slot:
+                ei.append(slot[id(k)]), ej.append(slot[id(o)]), kind.append(1)
+    points = [mp for mp in pMap.GetAllMapPoints() if not (hasattr(mp, "isBad") and mp.isBad())]
+    ref = []
+    for mp in points:
+        if getattr(mp, "mnCorrectedByKF", -1) == pCurMKF.mnId:
+            ref.append(next((i for i, k in enumerate(kfs) if k.mnId == mp.mnCorrectedReference), -1))
+        else:
+            r = mp.GetReferenceKeyFrame() if hasattr(mp, "GetReferenceKeyFrame") else mp.mpRefKF
+            ref.append(slot.get(id(r), -1))
+    fixed = [1 if k is pLoopMKF else 0 for k in kfs]
+    pos = [np.asarray(mp.GetWorldPos(), np.float64).reshape(-1)[:3] for mp in points]
+    return kfs, points, (Scw, Snc, has_nc, fixed, ei, ej, kind, np.asarray(pos, np.float64).reshape(-1, 3), ref)
+
+
+def OptimizeEssentialGraph(pMap, pLoopMKF, pCurMKF, NonCorrectedSim3, CorrectedSim3, LoopConnections, device=False, store=None, ctx=None):
+    """void cOptimizer::OptimizeEssentialGraph(pMap, pLoopMKF, pCurMKF, Scurw, NonCorrectedSim3, CorrectedSim3, LoopConnections)
+    (src/cOptimizerLoopStuff.cpp:267-513) -> the result of OptimizeEssentialGraphArrays.  pMap: GetAllKeyFrames(), GetAllMapPoints().  Keyframes: mnId, isBad(),
+    GetPoseInverse(), GetParent(), GetLoopEdges(), GetCovisiblesByWeight(w), GetWeight(kf), SetPose(M).  Points: isBad(), GetWorldPos(), SetWorldPos(X),
+    mnCorrectedByKF, mnCorrectedReference, GetReferenceKeyFrame() (or mpRefKF).  The two KeyFrameAndPose tables: {keyframe: Sim3 or eight numbers qx qy qz qw
+    tx ty tz s}.  LoopConnections: {keyframe: keyframes}.  A point whose reference keyframe has no vertex is left as it is.
+    store: a cCovisibility; the call then ends with SetPose of the keyframes and UpdateMapPoints of the moved points (UpdateNormalAndDepth, :511), which need
+    mpRefKF on the points and mvScaleFactors on pCurMKF; what UpdateMapPoints returns is the result's "update", the points it was given "updated".  The
+    wrapper hands the store the HOST copies of kf_t and pos it has read back for SetPose / SetWorldPos anyway; the chain without a host visit is the C
+    calls' (the result's "arrays" hold the device arrays of a device-kind call)."""
+    kfs, points, arrays = _essential_graph_lists(pMap, pLoopMKF, pCurMKF, NonCorrectedSim3, CorrectedSim3, LoopConnections)
+    r = OptimizeEssentialGraphArrays(*arrays, device=device, ctx=ctx)
+    if r["status"] != 0:
+        return r
+    for i, k in enumerate(kfs):
+        k.SetPose(r["pose"][i].reshape(4, 4).copy())
+    moved = [p for p in range(len(points)) if arrays[8][p] >= 0]
+    for p in moved:
+        mp = points[p]
+        mp.SetWorldPos(r["pos"][p].copy()) if hasattr(mp, "SetWorldPos") else setattr(mp, "mWorldPos", r["pos"][p].copy())
+    if store is not None:
+        store.SetPose(kfs, ts=r["kf_t"])
+        if moved and all(hasattr(points[p], "mpRefKF") for p in moved):
+            r["updated"] = [points[p] for p in moved]
+            r["update"] = store.UpdateMapPoints(r["updated"], r["pos"][moved], [points[p].mpRefKF for p in moved], pCurMKF.mvScaleFactors)
+    return r
