@@ -1,5 +1,6 @@
 // mcs_essgraph.hip — cOptimizer::OptimizeEssentialGraph (src/cOptimizerLoopStuff.cpp:267-513) as one problem over the whole device, and the entry point
 // mcs_optimize_essential_graph (include/mcs_c.h).  DESIGN.md 4o; the statement-by-statement restatement the kernels are held to is tests/essgraph_model.py.
+// The Levenberg-Marquardt steps, the wave sums and the ordered lists are csrc/mcs_lm.h's, the Sim3 arithmetic csrc/mcs_sim3g.h's.
 //
 // The phases are separate launches on the context's stream — no grid-wide barrier, no workgroup waits for another inside a launch:
 //   k_eg_prepare       per edge: the guards, the measurement Sjw * Swi from Scw / Snc
@@ -27,20 +28,20 @@
 #include "mcs_essgraph.h"
 #include "mcs_geom.h"
 #include "mcs_sim3g.h"
-#include <cfloat>
+#include "mcs_lm.h"
 
 using namespace mcs;
 
 namespace {
 
-enum { STOP_ITERATIONS = 0, STOP_GAIN = 1, STOP_TRIALS = 2, STOP_NBAD = 3, STOP_NOT_RUN = 4, STOP_CAP = 5 };
 constexpr int kEdgeDoubles = 49 + 49 + 7 + 1;   // A [7][7] (row: residual component, column: d), B, e, chi2
 constexpr int NB = kEgPanel;
 constexpr int kMaxN = 7 * kEgMaxFree;
 
 struct EgCtl {   // the Levenberg-Marquardt state, on the device
-	double lambda, ni, currentChi, iniChi, postChi, lastChi, rho, sumChi, sumScale;
-	int nonfinite, solveOk, qmax, lmBad, accepted, nEdgesOk;
+	LmState lm;
+	double sumChi, sumScale;   // of k_eg_reduce
+	int nonfinite, solveOk, accepted, nEdgesOk;
 };
 struct EgRecord {   // 64 bytes, page-locked host memory: what the host loop reads
 	int more, resultOk, why, stopNow, qmax, nonfinite, nEdgesOk, accepted;
@@ -63,21 +64,6 @@ struct EgDev {
 	EgCtl* ctl; EgRecord* rec;
 };
 
-__device__ __forceinline__ bool finite_(double v) { return fabs(v) <= DBL_MAX; }
-__device__ __forceinline__ Sim3g load8(const double* p) { Sim3g S; S.q[0] = p[0]; S.q[1] = p[1]; S.q[2] = p[2]; S.q[3] = p[3]; S.t[0] = p[4]; S.t[1] = p[5]; S.t[2] = p[6]; S.s = p[7]; return S; }
-__device__ __forceinline__ void store8(const Sim3g& S, double* p) { p[0] = S.q[0]; p[1] = S.q[1]; p[2] = S.q[2]; p[3] = S.q[3]; p[4] = S.t[0]; p[5] = S.t[1]; p[6] = S.t[2]; p[7] = S.s; }
-
-template <int N>
-__device__ __forceinline__ void wave_sum(double* acc) {
-#pragma unroll
-	for (int k = 0; k < N; ++k) {
-		double v = acc[k];
-#pragma unroll
-		for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-		acc[k] = v;   // lane 0 holds the sum
-	}
-}
-
 // ---------------------------------------------------------------------------------------------- once per call
 __global__ void k_eg_prepare(EgDev d) {
 	const int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -87,39 +73,23 @@ __global__ void k_eg_prepare(EgDev d) {
 	d.ok[e] = ok;
 	if (!ok) return;
 	const bool nc = d.edgeKind[e] != 0;
-	const Sim3g Siw = load8((nc && d.hasNc[i] ? d.Snc : d.Scw) + 8 * (size_t)i);
-	const Sim3g Sjw = load8((nc && d.hasNc[j] ? d.Snc : d.Scw) + 8 * (size_t)j);
-	store8(sim3_mul(Sjw, sim3_inverse(Siw)), d.meas + 8 * (size_t)e);
+	const Sim3g Siw = sim3_load((nc && d.hasNc[i] ? d.Snc : d.Scw) + 8 * (size_t)i);
+	const Sim3g Sjw = sim3_load((nc && d.hasNc[j] ? d.Snc : d.Scw) + 8 * (size_t)j);
+	sim3_store(sim3_mul(Sjw, sim3_inverse(Siw)), d.meas + 8 * (size_t)e);
 	atomicAdd(&d.ctl->nEdgesOk, 1);
 }
 
-// the edges at free vertex blockIdx.x in ascending order: Fill = false counts, Fill = true writes behind vOff (the ballot compaction of k_lba_kf_lists)
+// the edges at free vertex blockIdx.x in ascending order: Fill = false counts, Fill = true writes behind vOff
 template <bool Fill>
 __global__ void __launch_bounds__(256) k_eg_lists(EgDev d) {
-	__shared__ int wc[4];
-	const int f = blockIdx.x, v = d.freeKf[f], lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	int running = 0;
-	int* const out = Fill ? d.vList + d.vOff[f] : nullptr;
-	for (int base = 0; base < d.nEdges; base += 256) {
-		const int e = base + threadIdx.x;
-		const bool m = e < d.nEdges && d.ok[e] && (d.edgeI[e] == v || d.edgeJ[e] == v);
-		const unsigned long long bal = __ballot(m);
-		if (lane == 0) wc[wave] = __popcll(bal);
-		__syncthreads();
-		int before = 0, all = 0;
-		for (int w = 0; w < 4; ++w) { if (w < wave) before += wc[w]; all += wc[w]; }
-		if (Fill && m) out[running + before + __popcll(bal & ((1ull << lane) - 1ull))] = e;
-		running += all;
-		__syncthreads();
-	}
-	if (!Fill && threadIdx.x == 0) d.vCount[f] = running;
+	const int f = blockIdx.x, v = d.freeKf[f];
+	const int n = compact_indices<Fill, 256>(d.nEdges, [&](int e) { return d.ok[e] && (d.edgeI[e] == v || d.edgeJ[e] == v); }, Fill ? d.vList + d.vOff[f] : nullptr);
+	if (!Fill && threadIdx.x == 0) d.vCount[f] = n;
 }
 
 __global__ void k_eg_offsets(EgDev d) {
 	if (blockIdx.x || threadIdx.x) return;
-	int at = 0;
-	for (int f = 0; f < d.nFree; ++f) { d.vOff[f] = at; at += d.vCount[f]; }
-	d.vOff[d.nFree] = at;
+	list_offsets(d.vCount, d.vOff, d.nFree);
 	EgRecord r{};
 	r.nEdgesOk = d.ctl->nEdgesOk;
 	*d.rec = r;
@@ -131,14 +101,14 @@ __global__ void k_eg_vertices(EgDev d, const double* est, int nEval) {
 	const int t = blockIdx.x * blockDim.x + threadIdx.x;
 	if (t >= d.nKfs * nEval) return;
 	const int v = t / nEval, k = t - v * nEval;
-	Sim3g S = load8(est + 8 * (size_t)v);
+	Sim3g S = sim3_load(est + 8 * (size_t)v);
 	if (k > 0) {
 		double u[7] = {0, 0, 0, 0, 0, 0, 0};
 		u[(k - 1) >> 1] = (k & 1) ? 1e-9 : -1e-9;
 		S = sim3_mul(sim3_exp(u), S);
 	}
-	store8(S, d.V + 8 * ((size_t)v * 15 + k));
-	store8(sim3_inverse(S), d.Vinv + 8 * ((size_t)v * 15 + k));
+	sim3_store(S, d.V + 8 * ((size_t)v * 15 + k));
+	sim3_store(sim3_inverse(S), d.Vinv + 8 * ((size_t)v * 15 + k));
 }
 
 // Two edges per workgroup of 64, 32 lanes each, 29 of them at work: evaluation 0 is the residual, 1..14 move vertex i, 15..28 vertex j
@@ -152,7 +122,7 @@ __global__ void __launch_bounds__(64) k_eg_linearise(EgDev d) {
 	if (live && lane < 29) {
 		const int ki = lane < 15 ? lane : 0, kj = lane < 15 ? 0 : lane - 14;
 		double out[7];
-		sim3_edge_error(load8(d.meas + 8 * (size_t)e), load8(d.V + 8 * ((size_t)i * 15 + ki)), load8(d.Vinv + 8 * ((size_t)j * 15 + kj)), out);
+		sim3_edge_error(sim3_load(d.meas + 8 * (size_t)e), sim3_load(d.V + 8 * ((size_t)i * 15 + ki)), sim3_load(d.Vinv + 8 * ((size_t)j * 15 + kj)), out);
 #pragma unroll
 		for (int k = 0; k < 7; ++k) r[half][lane][k] = out[k];
 	}
@@ -185,7 +155,7 @@ __global__ void k_eg_residuals(EgDev d) {
 	if (e >= d.nEdges) return;
 	if (!d.ok[e]) { d.eChi[e] = 0.0; return; }
 	double r[7];
-	sim3_edge_error(load8(d.meas + 8 * (size_t)e), load8(d.V + 8 * (size_t)d.edgeI[e] * 15), load8(d.Vinv + 8 * (size_t)d.edgeJ[e] * 15), r);
+	sim3_edge_error(sim3_load(d.meas + 8 * (size_t)e), sim3_load(d.V + 8 * (size_t)d.edgeI[e] * 15), sim3_load(d.Vinv + 8 * (size_t)d.edgeJ[e] * 15), r);
 	double c = r[0] * r[0];
 #pragma unroll
 	for (int k = 1; k < 7; ++k) c += r[k] * r[k];
@@ -198,7 +168,7 @@ __global__ void __launch_bounds__(1024) k_eg_reduce(EgDev d, int trial) {
 	double acc[2] = {0.0, 0.0};
 	for (int e = threadIdx.x; e < d.nEdges; e += 1024) acc[0] += d.eChi[e];
 	if (trial) {
-		const double lam = d.ctl->lambda;
+		const double lam = d.ctl->lm.lambda;
 		for (int k = threadIdx.x; k < d.N; k += 1024) acc[1] += d.x[k] * (lam * d.x[k] + d.b[k]);
 	}
 	wave_sum<2>(acc);
@@ -216,12 +186,11 @@ __global__ void __launch_bounds__(1024) k_eg_reduce(EgDev d, int trial) {
 __global__ void k_eg_iter_begin(EgDev d, int it) {
 	if (blockIdx.x || threadIdx.x) return;
 	EgCtl& c = *d.ctl;
-	c.currentChi = c.iniChi = c.postChi = c.sumChi;
+	lm_iter_begin(c.lm, c.sumChi);
 	if (it == 0) {
 		if (!finite_(c.sumChi)) c.nonfinite = 1;
-		c.lambda = 1e-6; c.ni = 2.0; c.lmBad = 0;   // computeLambdaInit returns the user's value (optimization_algorithm_levenberg.cpp:168-169)
+		lm_start(c.lm, 1e-6);   // not lm_lambda_init: computeLambdaInit returns the user's value (optimization_algorithm_levenberg.cpp:168-169)
 	}
-	c.qmax = 0;
 }
 
 // ---------------------------------------------------------------------------------------------- a trial
@@ -259,7 +228,7 @@ __global__ void __launch_bounds__(64) k_eg_assemble(EgDev d) {
 			d.S[(size_t)(7 * f + r) * d.N + 7 * g + c] += s;
 		}
 	}
-	if (lane < 49) { if (c <= r) d.S[(size_t)(7 * f + r) * d.N + 7 * f + c] = acc + (r == c ? d.ctl->lambda : 0.0); }
+	if (lane < 49) { if (c <= r) d.S[(size_t)(7 * f + r) * d.N + 7 * f + c] = acc + (r == c ? d.ctl->lm.lambda : 0.0); }
 	else if (lane < 56) d.b[7 * f + lane - 49] = acc;
 	if (f == 0 && lane == 0) d.ctl->solveOk = 1;
 }
@@ -402,13 +371,13 @@ __global__ void k_eg_apply(EgDev d) {
 	const int v = blockIdx.x * blockDim.x + threadIdx.x;
 	if (v >= d.nKfs) return;
 	const int f = d.fidx[v];
-	Sim3g S = load8(d.est + 8 * (size_t)v);
+	Sim3g S = sim3_load(d.est + 8 * (size_t)v);
 	if (f >= 0) {
 		double u[7];
 		for (int k = 0; k < 7; ++k) u[k] = d.x[7 * f + k];
 		S = sim3_mul(sim3_exp(u), S);
 	}
-	store8(S, d.estT + 8 * (size_t)v);
+	sim3_store(S, d.estT + 8 * (size_t)v);
 }
 
 // OptimizationAlgorithmLevenberg::solve behind the trial's evaluation (optimization_algorithm_levenberg.cpp:123-163) and — when the trial loop ends — its
@@ -416,45 +385,20 @@ __global__ void k_eg_apply(EgDev d) {
 __global__ void k_eg_decide(EgDev d, int it) {
 	if (blockIdx.x || threadIdx.x) return;
 	EgCtl& c = *d.ctl;
+	LmState& lm = c.lm;
 	const double raw = c.sumChi;
-	const double tempChi = c.solveOk ? raw : DBL_MAX;
-	double rho = c.currentChi - tempChi;
-	double scale = c.sumScale;
-	scale += 1e-3;
-	rho /= scale;
-	c.postChi = raw;
-	if (rho > 0 && finite_(tempChi)) {
-		double alpha = 1. - pow(2 * rho - 1, 3.0);
-		alpha = fmin(alpha, 2. / 3.);
-		c.lambda *= fmax(1. / 3., alpha);
-		c.ni = 2;
-		c.currentChi = tempChi;
-		c.accepted = 1;
-	} else {
-		c.lambda *= c.ni;
-		c.ni *= 2;
-		c.accepted = 0;
-	}
-	++c.qmax;
-	c.rho = rho;
+	lm.postChi = raw;   // accepted or not: the action reads the errors the edges hold, and nothing evaluates them again behind a rejected trial
+	c.accepted = lm_trial(lm, raw, c.solveOk != 0, c.sumScale) ? 1 : 0;   // computeScale: k_eg_reduce summed all of it
 	EgRecord r{};
-	r.more = rho < 0 && c.qmax < 10;
+	r.more = lm_more(lm);   // no stop-flag term: the run ends behind the iteration whose action sets the flag
 	r.resultOk = 1; r.why = STOP_ITERATIONS;
 	if (!r.more) {
-		if (c.qmax == 10 || rho == 0) { r.resultOk = 0; r.why = STOP_TRIALS; }
-		else {
-			c.lmBad = (c.iniChi - c.currentChi) * 1e3 < c.iniChi ? c.lmBad + 1 : 0;
-			if (c.lmBad >= 3) { r.resultOk = 0; r.why = STOP_NBAD; }
-		}
-		if (it == 0) c.lastChi = c.postChi;
-		else if (it < 15) {
-			const double gain = (c.lastChi - c.postChi) / c.postChi;
-			c.lastChi = c.postChi;
-			if (gain >= 0 && gain < 1e-6) { r.stopNow = 1; if (r.resultOk) r.why = STOP_GAIN; }
-		} else { r.stopNow = 1; if (r.resultOk) r.why = STOP_CAP; }   // iteration >= _maxIterations: stop without a test
+		if (const int end = lm_iter_end(lm)) { r.resultOk = 0; r.why = end; }
+		if (it < 15) { if (lm_gain_stop(lm, it)) { r.stopNow = 1; if (r.resultOk) r.why = STOP_GAIN; } }
+		else { r.stopNow = 1; if (r.resultOk) r.why = STOP_CAP; }   // iteration >= _maxIterations: stop without a test
 	}
-	r.qmax = c.qmax; r.nonfinite = c.nonfinite; r.nEdgesOk = c.nEdgesOk; r.accepted = c.accepted;
-	r.lambda = c.lambda; r.chi2 = c.currentChi;
+	r.qmax = lm.qmax; r.nonfinite = c.nonfinite; r.nEdgesOk = c.nEdgesOk; r.accepted = c.accepted;
+	r.lambda = lm.lambda; r.chi2 = lm.currentChi;   // the chi2 of the estimate, not the action's last
 	*d.rec = r;
 }
 
@@ -468,8 +412,8 @@ __global__ void k_eg_accept(EgDev d) {
 __global__ void k_eg_writeback(EgDev d) {
 	const int t = blockIdx.x * blockDim.x + threadIdx.x;
 	if (t < d.nKfs) {
-		const Sim3g S = load8(d.est + 8 * (size_t)t);
-		store8(S, d.ScwOut + 8 * (size_t)t);
+		const Sim3g S = sim3_load(d.est + 8 * (size_t)t);
+		sim3_store(S, d.ScwOut + 8 * (size_t)t);
 		double R[9], M[16], inv[16];
 		quat_to_mat(S.q, R);
 		for (int i = 0; i < 3; ++i) {
@@ -486,14 +430,12 @@ __global__ void k_eg_writeback(EgDev d) {
 		if (r >= 0 && r < d.nKfs) {   // corrected_Swr.map(Srw.map(X)), :504-510
 			const double X[3] = {d.posIO[3 * (size_t)t], d.posIO[3 * (size_t)t + 1], d.posIO[3 * (size_t)t + 2]};
 			double a[3], b[3];
-			sim3_map(load8(d.Scw + 8 * (size_t)r), X, a);
-			sim3_map(sim3_inverse(load8(d.est + 8 * (size_t)r)), a, b);
+			sim3_map(sim3_load(d.Scw + 8 * (size_t)r), X, a);
+			sim3_map(sim3_inverse(sim3_load(d.est + 8 * (size_t)r)), a, b);
 			for (int k = 0; k < 3; ++k) d.posIO[3 * (size_t)t + k] = b[k];
 		}
 	}
 }
-
-inline dim3 blocks(size_t n, int per) { return dim3((unsigned)std::max<size_t>(1, (n + per - 1) / per)); }
 
 }  // namespace
 

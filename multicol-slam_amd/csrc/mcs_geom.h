@@ -1,4 +1,4 @@
-// mcs_geom.h — the rig geometry of the map-side kernels (mcs_project / mcs_frustum / mcs_lastframe / mcs_newpoints / mcs_sim3 / mcs_poseopt), stated once.
+// mcs_geom.h — the rig geometry of the map-side kernels (mcs_project / mcs_frustum / mcs_lastframe / mcs_newpoints / mcs_sim3 / mcs_poseopt / mcs_lba), stated once.
 // Each function restates one statement of the reference's scalar C++ and is held to it bit for bit: FP64, no contraction, every sum in the reference's order.
 // Host and device: tests/test_geom_cpu.py compiles this header alone for the host and compares it with the reference's compiled code.
 #pragma once
@@ -114,6 +114,57 @@ MCS_GEOM void omni_world_to_img(const OcamDev& cam, double x, double y, double z
 	const double vv = y / norm * rho;
 	u = uu * cam.c + vv * cam.d + cam.u0;
 	v = uu * cam.e + vv + cam.v0;
+}
+
+// ---------------------------------------------------------------------------------------------- the derivatives of the optimisers (mcs_poseopt / mcs_lba.hip)
+// Derived here by the chain rule — the reference's Jacobians are generated text and are not used in any form — and held bit for bit to the same statements
+// of tests/poseopt_model.py (d_world_to_img, d_cayley2rot) by tests/test_lm_cpu.py.
+
+// the coefficients of d rho / d theta for horner_fixed: k * invP[k], zero behind the degree
+MCS_GEOM void ocam_dinvp(const mcs_ocam& m, const OcamDev& o, double* dInvP) {
+	for (int k = 0; k < MCS_MAX_POLY; ++k) dInvP[k] = k + 1 < o.invP_deg ? m.invP[k + 1] * (double)(k + 1) : 0.0;
+}
+
+// d(u, v) / d(x, y, z) of omni_world_to_img; the norm == 0 -> 1e-14 branch is a constant
+MCS_GEOM void d_world_to_img(const OcamDev& cam, const double* dInvP, double x, double y, double z, double D[2][3]) {
+	const double n0 = sqrt(x * x + y * y);
+	const bool constant = n0 == 0.0;
+	const double n = constant ? 1e-14 : n0;
+	const double dn[3] = {constant ? 0.0 : x / n, constant ? 0.0 : y / n, 0.0};
+	const double q = -z / n;
+	const double theta = atan(q);
+	const double dthdq = 1.0 / (1.0 + q * q);
+	const double rho = horner_fixed(cam.invP, theta), drho_dth = horner_fixed(dInvP, theta);
+	const double fx = x / n, fy = y / n;
+	for (int k = 0; k < 3; ++k) {
+		const double dq = k == 2 ? -1.0 / n : (z / (n * n)) * dn[k];
+		const double drho = drho_dth * (dthdq * dq);
+		const double dfx = -(x / (n * n)) * dn[k] + (k == 0 ? 1.0 / n : 0.0);
+		const double dfy = -(y / (n * n)) * dn[k] + (k == 1 ? 1.0 / n : 0.0);
+		const double duu = dfx * rho + fx * drho, dvv = dfy * rho + fy * drho;
+		D[0][k] = duu * cam.c + dvv * cam.d;
+		D[1][k] = duu * cam.e + dvv;
+	}
+}
+
+// A_i = Rc^T (dRt/dc_i)^T, i = 0..2, row-major 3x3 each: with Mct = Mt * Mc the camera-frame point is p = Rc^T Rt^T (X - t) - Rc^T tc, so
+// dp/dc_i = A_i (X - t).  cayley2rot is R = N / s with s = 1 + |c|^2, so dR/dc_i = (dN/dc_i - 2 c_i R) / s.  Mt = cayley2hom(pose), McH = cayley2hom(M_c_min[c]).
+MCS_GEOM void cayley_rot_factors(const double* pose, const double* Mt, const double* McH, double* A) {
+	const double c1 = pose[0], c2 = pose[1], c3 = pose[2];
+	const double s = 1.0 + c1 * c1 + c2 * c2 + c3 * c3;
+	const double dN[3][9] = {{2 * c1, 2 * c2, 2 * c3, 2 * c2, -2 * c1, -2.0, 2 * c3, 2.0, -2 * c1},
+	                         {-2 * c2, 2 * c1, 2.0, 2 * c1, 2 * c2, 2 * c3, -2.0, 2 * c3, -2 * c2},
+	                         {-2 * c3, -2.0, 2 * c1, 2.0, -2 * c3, 2 * c2, 2 * c1, 2 * c2, 2 * c3}};
+	for (int i = 0; i < 3; ++i) {
+		double dR[9];
+		for (int k = 0; k < 9; ++k) dR[k] = (dN[i][k] - 2.0 * pose[i] * Mt[4 * (k / 3) + k % 3]) / s;
+		for (int r = 0; r < 3; ++r)
+			for (int k = 0; k < 3; ++k) {
+				double a = 0;
+				for (int j = 0; j < 3; ++j) a += McH[4 * j + r] * dR[3 * k + j];
+				A[9 * i + 3 * r + k] = a;
+			}
+	}
 }
 
 // cCamModelGeneral_::isPointInMirrorMask(u, v, 0) (src/cam_model_omni.cpp:163-178): cvRound, the open bounds test, then the level-0 mask (nullptr: bounds only).

@@ -1,5 +1,7 @@
 // mcs_lba.hip — cOptimizer::LocalBundleAdjustment (src/cOptimizer.cpp:461-874) as one problem over the whole device, and the entry point
 // mcs_local_bundle_adjustment (include/mcs_c.h).  DESIGN.md 4n; the statement-by-statement restatement the kernels are held to is tests/lba_model.py.
+// The Levenberg-Marquardt steps, the Huber pair, the wave sums and the ordered lists are csrc/mcs_lm.h's, the matrices, the camera and the derivatives
+// csrc/mcs_geom.h's.
 //
 // The phases are separate launches on the context's stream — no grid-wide barrier, no workgroup waits for another inside a launch:
 //   k_lba_prepare      per point: its edge range, the guards, the point of every edge, the level of every edge
@@ -25,21 +27,20 @@
 // which is the rotation block of invMat(Mt Mc), and dp/dc_i = Rc^T (dRt/dc_i)^T (X - t); d(u, v)/dp differentiates WorldToImg; e = z - (u, v).
 #include "mcs_lba.h"
 #include "mcs_geom.h"
-#include <cfloat>
+#include "mcs_lm.h"
 
 using namespace mcs;
 
 namespace {
 
-enum { STOP_ITERATIONS = 0, STOP_GAIN = 1, STOP_TRIALS = 2, STOP_NBAD = 3, STOP_NOT_RUN = 4 };
 enum { PT_WRITTEN = 0, PT_KEPT = 1, PT_BAD = 2 };
 constexpr int kRigDoubles = 16 + 27;   // inv (4x4), then A_i = Rc^T (dRt/dc_i)^T, i = 0..2
 constexpr int kEdgeDoubles = 12 + 6 + 2 + 1;   // Jp [2][6], Jl [2][3], e [2], rho[1] * information
 
 struct LbaCtl {   // the Levenberg-Marquardt state, on the device
-	double lambda, ni, currentChi, iniChi, postChi, lastChi, rho;
+	LmState lm;
 	double sumChi, maxDiag, sumScale;   // of k_lba_reduce
-	int nonfinite, solveOk, qmax, lmBad, accepted, nActive, nErased[2];
+	int nonfinite, solveOk, accepted, nActive, nErased[2];
 };
 struct LbaRecord {   // 64 bytes, page-locked host memory: what the host loop reads
 	int more, resultOk, why, gainStop, qmax, nonfinite, nActive, accepted;
@@ -69,45 +70,10 @@ struct LbaDev {
 	LbaCtl* ctl; LbaRecord* rec;
 };
 
-__device__ __forceinline__ bool finite_(double v) { return fabs(v) <= DBL_MAX; }
-
-// d(u, v) / d(x, y, z) of omni_world_to_img; the norm == 0 -> 1e-14 branch is a constant (restated from mcs_poseopt.hip)
-__device__ void lba_d_world_to_img(const OcamDev& cam, const double* dInvP, double x, double y, double z, double D[2][3]) {
-	const double n0 = sqrt(x * x + y * y);
-	const bool constant = n0 == 0.0;
-	const double n = constant ? 1e-14 : n0;
-	const double dn[3] = {constant ? 0.0 : x / n, constant ? 0.0 : y / n, 0.0};
-	const double q = -z / n;
-	const double theta = atan(q);
-	const double dthdq = 1.0 / (1.0 + q * q);
-	const double rho = horner_fixed(cam.invP, theta), drho_dth = horner_fixed(dInvP, theta);
-	const double fx = x / n, fy = y / n;
-	for (int k = 0; k < 3; ++k) {
-		const double dq = k == 2 ? -1.0 / n : (z / (n * n)) * dn[k];
-		const double drho = drho_dth * (dthdq * dq);
-		const double dfx = -(x / (n * n)) * dn[k] + (k == 0 ? 1.0 / n : 0.0);
-		const double dfy = -(y / (n * n)) * dn[k] + (k == 1 ? 1.0 / n : 0.0);
-		const double duu = dfx * rho + fx * drho, dvv = dfy * rho + fy * drho;
-		D[0][k] = duu * cam.c + dvv * cam.d;
-		D[1][k] = duu * cam.e + dvv;
-	}
-}
-
 __device__ __forceinline__ bool point_range(const LbaDev& d, int p, int& a, int& b) {
 	a = d.ptFirst[p]; b = d.ptFirst[p + 1];
 	if (a < 0 || a > b || b > d.nEdges) { a = b = 0; return false; }
 	return true;
-}
-
-template <int N>
-__device__ __forceinline__ void wave_sum(double* acc) {
-#pragma unroll
-	for (int k = 0; k < N; ++k) {
-		double v = acc[k];
-#pragma unroll
-		for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-		acc[k] = v;   // lane 0 holds the sum
-	}
 }
 
 // ---------------------------------------------------------------------------------------------- once per call
@@ -117,7 +83,7 @@ __global__ void k_lba_cams(LbaDev d) {
 	const mcs_ocam& m = d.cams[c];
 	const OcamDev o = ocam_dev_of(m);
 	d.cam[c] = o;
-	for (int k = 0; k < MCS_MAX_POLY; ++k) d.dInvP[c * MCS_MAX_POLY + k] = k + 1 < o.invP_deg ? m.invP[k + 1] * (double)(k + 1) : 0.0;
+	ocam_dinvp(m, o, d.dInvP + c * MCS_MAX_POLY);
 	cayley2hom(d.McMin + 6 * c, d.McH + 16 * c);
 }
 
@@ -142,30 +108,14 @@ __global__ void k_lba_prepare(LbaDev d) {   // d.level was set to 1 everywhere, 
 // the edges of free keyframe blockIdx.x in ascending order: Fill = false counts, Fill = true writes behind kfOff
 template <bool Fill>
 __global__ void __launch_bounds__(256) k_lba_kf_lists(LbaDev d) {
-	__shared__ int wc[4];
-	const int f = blockIdx.x, kf = d.freeKf[f], lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	int running = 0;
-	int* const out = Fill ? d.kfList + d.kfOff[f] : nullptr;
-	for (int base = 0; base < d.nEdges; base += 256) {
-		const int e = base + threadIdx.x;
-		const bool m = e < d.nEdges && d.edgeKf[e] == kf;
-		const unsigned long long bal = __ballot(m);
-		if (lane == 0) wc[wave] = __popcll(bal);
-		__syncthreads();
-		int before = 0, all = 0;
-		for (int w = 0; w < 4; ++w) { if (w < wave) before += wc[w]; all += wc[w]; }
-		if (Fill && m) out[running + before + __popcll(bal & ((1ull << lane) - 1ull))] = e;
-		running += all;
-		__syncthreads();
-	}
-	if (!Fill && threadIdx.x == 0) d.kfCount[f] = running;
+	const int f = blockIdx.x, kf = d.freeKf[f];
+	const int n = compact_indices<Fill, 256>(d.nEdges, [&](int e) { return d.edgeKf[e] == kf; }, Fill ? d.kfList + d.kfOff[f] : nullptr);
+	if (!Fill && threadIdx.x == 0) d.kfCount[f] = n;
 }
 
 __global__ void k_lba_kf_offsets(LbaDev d) {
 	if (blockIdx.x || threadIdx.x) return;
-	int at = 0;
-	for (int f = 0; f < d.nFree; ++f) { d.kfOff[f] = at; at += d.kfCount[f]; }
-	d.kfOff[d.nFree] = at;
+	list_offsets(d.kfCount, d.kfOff, d.nFree);
 }
 
 // ---------------------------------------------------------------------------------------------- an evaluation
@@ -184,21 +134,7 @@ __global__ void k_lba_rigs(LbaDev d, const double* poses, int build, int freeOnl
 	inv_mat(Mct, inv);
 	for (int k = 0; k < 16; ++k) out[k] = inv[k];
 	if (!build) return;
-	const double c1 = pose[0], c2 = pose[1], c3 = pose[2];
-	const double s = 1.0 + c1 * c1 + c2 * c2 + c3 * c3;
-	const double dN[3][9] = {{2 * c1, 2 * c2, 2 * c3, 2 * c2, -2 * c1, -2.0, 2 * c3, 2.0, -2 * c1},
-	                         {-2 * c2, 2 * c1, 2.0, 2 * c1, 2 * c2, 2 * c3, -2.0, 2 * c3, -2 * c2},
-	                         {-2 * c3, -2.0, 2 * c1, 2.0, -2 * c3, 2 * c2, 2 * c1, 2 * c2, 2 * c3}};
-	for (int i = 0; i < 3; ++i) {
-		double dR[9];
-		for (int k = 0; k < 9; ++k) dR[k] = (dN[i][k] - 2.0 * pose[i] * Mt[4 * (k / 3) + k % 3]) / s;
-		for (int r = 0; r < 3; ++r)
-			for (int k = 0; k < 3; ++k) {
-				double a = 0;
-				for (int j = 0; j < 3; ++j) a += McH[4 * j + r] * dR[3 * k + j];
-				out[16 + 9 * i + 3 * r + k] = a;
-			}
-	}
+	cayley_rot_factors(pose, Mt, McH, out + 16);
 }
 
 // One wave per point, lanes over its edges (looping above 64).  The active edges are those at level 0.  Writes the plain chi2 of every edge of the point and
@@ -228,14 +164,13 @@ __global__ void __launch_bounds__(256) k_lba_linearise(LbaDev d, const double* p
 		const double e0 = (double)d.key[e].x - u, e1 = (double)d.key[e].y - v;
 		const double w = d.invSigma2[d.key[e].octave];
 		const double c2 = e0 * (w * e0) + e1 * (w * e1);   // _error.dot(information() * _error)
-		double rho0, rho1;                                  // RobustKernelHuber::robustify
-		if (c2 <= d.dsqr) { rho0 = c2; rho1 = 1.0; }
-		else { const double sq = sqrt(c2); rho0 = 2 * sq * d.delta - d.dsqr; rho1 = d.delta / sq; }
+		double rho0, rho1;
+		huber_robustify(c2, d.delta, d.dsqr, rho0, rho1);
 		d.eChi[e] = c2;
 		acc[9] += rho0;
 		if constexpr (Build) {
 			double D[2][3], Jp[2][6], Jl[2][3];
-			lba_d_world_to_img(cam, d.dInvP + c * MCS_MAX_POLY, pc[0], pc[1], pc[2], D);
+			d_world_to_img(cam, d.dInvP + c * MCS_MAX_POLY, pc[0], pc[1], pc[2], D);
 			const double* pose = poses + 6 * kf;
 			const double dd[3] = {X[0] - pose[3], X[1] - pose[4], X[2] - pose[5]};
 #pragma unroll
@@ -356,7 +291,7 @@ __global__ void __launch_bounds__(256) k_lba_pose_blocks(LbaDev d) {
 __global__ void k_lba_iter_begin(LbaDev d, int first, int it) {
 	if (blockIdx.x || threadIdx.x) return;
 	LbaCtl& c = *d.ctl;
-	c.currentChi = c.iniChi = c.postChi = c.sumChi;
+	lm_iter_begin(c.lm, c.sumChi);
 	if (first) {   // the screen of the first evaluation: every edge's residual, Jacobians and weight (k_lba_linearise), the Huber pair, the sums
 		bool nf = c.nonfinite || !finite_(d.delta) || !finite_(d.dsqr) || !finite_(c.sumChi);
 		for (int k = 0; k < 21 * d.nFree; ++k) nf |= !finite_(d.Hpp[k]);
@@ -365,13 +300,9 @@ __global__ void k_lba_iter_begin(LbaDev d, int first, int it) {
 	}
 	if (it == 0) {   // computeLambdaInit: tau * max |H_jj| over poses AND points
 		double m = c.maxDiag;
-		for (int f = 0; f < d.nFree; ++f) {
-			int s = 0;
-			for (int r = 0; r < 6; ++r) { m = fmax(fabs(d.Hpp[21 * f + s]), m); s += 6 - r; }
-		}
-		c.lambda = 1e-5 * m; c.ni = 2.0; c.lmBad = 0;
+		for (int f = 0; f < d.nFree; ++f) m = max_abs_diag<6>(d.Hpp + 21 * f, m);
+		lm_start(c.lm, lm_lambda_init(m));
 	}
-	c.qmax = 0;
 }
 
 // ---------------------------------------------------------------------------------------------- a trial
@@ -380,7 +311,7 @@ __global__ void k_lba_dinv(LbaDev d) {
 	const int p = blockIdx.x * blockDim.x + threadIdx.x;
 	if (p >= d.nPoints || !d.ptAct[p]) return;
 	const double* H = d.Hll + 6 * (size_t)p;
-	const double lam = d.ctl->lambda;
+	const double lam = d.ctl->lm.lambda;
 	const double M[3][3] = {{H[0] + lam, H[1], H[2]}, {H[1], H[3] + lam, H[4]}, {H[2], H[4], H[5] + lam}};
 	double cof[3][3];
 	for (int i = 0; i < 3; ++i)
@@ -456,7 +387,7 @@ __global__ void __launch_bounds__(64) k_lba_schur(LbaDev d) {
 	wave_sum<42>(acc);
 	if (lane != 0) return;
 	const int N = 6 * d.nFree;
-	const double lam = d.ctl->lambda;
+	const double lam = d.ctl->lm.lambda;
 	for (int r = 0; r < 6; ++r)
 		for (int c = 0; c < 6; ++c) {
 			double h = 0.0;
@@ -543,7 +474,7 @@ __global__ void k_lba_apply(LbaDev d) {
 		const double* Di = d.Dinv + 9 * (size_t)p;
 		for (int r = 0; r < 3; ++r) xl[r] = (Di[3 * r] * cl[0] + Di[3 * r + 1] * cl[1]) + Di[3 * r + 2] * cl[2];
 	}
-	const double lam = d.ctl->lambda;
+	const double lam = d.ctl->lm.lambda;
 	double sc = 0.0;
 	for (int k = 0; k < 3; ++k) {
 		d.posT[3 * (size_t)p + k] = d.pos[3 * (size_t)p + k] + xl[k];
@@ -556,48 +487,23 @@ __global__ void k_lba_apply(LbaDev d) {
 __global__ void k_lba_decide(LbaDev d, int stopSeen, int it) {
 	if (blockIdx.x || threadIdx.x) return;
 	LbaCtl& c = *d.ctl;
+	LmState& lm = c.lm;
 	const double raw = c.sumChi;
-	const double tempChi = c.solveOk ? raw : DBL_MAX;
-	double rho = c.currentChi - tempChi;
 	double scale = 0.0;
-	for (int k = 0; k < 6 * d.nFree; ++k) scale += d.xp[k] * (c.lambda * d.xp[k] + d.bp[k]);   // computeScale: all of x and b, poses then points
-	scale += c.sumScale;
-	scale += 1e-3;
-	rho /= scale;
-	if (rho > 0 && finite_(tempChi)) {
-		double alpha = 1. - pow(2 * rho - 1, 3.0);
-		alpha = fmin(alpha, 2. / 3.);
-		c.lambda *= fmax(1. / 3., alpha);
-		c.ni = 2;
-		c.currentChi = tempChi;
-		c.postChi = raw;
-		c.accepted = 1;
-	} else {
-		c.lambda *= c.ni;
-		c.ni *= 2;
-		c.accepted = 0;
-	}
-	++c.qmax;
-	c.rho = rho;
+	for (int k = 0; k < 6 * d.nFree; ++k) scale += d.xp[k] * (lm.lambda * d.xp[k] + d.bp[k]);   // computeScale: all of x and b, poses then points
+	scale += c.sumScale;                                                                       // the points' share, of k_lba_reduce
+	c.accepted = lm_trial(lm, raw, c.solveOk != 0, scale) ? 1 : 0;
+	if (c.accepted) lm.postChi = raw;   // an accepted trial's evaluation is the one the action will judge
 	LbaRecord r{};
-	r.more = rho < 0 && c.qmax < 10 && !stopSeen;
+	r.more = lm_more(lm) && !stopSeen;
 	r.resultOk = 1; r.why = STOP_ITERATIONS;
 	if (!r.more) {
-		if (c.qmax == 10 || rho == 0) { r.resultOk = 0; r.why = STOP_TRIALS; }
-		else {
-			c.lmBad = (c.iniChi - c.currentChi) * 1e3 < c.iniChi ? c.lmBad + 1 : 0;
-			if (c.lmBad >= 3) { r.resultOk = 0; r.why = STOP_NBAD; }
-		}
+		if (const int end = lm_iter_end(lm)) { r.resultOk = 0; r.why = end; }
 		// postIteration(it): the terminate action, on the errors of the current estimate
-		if (it == 0) c.lastChi = c.postChi;
-		else {
-			const double gain = (c.lastChi - c.postChi) / c.postChi;
-			c.lastChi = c.postChi;
-			if (gain >= 0 && gain < 1e-6) r.gainStop = 1;
-		}
+		if (lm_gain_stop(lm, it)) r.gainStop = 1;
 	}
-	r.qmax = c.qmax; r.nonfinite = c.nonfinite; r.nActive = c.nActive; r.accepted = c.accepted;
-	r.lambda = c.lambda; r.chi2 = c.lastChi; r.nErased[0] = c.nErased[0]; r.nErased[1] = c.nErased[1];
+	r.qmax = lm.qmax; r.nonfinite = c.nonfinite; r.nActive = c.nActive; r.accepted = c.accepted;
+	r.lambda = lm.lambda; r.chi2 = lm.lastChi; r.nErased[0] = c.nErased[0]; r.nErased[1] = c.nErased[1];   // chi2: what the action last judged
 	*d.rec = r;
 }
 
@@ -636,7 +542,7 @@ __global__ void k_lba_record(LbaDev d) {
 	if (blockIdx.x || threadIdx.x) return;
 	const LbaCtl& c = *d.ctl;
 	LbaRecord r{};
-	r.nonfinite = c.nonfinite; r.nActive = c.nActive; r.lambda = c.lambda; r.chi2 = c.lastChi; r.nErased[0] = c.nErased[0]; r.nErased[1] = c.nErased[1];
+	r.nonfinite = c.nonfinite; r.nActive = c.nActive; r.lambda = c.lm.lambda; r.chi2 = c.lm.lastChi; r.nErased[0] = c.nErased[0]; r.nErased[1] = c.nErased[1];
 	*d.rec = r;
 }
 
@@ -655,8 +561,6 @@ __global__ void k_lba_writeback(LbaDev d, int full) {
 	}
 	d.ptStateOut[t] = st;
 }
-
-inline dim3 blocks(size_t n, int per) { return dim3((unsigned)std::max<size_t>(1, (n + per - 1) / per)); }
 
 }  // namespace
 

@@ -1,6 +1,7 @@
 // mcs_poseopt.hip — cOptimizer::PoseOptimization (src/cOptimizer.cpp:259-459) for a batch of independent problems: one workgroup per problem, both rounds of the
 // reference's g2o run in one launch, and the entry point mcs_pose_optimization (include/mcs_c.h).  DESIGN.md 4l; the statement-by-statement restatement the
-// kernel is held to is tests/poseopt_model.py.
+// kernel is held to is tests/poseopt_model.py.  The Levenberg-Marquardt steps, the Huber pair, the 6x6 solve and the ordered sums are csrc/mcs_lm.h's, the
+// matrices, the camera and the derivatives csrc/mcs_geom.h's.
 //
 // The edges (features with a map point) are strided over the threads: thread t owns features t, t + kPoseThreads, ... in every pass, and sums them in ascending
 // order.  A pass reduces within a wave by shuffles, then across the waves through LDS in wave order, so a problem's sums do not depend on the batch or the run.
@@ -14,7 +15,7 @@
 // p = Rc^T Rt^T (X - t) - Rc^T tc, so dp/dt = -(Rt Rc)^T and dp/dc_i = Rc^T (dRt/dc_i)^T (X - t); d(u, v)/dp differentiates WorldToImg; e = z - (u, v).
 #include "mcs_poseopt.h"
 #include "mcs_geom.h"
-#include <cfloat>
+#include "mcs_lm.h"
 
 using namespace mcs;
 
@@ -22,7 +23,6 @@ namespace {
 
 constexpr int kWaves = kPoseThreads / 64;
 constexpr int kSums = 28;   // 21 of H (upper triangle, row-major), 6 of b, 1 of the robust chi2
-enum { STOP_ITERATIONS = 0, STOP_GAIN = 1, STOP_TRIALS = 2, STOP_NBAD = 3, STOP_NOT_RUN = 4 };
 
 struct PoseShared {
 	OcamDev cam[32];
@@ -45,24 +45,7 @@ __device__ void camera_state(PoseShared& sh, int c, const double* pose, double* 
 	matx44_mul(Mt, sh.McH[c], Mct);
 	inv_mat(Mct, sh.inv[c]);
 	if (MtMcOut) for (int k = 0; k < 16; ++k) MtMcOut[k] = Mct[k];
-	if (Build) {
-		const double c1 = pose[0], c2 = pose[1], c3 = pose[2];
-		const double s = 1.0 + c1 * c1 + c2 * c2 + c3 * c3;
-		const double dN[3][9] = {{2 * c1, 2 * c2, 2 * c3, 2 * c2, -2 * c1, -2.0, 2 * c3, 2.0, -2 * c1},
-		                         {-2 * c2, 2 * c1, 2.0, 2 * c1, 2 * c2, 2 * c3, -2.0, 2 * c3, -2 * c2},
-		                         {-2 * c3, -2.0, 2 * c1, 2.0, -2 * c3, 2 * c2, 2 * c1, 2 * c2, 2 * c3}};
-		const double* Rc = sh.McH[c];   // rows of 4
-		for (int i = 0; i < 3; ++i) {
-			double dR[9];
-			for (int k = 0; k < 9; ++k) dR[k] = (dN[i][k] - 2.0 * pose[i] * Mt[4 * (k / 3) + k % 3]) / s;
-			for (int r = 0; r < 3; ++r)
-				for (int k = 0; k < 3; ++k) {
-					double a = 0;
-					for (int j = 0; j < 3; ++j) a += Rc[4 * j + r] * dR[3 * k + j];
-					sh.A[c][i][3 * r + k] = a;
-				}
-		}
-	}
+	if (Build) cayley_rot_factors(pose, Mt, sh.McH[c], &sh.A[c][0][0]);
 }
 
 __device__ __forceinline__ bool edge_of(const PoseArgs& a, const mcs_keypoint* keys, const int* cam, const int* points, int i, int& pid, int& c, int& oct) {
@@ -70,50 +53,6 @@ __device__ __forceinline__ bool edge_of(const PoseArgs& a, const mcs_keypoint* k
 	if (pid < 0 || pid >= a.npoints) return false;
 	c = cam[i]; oct = keys[i].octave;
 	return c >= 0 && c < a.nrCams && oct >= 0 && oct < a.nlevels;
-}
-
-// d(u, v) / d(x, y, z) of omni_world_to_img; the norm == 0 -> 1e-14 branch is a constant
-__device__ void d_world_to_img(const OcamDev& cam, const double* dInvP, double x, double y, double z, double D[2][3]) {
-	const double n0 = sqrt(x * x + y * y);
-	const bool constant = n0 == 0.0;
-	const double n = constant ? 1e-14 : n0;
-	const double dn[3] = {constant ? 0.0 : x / n, constant ? 0.0 : y / n, 0.0};
-	const double q = -z / n;
-	const double theta = atan(q);
-	const double dthdq = 1.0 / (1.0 + q * q);
-	const double rho = horner_fixed(cam.invP, theta), drho_dth = horner_fixed(dInvP, theta);
-	const double fx = x / n, fy = y / n;
-	for (int k = 0; k < 3; ++k) {
-		const double dq = k == 2 ? -1.0 / n : (z / (n * n)) * dn[k];
-		const double drho = drho_dth * (dthdq * dq);
-		const double dfx = -(x / (n * n)) * dn[k] + (k == 0 ? 1.0 / n : 0.0);
-		const double dfy = -(y / (n * n)) * dn[k] + (k == 1 ? 1.0 / n : 0.0);
-		const double duu = dfx * rho + fx * drho, dvv = dfy * rho + fy * drho;
-		D[0][k] = duu * cam.c + dvv * cam.d;
-		D[1][k] = duu * cam.e + dvv;
-	}
-}
-
-__device__ __forceinline__ bool finite_(double v) { return fabs(v) <= DBL_MAX; }
-
-// wave shuffles, then the waves in order: tot[0..N) on every thread after the closing barrier
-template <int N>
-__device__ void reduce_sums(PoseShared& sh, double* acc) {
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-	for (int k = 0; k < N; ++k) {
-		double v = acc[k];
-#pragma unroll
-		for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-		if (lane == 0) sh.red[wave][k] = v;
-	}
-	__syncthreads();
-	if (threadIdx.x < N) {
-		double t = sh.red[0][threadIdx.x];
-		for (int w = 1; w < kWaves; ++w) t += sh.red[w][threadIdx.x];
-		sh.tot[threadIdx.x] = t;
-	}
-	__syncthreads();
 }
 
 struct Edges { const mcs_keypoint* keys; const int* cam; const int* points; uint8_t* outlier; int n; };
@@ -137,9 +76,8 @@ __device__ void pass(PoseShared& sh, const PoseArgs& a, const Edges& e, bool lev
 		const double e0 = (double)e.keys[i].x - u, e1 = (double)e.keys[i].y - v;
 		const double w = a.invSigma2[oct];
 		const double c2 = e0 * (w * e0) + e1 * (w * e1);   // _error.dot(information() * _error)
-		double rho0, rho1;                                  // RobustKernelHuber::robustify
-		if (c2 <= dsqr) { rho0 = c2; rho1 = 1.0; }
-		else { const double sq = sqrt(c2); rho0 = 2 * sq * delta - dsqr; rho1 = delta / sq; }
+		double rho0, rho1;
+		huber_robustify(c2, delta, dsqr, rho0, rho1);
 		if constexpr (!Build) { (void)rho1; acc[0] += rho0; }
 		else {
 		double D[2][3], J[2][6];
@@ -168,7 +106,7 @@ __device__ void pass(PoseShared& sh, const PoseArgs& a, const Edges& e, bool lev
 		}
 	}
 	if (Build && bad) atomicOr(&sh.nonfinite, 1);
-	reduce_sums<Build ? kSums : 1>(sh, acc);
+	block_sums<Build ? kSums : 1>(acc, sh.red, sh.tot);
 }
 
 // :412-427 / :433-447: chi2 > thHuber2 of every edge still at level 0, at the estimate behind sh.inv
@@ -189,50 +127,6 @@ __device__ void outlier_pass(PoseShared& sh, const PoseArgs& a, const Edges& e, 
 	__syncthreads();
 }
 
-// unpivoted LDL^T of H + lambda I (H: upper triangle, row-major) and the solve; false as soon as a pivot is not > 0 (x is then left alone)
-__device__ __noinline__ bool ldlt6_solve(const double* Hu, double lambda, const double* b, double* x) {
-	double A[6][6], L[6][6], d[6], y[6];
-	int s = 0;
-#pragma unroll
-	for (int r = 0; r < 6; ++r)
-#pragma unroll
-		for (int q = r; q < 6; ++q) { A[r][q] = A[q][r] = Hu[s++]; }
-#pragma unroll
-	for (int r = 0; r < 6; ++r) A[r][r] = A[r][r] + lambda;
-#pragma unroll
-	for (int j = 0; j < 6; ++j) {
-		double t = A[j][j];
-#pragma unroll
-		for (int k = 0; k < j; ++k) t -= L[j][k] * L[j][k] * d[k];
-		if (!(t > 0.0)) return false;
-		d[j] = t;
-#pragma unroll
-		for (int i = j + 1; i < 6; ++i) {
-			double u = A[i][j];
-#pragma unroll
-			for (int k = 0; k < j; ++k) u -= L[i][k] * L[j][k] * d[k];
-			L[i][j] = u / t;
-		}
-	}
-#pragma unroll
-	for (int i = 0; i < 6; ++i) {
-		double t = b[i];
-#pragma unroll
-		for (int k = 0; k < i; ++k) t -= L[i][k] * y[k];
-		y[i] = t;
-	}
-#pragma unroll
-	for (int i = 0; i < 6; ++i) y[i] = y[i] / d[i];
-#pragma unroll
-	for (int i = 5; i >= 0; --i) {
-		double t = y[i];
-#pragma unroll
-		for (int k = i + 1; k < 6; ++k) t -= L[k][i] * x[k];
-		x[i] = t;
-	}
-	return true;
-}
-
 __global__ void __launch_bounds__(kPoseThreads) k_poseopt(PoseArgs a, PoseChunk ch, int first) {
 	__shared__ PoseShared sh;
 	const int tid = threadIdx.x, lp = blockIdx.x, gp = first + lp, nr = a.nrCams;
@@ -243,7 +137,7 @@ __global__ void __launch_bounds__(kPoseThreads) k_poseopt(PoseArgs a, PoseChunk 
 		const mcs_ocam& m = a.cams[tid];
 		const OcamDev o = ocam_dev_of(m);
 		sh.cam[tid] = o;
-		for (int k = 0; k < MCS_MAX_POLY; ++k) sh.dInvP[tid][k] = k + 1 < o.invP_deg ? m.invP[k + 1] * (double)(k + 1) : 0.0;
+		ocam_dinvp(m, o, sh.dInvP[tid]);
 		cayley2hom(a.McMin + 6 * tid, sh.McH[tid]);
 	}
 	if (tid == 0) {
@@ -264,14 +158,15 @@ __global__ void __launch_bounds__(kPoseThreads) k_poseopt(PoseArgs a, PoseChunk 
 	const double delta = 1.345 * a.huber[gp], dsqr = delta * delta, th2 = delta * delta;
 	// lane 0's state
 	int status = MCS_POSE_OK, iters[2] = {0, 0}, stop[2] = {STOP_NOT_RUN, STOP_NOT_RUN}, trials[2][10] = {};
-	double lambda = -1.0, ni = 2.0, lastChi = 0.0;
+	LmState lm{};
+	lm.lambda = -1.0; lm.ni = 2.0;
 	bool stopFlag = false;
 
 	if (nInit > 0) {   // uniform
 		for (int rnd = 0; rnd < 2; ++rnd) {
 			const int nAct = nInit - sh.nBad;   // round 1: the edges the first outlier pass left at level 0
 			bool resultOk = true;
-			int it = 0, lmBad = 0, why = stopFlag || nAct == 0 ? STOP_NOT_RUN : STOP_ITERATIONS;
+			int it = 0, why = stopFlag || nAct == 0 ? STOP_NOT_RUN : STOP_ITERATIONS;
 			if (tid == 0) for (int k = 0; k < 6; ++k) sh.x[k] = 0.0;   // Solver::resize: zeros
 			while (true) {
 				if (tid == 0) sh.go = it < 10 && !stopFlag && resultOk && nAct > 0;
@@ -286,25 +181,19 @@ __global__ void __launch_bounds__(kPoseThreads) k_poseopt(PoseArgs a, PoseChunk 
 					for (int k = 0; k < kSums; ++k) nf |= !finite_(sh.tot[k]);
 					if (nf) { status = MCS_POSE_NONFINITE; break; }   // uniform: not optimised
 				}
-				double currentChi = 0, iniChi = 0, rho = 0, postChi = 0;
-				int qmax = 0;
+				lm_iter_begin(lm, sh.tot[27]);   // every thread: written by lane 0 alone, the iteration's values would stay live around the loop in the others
+				lm.rho = 0.0;                    // solve()'s "double rho=0;", for the same reason: lm_trial writes it before anything reads it
 				if (tid == 0) {
 					for (int k = 0; k < 21; ++k) sh.H[k] = sh.tot[k];
 					for (int k = 0; k < 6; ++k) sh.b[k] = sh.tot[21 + k];
-					currentChi = iniChi = postChi = sh.tot[27];
-					if (it == 0) {   // computeLambdaInit: tau * max |H_jj|
-						double m = 0.0;
-						int s = 0;
-						for (int r = 0; r < 6; ++r) { m = fmax(fabs(sh.H[s]), m); s += 6 - r; }
-						lambda = 1e-5 * m; ni = 2.0; lmBad = 0;
-					}
+					if (it == 0) lm_start(lm, lm_lambda_init(max_abs_diag<6>(sh.H, 0.0)));
 				}
 				while (true) {
 					bool ok2 = true;
 					if (tid == 0) {
 						double x[6];
 						for (int k = 0; k < 6; ++k) { x[k] = sh.x[k]; sh.backup[k] = sh.pose[k]; }   // push
-						ok2 = ldlt6_solve(sh.H, lambda, sh.b, x);
+						ok2 = ldlt_solve<6>(sh.H, lm.lambda, sh.b, x);
 						for (int k = 0; k < 6; ++k) { sh.x[k] = x[k]; sh.pose[k] = sh.pose[k] + x[k]; }   // oplus, with the stale x after a failed solve
 					}
 					__syncthreads();
@@ -313,44 +202,20 @@ __global__ void __launch_bounds__(kPoseThreads) k_poseopt(PoseArgs a, PoseChunk 
 					pass<false>(sh, a, e, rnd == 1, delta, dsqr);
 					if (tid == 0) {
 						const double rawChi = sh.tot[0];
-						double tempChi = ok2 ? rawChi : DBL_MAX;
-						rho = currentChi - tempChi;
-						double scale = 0.0;
-						for (int j = 0; j < 6; ++j) scale += sh.x[j] * (lambda * sh.x[j] + sh.b[j]);
-						scale += 1e-3;
-						rho /= scale;
-						if (rho > 0 && finite_(tempChi)) {
-							double alpha = 1. - pow(2 * rho - 1, 3.0);
-							alpha = fmin(alpha, 2. / 3.);
-							lambda *= fmax(1. / 3., alpha);
-							ni = 2;
-							currentChi = tempChi;
-							postChi = rawChi;
-						} else {
-							lambda *= ni;
-							ni *= 2;
-							for (int k = 0; k < 6; ++k) sh.pose[k] = sh.backup[k];   // pop
-						}
-						++qmax;
-						sh.cont = rho < 0 && qmax < 10 && !stopFlag;
+						double scale = 0.0;   // computeScale: the six of x and b
+						for (int j = 0; j < 6; ++j) scale += sh.x[j] * (lm.lambda * sh.x[j] + sh.b[j]);
+						if (lm_trial(lm, rawChi, ok2, scale)) lm.postChi = rawChi;   // an accepted trial's pass evaluated the estimate the action will judge
+						else for (int k = 0; k < 6; ++k) sh.pose[k] = sh.backup[k];   // pop
+						sh.cont = lm_more(lm) && !stopFlag;
 					}
 					__syncthreads();
 					if (!sh.cont) break;
 				}
 				if (tid == 0) {
-					trials[rnd][it] = qmax;
-					if (qmax == 10 || rho == 0) { resultOk = false; why = STOP_TRIALS; }
-					else {
-						lmBad = (iniChi - currentChi) * 1e3 < iniChi ? lmBad + 1 : 0;
-						if (lmBad >= 3) { resultOk = false; why = STOP_NBAD; }
-					}
+					trials[rnd][it] = lm.qmax;
+					if (const int end = lm_iter_end(lm)) { resultOk = false; why = end; }
 					// ---- postIteration(it): the terminate action, on the errors of the current estimate (postChi: the chi2 of the pass that evaluated it)
-					if (it == 0) lastChi = postChi;
-					else {
-						const double gain = (lastChi - postChi) / postChi;
-						lastChi = postChi;
-						if (gain >= 0 && gain < 1e-6) { stopFlag = true; if (resultOk) why = STOP_GAIN; }   // never cleared: this g2o has no iteration -1 call
-					}
+					if (lm_gain_stop(lm, it)) { stopFlag = true; if (resultOk) why = STOP_GAIN; }   // never cleared: this g2o has no iteration -1 call
 				}
 				++it;
 			}
@@ -383,7 +248,7 @@ __global__ void __launch_bounds__(kPoseThreads) k_poseopt(PoseArgs a, PoseChunk 
 			mcs_pose_diag& g = a.diag[gp];
 			g.status = status; g.pad = 0;
 			for (int r = 0; r < 2; ++r) { g.iters[r] = iters[r]; g.stop[r] = stop[r]; for (int k = 0; k < 10; ++k) g.trials[r][k] = trials[r][k]; }
-			g.lambda = nInit > 0 && status == MCS_POSE_OK ? lambda : 0.0; g.chi2 = status == MCS_POSE_OK ? lastChi : 0.0;
+			g.lambda = nInit > 0 && status == MCS_POSE_OK ? lm.lambda : 0.0; g.chi2 = status == MCS_POSE_OK ? lm.lastChi : 0.0;
 		}
 	}
 }

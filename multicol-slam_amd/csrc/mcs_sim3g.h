@@ -17,6 +17,10 @@ namespace mcs {
 // Quaterniond r (coeffs() order: x y z w), Vector3d t, double s: the members of g2o::Sim3, in the order of its operator[] (sim3.h:239-250)
 struct Sim3g { double q[4]; double t[3]; double s; };
 
+// the eight doubles of a Sim3 in memory (S12, Scw, Snc of include/mcs_c.h): q (x y z w), t, s
+MCS_GEOM Sim3g sim3_load(const double* p) { Sim3g S; S.q[0] = p[0]; S.q[1] = p[1]; S.q[2] = p[2]; S.q[3] = p[3]; S.t[0] = p[4]; S.t[1] = p[5]; S.t[2] = p[6]; S.s = p[7]; return S; }
+MCS_GEOM void sim3_store(const Sim3g& S, double* p) { p[0] = S.q[0]; p[1] = S.q[1]; p[2] = S.q[2]; p[3] = S.q[3]; p[4] = S.t[0]; p[5] = S.t[1]; p[6] = S.t[2]; p[7] = S.s; }
+
 // Quaternion(const MatrixBase&) for a 3x3: quaternionbase_assign_impl<Other,3,3>::run (Quaternion.h:720-759), Shoemake.  R row-major.
 // mat.trace() is diagonal().sum(): Eigen's unrolled scalar redux halves the range (Core/Redux.h:77-90), so it is m00 + (m11 + m22).
 MCS_GEOM void quat_from_mat(const double* R, double* q) {

@@ -1,6 +1,7 @@
 // mcs_sim3opt.hip — cOptimizer::OptimizeSim3 (src/cOptimizerLoopStuff.cpp:58-264) for a batch of independent loop candidates: one workgroup per problem, both
 // rounds of the reference's g2o run in one launch, and the entry point mcs_sim3_optimize (include/mcs_c.h).  DESIGN.md 4m; the statement-by-statement
-// restatement the kernel is held to is tests/sim3opt_model.py.  The Sim3 arithmetic is csrc/mcs_sim3g.h, the camera and the matrices csrc/mcs_geom.h.
+// restatement the kernel is held to is tests/sim3opt_model.py.  The Sim3 arithmetic is csrc/mcs_sim3g.h, the camera and the matrices csrc/mcs_geom.h, the
+// Levenberg-Marquardt steps, the Huber pair, the 7x7 solve and the ordered sums csrc/mcs_lm.h.
 //
 // The correspondences are strided over the threads: thread t owns correspondences t, t + kSim3OptThreads, ... in every pass and adds them in ascending order,
 // edge e12 before edge e21 (the order of the optimiser's active edges).  A pass reduces within a wave by shuffles, then across the waves through LDS in wave
@@ -16,7 +17,7 @@
 #include "mcs_sim3opt.h"
 #include "mcs_geom.h"
 #include "mcs_sim3g.h"
-#include <cfloat>
+#include "mcs_lm.h"
 
 using namespace mcs;
 
@@ -25,7 +26,6 @@ namespace {
 constexpr int kWaves = kSim3OptThreads / 64;
 constexpr int kSums = 36;   // 28 of H (upper triangle, row-major), 7 of b, 1 of the robust chi2
 constexpr int kEst = 15;    // S, then Sim3(+delta e_d) * S and Sim3(-delta e_d) * S for d = 0..6
-enum { STOP_ITERATIONS = 0, STOP_GAIN = 1, STOP_TRIALS = 2, STOP_NBAD = 3, STOP_NOT_RUN = 4 };
 
 struct Sim3Shared {
 	OcamDev cam[32];
@@ -43,8 +43,6 @@ struct Sim3Shared {
 
 struct Corr { const double* Xw; const int* cam; const double* obs; const double* w; uint8_t* keep; int n; };
 
-__device__ __forceinline__ bool finite_(double v) { return fabs(v) <= DBL_MAX; }
-
 __device__ __forceinline__ bool pair_of(const Corr& e, int nr, int i, int& c1, int& c2) {
 	c1 = e.cam[2 * i]; c2 = e.cam[2 * i + 1];
 	return c1 >= 0 && c1 < nr && c2 >= 0 && c2 < nr;
@@ -57,26 +55,6 @@ __device__ __forceinline__ void edge_error(const Sim3Shared& sh, const Sim3g& S,
 	matx44_point<3>(sh.invMc[c], v, p);
 	omni_world_to_img(sh.cam[c], p[0], p[1], p[2], u, vv);
 	e0 = ox - u; e1 = oy - vv;
-}
-
-// wave shuffles, then the waves in order: tot[0..N) on every thread after the closing barrier
-template <int N>
-__device__ void reduce_sums(Sim3Shared& sh, double* acc) {
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-	for (int k = 0; k < N; ++k) {
-		double v = acc[k];
-#pragma unroll
-		for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-		if (lane == 0) sh.red[wave][k] = v;
-	}
-	__syncthreads();
-	if (threadIdx.x < N) {
-		double t = sh.red[0][threadIdx.x];
-		for (int w = 1; w < kWaves; ++w) t += sh.red[w][threadIdx.x];
-		sh.tot[threadIdx.x] = t;
-	}
-	__syncthreads();
 }
 
 // the estimates of a pass, from sh.S: Build: all fifteen and their inverses (lanes 0..14), else the estimate and its inverse (lane 0).  Barrier behind it.
@@ -119,9 +97,8 @@ __device__ void pass(Sim3Shared& sh, const Corr& e, int nr, double delta, double
 			double e0, e1;
 			edge_error(sh, Es[0], P, c, ox, oy, e0, e1);
 			const double c2 = e0 * (w * e0) + e1 * (w * e1);   // _error.dot(information() * _error)
-			double rho0, rho1;                                  // RobustKernelHuber::robustify
-			if (c2 <= dsqr) { rho0 = c2; rho1 = 1.0; }
-			else { const double sq = sqrt(c2); rho0 = 2 * sq * delta - dsqr; rho1 = delta / sq; }
+			double rho0, rho1;
+			huber_robustify(c2, delta, dsqr, rho0, rho1);
 			if constexpr (!Build) { (void)rho1; acc[0] += rho0; }
 			else {
 			const double scalar = 1.0 / (2 * 1e-9);
@@ -153,7 +130,7 @@ __device__ void pass(Sim3Shared& sh, const Corr& e, int nr, double delta, double
 		}
 	}
 	if (Build && bad) atomicOr(&sh.nonfinite, 1);
-	reduce_sums<Build ? kSums : 1>(sh, acc);
+	block_sums<Build ? kSums : 1>(acc, sh.red, sh.tot);
 }
 
 // :206-226 / :241-257: a correspondence is bad if EITHER edge has chi2 > deltaHuber2, at the estimate in sh.E[0] / sh.Einv[0]
@@ -175,51 +152,6 @@ __device__ void outlier_pass(Sim3Shared& sh, const Corr& e, int nr, double dsqr)
 	}
 	if (nbad) atomicAdd(&sh.nBad, nbad);
 	__syncthreads();
-}
-
-// unpivoted LDL^T of H + lambda I (H: upper triangle, row-major) and the solve; false as soon as a pivot is not > 0 (x is then left alone)
-__device__ __noinline__ bool ldlt7_solve(const double* Hu, double lambda, const double* b, double* x) {
-	constexpr int N = 7;
-	double A[N][N], L[N][N], d[N], y[N];
-	int s = 0;
-#pragma unroll
-	for (int r = 0; r < N; ++r)
-#pragma unroll
-		for (int q = r; q < N; ++q) { A[r][q] = A[q][r] = Hu[s++]; }
-#pragma unroll
-	for (int r = 0; r < N; ++r) A[r][r] = A[r][r] + lambda;
-#pragma unroll
-	for (int j = 0; j < N; ++j) {
-		double t = A[j][j];
-#pragma unroll
-		for (int k = 0; k < j; ++k) t -= L[j][k] * L[j][k] * d[k];
-		if (!(t > 0.0)) return false;
-		d[j] = t;
-#pragma unroll
-		for (int i = j + 1; i < N; ++i) {
-			double u = A[i][j];
-#pragma unroll
-			for (int k = 0; k < j; ++k) u -= L[i][k] * L[j][k] * d[k];
-			L[i][j] = u / t;
-		}
-	}
-#pragma unroll
-	for (int i = 0; i < N; ++i) {
-		double t = b[i];
-#pragma unroll
-		for (int k = 0; k < i; ++k) t -= L[i][k] * y[k];
-		y[i] = t;
-	}
-#pragma unroll
-	for (int i = 0; i < N; ++i) y[i] = y[i] / d[i];
-#pragma unroll
-	for (int i = N - 1; i >= 0; --i) {
-		double t = y[i];
-#pragma unroll
-		for (int k = i + 1; k < N; ++k) t -= L[k][i] * x[k];
-		x[i] = t;
-	}
-	return true;
 }
 
 __global__ void __launch_bounds__(kSim3OptThreads) k_sim3opt(Sim3OptArgs a, Sim3OptChunk ch, int first) {
@@ -252,14 +184,15 @@ __global__ void __launch_bounds__(kSim3OptThreads) k_sim3opt(Sim3OptArgs a, Sim3
 	const double delta = 1.345 * a.stdSim[gp], dsqr = delta * delta;   // deltaHuber, deltaHuber2 (:109-110)
 	// lane 0's state
 	int status = MCS_SIM3OPT_OK, iters[2] = {0, 0}, stop[2] = {STOP_NOT_RUN, STOP_NOT_RUN}, trials[2][10] = {}, nBad1 = 0;
-	double lambda = -1.0, ni = 2.0, lastChi = 0.0;
+	LmState lm{};
+	lm.lambda = -1.0; lm.ni = 2.0;
 	bool stopFlag = false, returned0 = nC == 0;   // no correspondence: optimize() returns before its loop, then 0 - 0 < 3
 
 	if (nC > 0) {   // uniform
 		for (int rnd = 0; rnd < 2; ++rnd) {
 			const int maxIt = rnd == 0 || nBad1 == 0 ? 5 : 10;   // optimize(5); nMoreIterations (:228-232)
 			bool resultOk = true;
-			int it = 0, lmBad = 0, why = stopFlag ? STOP_NOT_RUN : STOP_ITERATIONS;
+			int it = 0, why = stopFlag ? STOP_NOT_RUN : STOP_ITERATIONS;
 			if (tid == 0) for (int k = 0; k < 7; ++k) sh.x[k] = 0.0;   // Solver::resize: zeros
 			while (true) {
 				if (tid == 0) sh.go = it < maxIt && !stopFlag && resultOk;
@@ -273,18 +206,12 @@ __global__ void __launch_bounds__(kSim3OptThreads) k_sim3opt(Sim3OptArgs a, Sim3
 					for (int k = 0; k < kSums; ++k) nf |= !finite_(sh.tot[k]);
 					if (nf) { status = MCS_SIM3OPT_NONFINITE; break; }   // uniform: not optimised
 				}
-				double currentChi = 0, iniChi = 0, rho = 0, postChi = 0;
-				int qmax = 0;
+				lm_iter_begin(lm, sh.tot[35]);   // every thread: written by lane 0 alone, the iteration's values would stay live around the loop in the others
+				lm.rho = 0.0;                    // solve()'s "double rho=0;", for the same reason: lm_trial writes it before anything reads it
 				if (tid == 0) {
 					for (int k = 0; k < 28; ++k) sh.H[k] = sh.tot[k];
 					for (int k = 0; k < 7; ++k) sh.b[k] = sh.tot[28 + k];
-					currentChi = iniChi = postChi = sh.tot[35];
-					if (it == 0) {   // computeLambdaInit: tau * max |H_jj|
-						double m = 0.0;
-						int s = 0;
-						for (int r = 0; r < 7; ++r) { m = fmax(fabs(sh.H[s]), m); s += 7 - r; }
-						lambda = 1e-5 * m; ni = 2.0; lmBad = 0;
-					}
+					if (it == 0) lm_start(lm, lm_lambda_init(max_abs_diag<7>(sh.H, 0.0)));
 				}
 				while (true) {
 					bool ok2 = true;
@@ -292,7 +219,7 @@ __global__ void __launch_bounds__(kSim3OptThreads) k_sim3opt(Sim3OptArgs a, Sim3
 						double x[7];
 						for (int k = 0; k < 7; ++k) x[k] = sh.x[k];
 						sh.backup = sh.S;   // push
-						ok2 = ldlt7_solve(sh.H, lambda, sh.b, x);
+						ok2 = ldlt_solve<7>(sh.H, lm.lambda, sh.b, x);
 						for (int k = 0; k < 7; ++k) sh.x[k] = x[k];
 						sh.S = sim3_mul(sim3_exp(x), sh.S);   // oplusImpl: Sim3(update) * estimate, with the stale x after a failed solve
 					}
@@ -301,44 +228,20 @@ __global__ void __launch_bounds__(kSim3OptThreads) k_sim3opt(Sim3OptArgs a, Sim3
 					pass<false>(sh, e, nr, delta, dsqr);
 					if (tid == 0) {
 						const double rawChi = sh.tot[0];
-						double tempChi = ok2 ? rawChi : DBL_MAX;
-						rho = currentChi - tempChi;
-						double scale = 0.0;
-						for (int j = 0; j < 7; ++j) scale += sh.x[j] * (lambda * sh.x[j] + sh.b[j]);
-						scale += 1e-3;
-						rho /= scale;
-						if (rho > 0 && finite_(tempChi)) {
-							double alpha = 1. - pow(2 * rho - 1, 3.0);
-							alpha = fmin(alpha, 2. / 3.);
-							lambda *= fmax(1. / 3., alpha);
-							ni = 2;
-							currentChi = tempChi;
-							postChi = rawChi;
-						} else {
-							lambda *= ni;
-							ni *= 2;
-							sh.S = sh.backup;   // pop
-						}
-						++qmax;
-						sh.cont = rho < 0 && qmax < 10 && !stopFlag;
+						double scale = 0.0;   // computeScale: the seven of x and b
+						for (int j = 0; j < 7; ++j) scale += sh.x[j] * (lm.lambda * sh.x[j] + sh.b[j]);
+						if (lm_trial(lm, rawChi, ok2, scale)) lm.postChi = rawChi;   // an accepted trial's pass evaluated the estimate the action will judge
+						else sh.S = sh.backup;   // pop
+						sh.cont = lm_more(lm) && !stopFlag;
 					}
 					__syncthreads();
 					if (!sh.cont) break;
 				}
 				if (tid == 0) {
-					trials[rnd][it] = qmax;
-					if (qmax == 10 || rho == 0) { resultOk = false; why = STOP_TRIALS; }
-					else {
-						lmBad = (iniChi - currentChi) * 1e3 < iniChi ? lmBad + 1 : 0;
-						if (lmBad >= 3) { resultOk = false; why = STOP_NBAD; }
-					}
+					trials[rnd][it] = lm.qmax;
+					if (const int end = lm_iter_end(lm)) { resultOk = false; why = end; }
 					// ---- postIteration(it): the terminate action, on the errors of the current estimate (postChi: the chi2 of the pass that evaluated it)
-					if (it == 0) lastChi = postChi;
-					else {
-						const double gain = (lastChi - postChi) / postChi;
-						lastChi = postChi;
-						if (gain >= 0 && gain < 1e-6) { stopFlag = true; if (resultOk) why = STOP_GAIN; }   // never cleared: this g2o has no iteration -1 call
-					}
+					if (lm_gain_stop(lm, it)) { stopFlag = true; if (resultOk) why = STOP_GAIN; }   // never cleared: this g2o has no iteration -1 call
 				}
 				++it;
 			}
@@ -357,17 +260,14 @@ __global__ void __launch_bounds__(kSim3OptThreads) k_sim3opt(Sim3OptArgs a, Sim3
 	__syncthreads();
 	if (tid == 0) {   // a non-finite problem left the screen before any keep byte was cleared
 		const Sim3g So = status == MCS_SIM3OPT_OK && !returned0 ? sh.S : Sin;
-		double* o = a.S12 + 8 * (size_t)gp;
-		for (int k = 0; k < 4; ++k) o[k] = So.q[k];
-		for (int k = 0; k < 3; ++k) o[4 + k] = So.t[k];
-		o[7] = So.s;
+		sim3_store(So, a.S12 + 8 * (size_t)gp);
 		if (a.R12out) quat_to_mat(So.q, a.R12out + 9 * (size_t)gp);
 		a.nInliers[gp] = status != MCS_SIM3OPT_OK ? nC : returned0 ? 0 : nC - sh.nBad;
 		if (a.diag) {
 			mcs_sim3opt_diag& g = a.diag[gp];
 			g.status = status; g.n_corr = nC; g.n_bad1 = status == MCS_SIM3OPT_OK ? nBad1 : 0; g.pad = 0;
 			for (int r = 0; r < 2; ++r) { g.iters[r] = iters[r]; g.stop[r] = stop[r]; for (int k = 0; k < 10; ++k) g.trials[r][k] = trials[r][k]; }
-			g.lambda = nC > 0 && status == MCS_SIM3OPT_OK ? lambda : 0.0; g.chi2 = status == MCS_SIM3OPT_OK ? lastChi : 0.0;
+			g.lambda = nC > 0 && status == MCS_SIM3OPT_OK ? lm.lambda : 0.0; g.chi2 = status == MCS_SIM3OPT_OK ? lm.lastChi : 0.0;
 		}
 	}
 }

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""One SHA-256 per entry point and memory kind over every output byte of the calls that go through csrc/mcs_geom.h, on the small scenes the tests already
-have (tests/poseopt_scenes.py, the hostile tables for new points, Sim3 and windows, tests/frustum_pack.py, tests/lastframe_scene.py).  Nothing is asserted:
+"""One SHA-256 per entry point and memory kind over every output byte of the calls that go through csrc/mcs_geom.h and csrc/mcs_lm.h, on the small scenes
+the tests already have (tests/poseopt_scenes.py, sim3opt_scenes.py, lba_scenes.py, essgraph_scenes.py, the hostile tables for new points, Sim3 and windows,
+tests/frustum_pack.py, tests/lastframe_scene.py).  Nothing is asserted:
 the lines of two libraries (MCS_HIP_LIB selects one) are compared with diff.  Equal lines from two processes of one library show the outputs do not depend on
 the process; equal lines from two libraries show a refactor of the shared arithmetic changed no output bit.  One process, a few seconds on an MI355X."""
 import ctypes as C
@@ -15,14 +16,17 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import gpu_common as G   # noqa: E402
+import essgraph_scenes as ES   # noqa: E402
 import frustum_model as FM   # noqa: E402
 import frustum_pack   # noqa: E402
 import hostile_newpoints as HN   # noqa: E402
 import hostile_sim3 as HS   # noqa: E402
 import hostile_windows as HW   # noqa: E402
 import lastframe_scene as LS   # noqa: E402
+import lba_scenes as LBS   # noqa: E402
 import newpoints_pack as NP   # noqa: E402
 import poseopt_scenes as PS   # noqa: E402
+import sim3opt_scenes as SS   # noqa: E402
 import window_pack as WP   # noqa: E402
 from test_gpu_lastframe import Call as TrackCall   # noqa: E402
 from test_gpu_sim3 import Batch   # noqa: E402
@@ -165,10 +169,35 @@ def pose_optimization(ctx):
         line("mcs_pose_optimization", kind, [[g[k] for k in ("pose", "MtMc", "MtMc_inv", "outlier", "diag", "n_inliers", "share")] for g in got])
 
 
+def sim3_optimize(ctx):
+    """the sizes up to the stride of a workgroup and a scene per path, a call of its own each; every output array and the diag record"""
+    names = [n for n in SS.SIZES if SS.SIZES[n]["n"] <= SS.T + 1] + list(SS.PATHS)
+    for device, kind in KINDS:
+        got = [SS.run_library(pkg, ctx, [SS.build(n)], device) for n in names]
+        assert all(isinstance(g, list) for g in got), got
+        line("mcs_sim3_optimize", kind, [[g[0][k] for k in ("S12", "R12", "keep", "n_inliers", "diag")] for g in got])
+
+
+def local_bundle_adjustment(ctx):
+    names = ("pair", "window", "twice", "split")
+    for device, kind in KINDS:
+        got = [LBS.run_library(pkg, ctx, LBS.build(n), device) for n in names]
+        assert all(isinstance(g, dict) for g in got), got
+        line("mcs_local_bundle_adjustment", kind, [[g[k] for k in ("status", "kf_pose", "kf_t", "pos", "edge_state", "pt_state", "diag")] for g in got])
+
+
+def optimize_essential_graph(ctx):
+    names = ("chain6", "dup", "isolated", "fixed_mid")
+    for device, kind in KINDS:
+        got = [ES.run_library(pkg, ctx, ES.build(n), device) for n in names]
+        assert all(isinstance(g, dict) for g in got), got
+        line("mcs_optimize_essential_graph", kind, [[g[k] for k in ("status", "Scw_out", "pose", "kf_t", "pos", "diag")] for g in got])
+
+
 def main():
     print("library: %s" % os.path.basename(os.path.dirname(os.path.abspath(pkg._capi.LIB_PATH))), file=sys.stderr)
     ctx = G.ctx()
-    for part in (world_to_cam, local_points, track, new_points, sim3, pose_optimization):
+    for part in (world_to_cam, local_points, track, new_points, sim3, pose_optimization, sim3_optimize, local_bundle_adjustment, optimize_essential_graph):
         part(ctx)
 
 
